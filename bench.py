@@ -46,8 +46,8 @@ for p in (os.path.join(ROOT, "rust-ida_amd"), os.path.join(ROOT, "tests")):
 
 import numpy as np  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec (/opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured copy)
-VALU_FMA_TFLOPS = 78.6       # fp64 vector peak with FMA = 1/2 x 157.3 TFLOP/s fp32 vector (same guide), 2.4 GHz
+HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec (8.0 TB/s; a plain copy measures 6.29 TB/s)
+VALU_FMA_TFLOPS = 78.6       # fp64 vector peak with FMA = 1/2 x 157.3 TFLOP/s fp32 vector (MI355X spec), 2.4 GHz
 VALU_UNFUSED_TFLOPS = 39.3   # a multiply and a subtract per update (the reference's arithmetic, dense.rs:151): half of it
 PMC_SUMMARY = os.path.join("profiles", "r05_bench_summary.json")  # committed rocprofv3 --pmc passes of this command
 
@@ -313,6 +313,46 @@ def cpu_baseline(prob_small, cores):
                          iters, seconds)}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
+DUMP_REALS = ("tn", "hused")
+DUMP_COUNTERS = ("nst", "nni", "nsetups", "netf", "ncfn", "kused")
+
+
+def dump_rows(total, n, limit=DUMP_LIMIT_BYTES):
+    """Global ids of the systems `--dump-outputs` writes: all of them when their arrays fit in `limit` bytes, otherwise a sorted
+    sample drawn with a fixed seed, so that every run with the same arguments writes the same systems."""
+    per_system = 8 * (2 * n + 1 + len(DUMP_REALS) + len(DUMP_COUNTERS))  # yy, yp, the system's id, reals and counters, all float64
+    m = min(total, limit // per_system)
+    if m >= total:
+        return np.arange(total)
+    return np.sort(np.random.default_rng(0).choice(total, size=m, replace=False))
+
+
+def stream_outputs(enss, first, rows):
+    """What a caller of the timed path (idaens_stream) receives after its last round, for the systems among `rows` (global ids) that
+    this rank holds (the groups' ensembles in order hold systems first, first + 1, ...): y and y' of the system, its current time tn,
+    its last step size, its counters, all float64."""
+    count = sum(e.ctx.batch for e in enss)
+    mine = rows[(rows >= first) & (rows < first + count)]
+    loc = mine - first
+    cat = lambda get: np.concatenate([get(e) for e in enss])[loc].astype(np.float64)
+    out = {"system": mine.astype(np.float64), "yy": cat(lambda e: e.yy()), "yp": cat(lambda e: e.yp())}
+    out.update({k: cat(lambda e, k=k: e.real(k)) for k in DUMP_REALS})
+    out.update({k: cat(lambda e, k=k: e.counter(k)) for k in DUMP_COUNTERS})
+    return out
+
+
+def write_outputs(d, parts):
+    """Rank blocks of stream_outputs, concatenated in rank (= global system) order, as d/<name>.npy. -> bytes written."""
+    os.makedirs(d, exist_ok=True)
+    nbytes = 0
+    for k in parts[0]:
+        a = np.ascontiguousarray(np.concatenate([p[k] for p in parts]))
+        np.save(os.path.join(d, k + ".npy"), a)
+        nbytes += a.nbytes
+    return nbytes
+
+
 def inputs_only(args, rank, world, first, count, procs):
     """`--inputs-only`: what an N-rank start costs the HOST before the first barrier -- every rank generates its shard exactly as
     the bench does (slice by slice; the upload is left out), rank 0 collects every rank's record and prints one JSON line. No GPU, no torch."""
@@ -414,10 +454,16 @@ def main():
     ap.add_argument("--results-npz", default=None,
                     help="rank 0 writes the concatenated per-system results of the ensemble's verification pass (nst, nni, y(tout), y'(tout) in "
                          "global system order, SURVEY 8(e): 'host concatenates') to this file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed stream computed in its last step as DIR/<name>.npy (float64): y and y' "
+                         "of every system, its time tn, last step size hused and counters, and `system`, the global id of each row; at most "
+                         "64 MB, a fixed seeded sample of the systems when all of them would take more")
     ap.add_argument("--inputs-only", action="store_true",
                     help="host-side rehearsal of an N-rank start: every rank generates its shard (slice by slice, as for the upload), "
                          "rank 0 collects and prints seconds and peak resident memory per rank; no GPU is touched (torch is not imported)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     dn, db = {"linear_dense": (512, 4096), "heat1d": (4096, 256), "lorenz63": (3, 1024)}[args.workload]
     args.n = dn if args.n is None else args.n
     args.batch = db if args.batch is None else args.batch
@@ -548,6 +594,19 @@ def main():
     if world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, (int(iters), round(elapsed, 6)))
+    # ---- --dump-outputs: the stream's state after its last timed round, before anything below continues the stream or reuses its
+    # device contexts
+    dump = None
+    if args.dump_outputs:
+        rows = dump_rows(args.batch * world, args.n)
+        block = stream_outputs(run.enss, first, rows)
+        parts = [block]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, block)
+        if rank == 0:
+            dump = {"dir": args.dump_outputs, "systems": int(rows.size), "total_systems": args.batch * world,
+                    "bytes": write_outputs(args.dump_outputs, parts)}
 
     # ---- untimed repetitions of the same K steps with event timers: per kernel class, then per kernel of the LU
     tim = krun.timed_steps(args.steps, 1)
@@ -750,6 +809,8 @@ def main():
                 "frac_with_lsetup": None if r is None else out["value"] / (world * 8.0e12 / (it_bytes + ls_bytes / r)),
                 "note": "8 TB/s over the algorithmic bytes of BASELINE.md section 3; the factorisation itself is bound by the fp64 vector "
                         "pipe at this N, not by HBM (`roofline`, `lu_plus_solve`)"}
+        if dump:
+            out["dump_outputs"] = dump
         if extras:
             out.update(extras)
         if TIME_ALL:

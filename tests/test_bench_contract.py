@@ -36,7 +36,7 @@ def test_algorithmic_work_matches_the_design_document():
 def test_help_runs_without_gpu_or_torch():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--workload"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--dump-outputs"):
         assert flag in out.stdout
 
 
@@ -80,3 +80,53 @@ def test_eight_rank_start_rehearsed_on_the_host_side():
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["inputs_only"] and line["ranks"] == 8 and len(line["peak_rss_GiB_per_rank"]) == 8 and len(line["seconds_per_rank"]) == 8
     assert line["slices_per_rank"] >= 1 and line["seconds_until_every_rank_has_its_inputs_max"] >= 0.0
+
+
+def test_dump_outputs_stays_within_64_mb_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: every system while the arrays fit in 64 MB, otherwise the same seeded sample on every run; the groups' ensembles
+    are concatenated in system order and only the rank's own systems are taken."""
+    import numpy as np
+    b = load_bench()
+    assert np.array_equal(b.dump_rows(4096, 512), np.arange(4096))  # the headline workload is written whole (34 MB)
+    rows = b.dump_rows(1 << 20, 512)
+    assert np.array_equal(rows, b.dump_rows(1 << 20, 512)) and np.array_equal(rows, np.unique(rows)) and 0 < rows.size < 1 << 20
+
+    class Ctx:
+        def __init__(self, batch):
+            self.batch = batch
+
+    class Ens:  # the getters of idahip.Ensemble over systems first .. first + batch - 1 with n = 3
+        def __init__(self, first, batch):
+            self.ctx, self.ids = Ctx(batch), np.arange(first, first + batch)
+
+        def yy(self):
+            return np.repeat(self.ids[:, None], 3, axis=1) + np.array([0.0, 0.25, 0.5])
+
+        def yp(self):
+            return -self.yy()
+
+        def real(self, name):
+            return self.ids + 0.5
+
+        def counter(self, name):
+            return self.ids * 2
+
+    n, world, per_rank = 3, 2, 100
+    limit = 40 * 8 * (2 * n + 1 + len(b.DUMP_REALS) + len(b.DUMP_COUNTERS))  # room for 40 of the 200 systems
+    rows = b.dump_rows(world * per_rank, n, limit=limit)
+    assert rows.size == 40
+    # rank r holds systems [100 r, 100 r + 100) as two groups of 60 and 40
+    parts = [b.stream_outputs([Ens(per_rank * r, 60), Ens(per_rank * r + 60, 40)], per_rank * r, rows) for r in range(world)]
+    nbytes = b.write_outputs(str(tmp_path / "d"), parts)
+    assert nbytes <= limit
+    got = {f[:-4]: np.load(str(tmp_path / "d" / f)) for f in os.listdir(str(tmp_path / "d"))}
+    assert set(got) == {"system", "yy", "yp"} | set(b.DUMP_REALS) | set(b.DUMP_COUNTERS)
+    assert all(a.dtype == np.float64 and a.shape[0] == 40 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) == nbytes
+    assert np.array_equal(got["system"], rows)
+    assert np.array_equal(got["yy"][:, 0], rows) and np.array_equal(got["yp"], -got["yy"]) and np.array_equal(got["nni"], 2 * rows)
+
+
+def test_steps_below_one_are_refused():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr
