@@ -169,7 +169,7 @@ int idahip_newton_iter2(idahip_ctx* ctx, const double* hScale, const double* hTn
  * restore    : IDARestore's phi part, phi[j] *= cvals[j-ns], j = ns..kk (lib.rs:1057-1082). hCvals [nsys][6].
  * complete_step: phi[kused+1] = ee (if kused < maxord), the phi recurrence (impl_complete_step.rs:152-176), ee *= ck
  *              (lib.rs:708), then the next step's ewt_set(phi[0]) and tolsf norm (impl_solve.rs:266-295):
- *              hPhi0Nrm[s] = ||phi[0]||_wrms(ewt), hEwtBad[s] != 0 if some ewt component <= 0.
+ *              hPhi0Nrm[s] = ||phi[0]||_wrms(ewt), hEwtBad[s] != 0 if some ewt component <= 0 (a NaN is not).
  * get_solution: IDAGetSolution's linear combinations (lib.rs:1319-1340). hCvals [nsys][6], hDvals [nsys][5].       */
 int idahip_init_first(idahip_ctx* ctx, double* hYpnorm, double* hPhi0Nrm, const int32_t* hIdx, int nsys);
 int idahip_scale_phi1(idahip_ctx* ctx, const double* hFac, const int32_t* hIdx, int nsys);

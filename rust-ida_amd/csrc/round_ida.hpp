@@ -163,7 +163,7 @@ struct WgVec {
             a.v.ee[vb + i] = e * ck;
             const double w = ewt_of(a.v, tmp, i);
             a.v.ewt[vb + i] = w;
-            if (!(w > 0.0)) res()[1] = 1.0;
+            if (w <= 0.0) res()[1] = 1.0;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
             const double p = tmp * w;
             sm[i] = p * p;
         }

@@ -142,7 +142,7 @@ struct TinyVec {
             a.v.ee[vb + i] = e * ck;
             const double w = ewt_of(a.v, tmp, i);
             a.v.ewt[vb + i] = w;
-            if (!(w > 0.0)) bad = true;
+            if (w <= 0.0) bad = true;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
             const double p = tmp * w;
             acc = acc + p * p;
         }

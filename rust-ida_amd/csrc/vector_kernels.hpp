@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void complete_step_kernel(VecState s, const in
         s.ee[vb + i] = e * ck;
         const double w = ewt_of(s, tmp, i);  // tmp == new phi[0]
         s.ewt[vb + i] = w;
-        if (!(w > 0.0)) s_bad = 1;
+        if (w <= 0.0) s_bad = 1;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
         const double p = tmp * w;
         sm[i] = p * p;
     }

@@ -121,6 +121,8 @@ def load():
     H.idahip_complete_step.argtypes = [vp, i32p, dp, ci, dp, i32p, i32p, ci]
     H.idahip_get_solution.argtypes = [vp, i32p, dp, dp, i32p, ci]
     H.idahip_get_dky.argtypes = [vp, i32p, i32p, dp, dp, i32p, ci]
+    H.idahip_snapshot_initial.argtypes = [vp]
+    H.idahip_restore_initial.argtypes = [vp, i32p, ci]
     H.idahip_set_lu_variant.argtypes = [vp, ci]
     H.idahip_pow_batch.argtypes = [vp, dp, dp, dp, C.c_size_t]
     H.idahip_newton_iter2.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, i32p, i32p, ci]
@@ -344,6 +346,16 @@ class Ctx:
         self._chk(self.H.idahip_newton_iter(self.h, _p(scale), _p(out), _p(idx, i32p), idx.size), "newton_iter")
         return out
 
+    def newton_iter2(self, scale, tn, cj, toldel, ss, eps_newt, idx=None):
+        """The first two Newton iterations with their convergence tests on the device -> (delnrm [nsys][2], conv [nsys])."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        scale, tn, cj, toldel, ss, eps_newt = (_f64(np.broadcast_to(v, idx.shape)) for v in (scale, tn, cj, toldel, ss, eps_newt))
+        dn = np.zeros((idx.size, 2))
+        conv = np.zeros(idx.size, dtype=np.int32)
+        self._chk(self.H.idahip_newton_iter2(self.h, _p(scale), _p(tn), _p(cj), _p(toldel), _p(ss), _p(eps_newt), _p(dn),
+                                             _p(conv, i32p), _p(idx, i32p), idx.size), "newton_iter2")
+        return dn, conv
+
     # --- stepper vector ops
     def init_first(self, idx=None):
         idx = self.all_idx() if idx is None else _i32(idx)
@@ -393,6 +405,25 @@ class Ctx:
         cvals = _f64(np.broadcast_to(cvals, (idx.size, 6)))
         dvals = _f64(np.broadcast_to(dvals, (idx.size, 5)))
         self._chk(self.H.idahip_get_solution(self.h, _p(kord, i32p), _p(cvals), _p(dvals), _p(idx, i32p), idx.size), "get_solution")
+
+    def get_dky(self, kfirst, klast, cjk, idx=None):
+        """sum_{j = kfirst .. klast} cjk[j] * phi[j] of the listed systems -> [nsys][n]."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        kfirst = _i32(np.broadcast_to(kfirst, idx.shape))
+        klast = _i32(np.broadcast_to(klast, idx.shape))
+        cjk = _f64(np.broadcast_to(cjk, (idx.size, 6)))
+        out = np.zeros((idx.size, self.n))
+        self._chk(self.H.idahip_get_dky(self.h, _p(kfirst, i32p), _p(klast, i32p), _p(cjk), _p(out), _p(idx, i32p), idx.size), "get_dky")
+        return out
+
+    def snapshot_initial(self):
+        """Keep a device copy of every system's phi[0], phi[1] (Ida::new again: restore_initial)."""
+        self._chk(self.H.idahip_snapshot_initial(self.h), "snapshot_initial")
+
+    def restore_initial(self, idx=None):
+        """phi[0] = yy and phi[1] = yp of the listed systems back to the snapshot."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        self._chk(self.H.idahip_restore_initial(self.h, _p(idx, i32p), idx.size), "restore_initial")
 
     def pow_batch(self, x, y):
         """The device controller's pow (glibc_pow.hpp) for arrays of arguments."""
