@@ -10,8 +10,9 @@
  *   - all floating point is fp64; no FMA contraction anywhere (the reference is plain Rust arithmetic);
  *   - matrices are column-major per system, A(i,j) = a[j*n + i] (nalgebra layout of crates/linear/src/dense.rs);
  *   - "h" pointers are host memory, borrowed for the duration of the call; "d" pointers are device memory;
- *   - hIdx[0..nsys) lists the systems a call acts on (the reference acts on one `Ida` at a time); per-call scalar
- *     arguments (hTn, hCj, ...) are indexed by list position, not by system id;
+ *   - hIdx[0..nsys) lists the systems a call acts on (the reference acts on one `Ida` at a time), each at most once: a list
+ *     that names a system twice, or an id outside [0, batch), is refused (-2) before anything is uploaded or launched;
+ *     per-call scalar arguments (hTn, hCj, ...) are indexed by list position, not by system id;
  *   - return value: 0 ok; > 0 recoverable (some listed system flagged, see the per-system output); < 0 fatal
  *     (bad argument, HIP error) -- the taxonomy documented at crates/nonlinear/src/traits.rs:17-22;
  *   - nothing panics, throws or aborts across this boundary; idahip_last_error() describes the last failure;

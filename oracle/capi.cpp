@@ -99,6 +99,32 @@ extern "C" {
 
 int oracle_dense_getrf(double* a, int m, int n, int64_t* pivot) { return dense_get_rf(a, m, n, pivot); }
 void oracle_dense_getrs(const double* a, int n, const int64_t* pivot, double* b) { dense_get_rs(a, n, pivot, b); }
+// The same factorisation of `nsys` matrices [nsys][n*n] (column-major, in place), systems dealt round-robin to `nthreads`
+// std::threads: piv [nsys][n], info [nsys]. Each matrix goes through dense_get_rf unchanged, so the bits are those of a loop
+// over oracle_dense_getrf.
+void oracle_dense_getrf_batch(double* a, int n, int nsys, int64_t* pivot, int32_t* info, int nthreads) {
+    const size_t nn = (size_t)n * n;
+    if (nthreads < 1) nthreads = 1;
+    auto worker = [&](int tid) {
+        for (int s = tid; s < nsys; s += nthreads) info[s] = dense_get_rf(a + s * nn, n, n, pivot + (size_t)s * n);
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nthreads; ++t) th.emplace_back(worker, t);
+    worker(0);
+    for (auto& t : th) t.join();
+}
+// getrs of `nsys` systems [nsys][n*n] / [nsys][n] / rhs [nsys][n] (solution in place), over `nthreads` std::threads
+void oracle_dense_getrs_batch(const double* a, int n, int nsys, const int64_t* pivot, double* b, int nthreads) {
+    const size_t nn = (size_t)n * n;
+    if (nthreads < 1) nthreads = 1;
+    auto worker = [&](int tid) {
+        for (int s = tid; s < nsys; s += nthreads) dense_get_rs(a + s * nn, n, pivot + (size_t)s * n, b + (size_t)s * n);
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nthreads; ++t) th.emplace_back(worker, t);
+    worker(0);
+    for (auto& t : th) t.join();
+}
 double oracle_norm_wrms(const double* x, const double* w, int n) { return norm_wrms(x, w, n); }
 double oracle_norm_wrms_masked(const double* x, const double* w, const uint8_t* id, int n) { return norm_wrms_masked(x, w, id, n); }
 

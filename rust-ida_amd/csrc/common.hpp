@@ -109,6 +109,9 @@ struct idahip_ctx {
     double *cb_jpin = nullptr, *cb_jdev = nullptr;    // pinned / device staging of a chunk of user Jacobians (lazy)
     size_t cb_jcap = 0;                               // systems the two staging buffers hold
 
+    // check_list's map of the ids seen in one list: one bit per system, sized at idahip_create and all clear between calls
+    std::vector<uint64_t> list_seen;
+
     // staging ring
     idahip::Slot slots[idahip::NSLOT];
     size_t slot_cap = 0;

@@ -26,6 +26,16 @@ int check_list(idahip_ctx* c, const int32_t* hIdx, int nsys) {
     if (nsys > 0 && !hIdx) return fail(c, -2, "null system list");
     for (int s = 0; s < nsys; ++s)
         if (hIdx[s] < 0 || hIdx[s] >= c->batch) return fail(c, -2, "system id %d out of range at list position %d", hIdx[s], s);
+    // no id twice: two workgroups would factor one matrix in place, or update one system's vectors, at the same time
+    uint64_t* seen = c->list_seen.data();
+    int dup = -1;
+    for (int s = 0; s < nsys && dup < 0; ++s) {
+        const uint64_t bit = 1ull << (hIdx[s] & 63);
+        if (seen[hIdx[s] >> 6] & bit) dup = s;
+        seen[hIdx[s] >> 6] |= bit;
+    }
+    for (int s = 0; s < (dup < 0 ? nsys : dup); ++s) seen[hIdx[s] >> 6] = 0;  // leave the map clear for the next call
+    if (dup >= 0) return fail(c, -2, "system id %d listed twice (again at list position %d)", hIdx[dup], dup);
     return 0;
 }
 
@@ -75,6 +85,7 @@ int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem
     idahip_ctx* c = new idahip_ctx();
     c->device = device; c->n = n; c->batch = batch; c->kind = kind;
     c->npad16 = (n + 15) & ~15;
+    c->list_seen.assign(((size_t)batch + 63) / 64, 0);
     c->lu_superpanel = kind == IDAHIP_HEAT1D ? 1 : 0;
     if (const char* sp = std::getenv("IDAHIP_LU_SUPERPANEL")) c->lu_superpanel = std::strtol(sp, nullptr, 10) != 0 ? 1 : 0;
     if (const char* sp = std::getenv("IDAHIP_LU_PERIOD")) {
@@ -138,6 +149,9 @@ int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem
     (void)hipMemsetAsync(c->delta, 0, bn * sizeof(double), c->stream);
     (void)hipMemsetAsync(c->phi, 0, (size_t)MXORDP1 * bn * sizeof(double), c->stream);
     (void)hipMemsetAsync(c->lu_info, 0, (size_t)batch * sizeof(int), c->stream);
+    // pivots and row permutation in range before the first setup: a Newton iteration or solve ahead of it gathers rows by them
+    (void)hipMemsetAsync(c->piv, 0, bn * sizeof(int64_t), c->stream);
+    (void)hipMemsetAsync(c->perm, 0, bn * sizeof(int32_t), c->stream);
     (void)hipMemsetAsync(c->lu_redo, 0, (size_t)batch * sizeof(int), c->stream);
     if (c->lu_dirty) {  // the factors start as zeros, and so does the map of their blocks that have ever held anything else
         (void)hipMemsetAsync(c->lu, 0, bnn * sizeof(double), c->stream);

@@ -44,6 +44,10 @@ def lib():
     L.oracle_dense_getrf.restype = C.c_int
     L.oracle_dense_getrs.argtypes = [dp, C.c_int, i64p, dp]
     L.oracle_dense_getrs.restype = None
+    L.oracle_dense_getrf_batch.argtypes = [dp, C.c_int, C.c_int, i64p, i32p, C.c_int]
+    L.oracle_dense_getrf_batch.restype = None
+    L.oracle_dense_getrs_batch.argtypes = [dp, C.c_int, C.c_int, i64p, dp, C.c_int]
+    L.oracle_dense_getrs_batch.restype = None
     L.oracle_norm_wrms.argtypes = [dp, dp, C.c_int]
     L.oracle_norm_wrms.restype = C.c_double
     L.oracle_norm_wrms_masked.argtypes = [dp, dp, C.POINTER(C.c_uint8), C.c_int]
@@ -124,6 +128,33 @@ def getrs(lu_logical, piv, b):
     x = f64(b).copy()
     piv = np.ascontiguousarray(piv, dtype=np.int64)
     lib().oracle_dense_getrs(lu.ctypes.data_as(dp), n, _ptr(piv, i64p), _ptr(x))
+    return x
+
+
+def batch_threads():
+    """Threads of the batched entries: a GPU box grants a command 16 CPUs, whatever the machine has."""
+    return max(1, min(16, os.cpu_count() or 1))
+
+
+def getrf_batch(cm, nthreads=None):
+    """cm: [nsys][n][n] contiguous, each matrix in column-major storage (cm[s, j, i] = A_s(i, j)), factored IN PLACE, one
+    dense_get_rf per matrix. Returns (info [nsys] int32, pivots [nsys][n] int64)."""
+    assert cm.dtype == np.float64 and cm.flags.c_contiguous and cm.ndim == 3 and cm.shape[1] == cm.shape[2]
+    nsys, n = cm.shape[0], cm.shape[1]
+    piv = np.zeros((nsys, n), dtype=np.int64)
+    info = np.zeros(nsys, dtype=np.int32)
+    lib().oracle_dense_getrf_batch(_ptr(cm), n, nsys, _ptr(piv, i64p), _ptr(info, i32p), batch_threads() if nthreads is None else nthreads)
+    return info, piv
+
+
+def getrs_batch(cm, piv, b, nthreads=None):
+    """Solutions of the factored systems cm [nsys][n][n] (column-major storage, as getrf_batch leaves them), pivots [nsys][n],
+    right-hand sides b [nsys][n] -> x [nsys][n]."""
+    assert cm.dtype == np.float64 and cm.flags.c_contiguous
+    nsys, n = cm.shape[0], cm.shape[1]
+    piv = np.ascontiguousarray(piv, dtype=np.int64)
+    x = f64(b).reshape(nsys, n).copy()
+    lib().oracle_dense_getrs_batch(_ptr(cm), n, nsys, _ptr(piv, i64p), _ptr(x), batch_threads() if nthreads is None else nthreads)
     return x
 
 

@@ -429,6 +429,51 @@ def test_empty_and_invalid_system_lists():
         idahip.Ctx("linear_dense", 5000, 1).ls_setup(ctx.dev_empty(8), ctx.dev_empty(8), [0])  # n > 4096: refused
 
 
+@pytest.mark.parametrize("entry", ["wrms", "ls_setup", "ls_solve", "nls_sys", "nls_lsetup", "nls_sys_setup", "newton_iter", "scale_phi1"])
+def test_lists_that_name_a_system_twice_are_refused(entry):
+    """A list names each system at most once (include/ida_hip.h): a duplicate would have two workgroups factor one matrix in place,
+    or update one system's vectors, at the same time. check_list refuses it for every entry point before anything is uploaded or
+    launched, and every buffer -- the caller's and the ctx's -- is left as it was."""
+    import idahip
+    n, B = 24, 3
+    rng = np.random.default_rng(1)
+    mats = rng.standard_normal((B, n, n))
+    ctx = idahip.Ctx("linear_dense", n, B)
+    ctx.set_lu_variant(LU_VARIANT)
+    ctx.set_linear_dense(colmajor(mats), colmajor(mats), np.ones((B, n)))
+    fields = [idahip.F_YY, idahip.F_YP, idahip.F_EWT, idahip.F_EE, idahip.F_DELTA, idahip.F_PHI0, idahip.F_PHI0 + 1]
+    for f in fields:
+        ctx.upload(f, rng.standard_normal((B, n)))
+    rc, info = ctx.nls_lsetup(0.0, 1.0)  # factors for the accepted calls below (newton_iter solves with the ctx's own)
+    assert rc == 0 and not info.any()
+    dA = ctx.dev_array(colmajor(mats))
+    dP = ctx.dev_array(np.arange(B * n, dtype=np.int64) % n)
+    dX = ctx.dev_array(rng.standard_normal((B, n)))
+    calls = {
+        "wrms": lambda idx: ctx.wrms(dA, dA, idx=idx),
+        "ls_setup": lambda idx: ctx.ls_setup(dA, dP, idx),
+        "ls_solve": lambda idx: ctx.ls_solve(dA, dP, dX, dA, idx),
+        "nls_sys": lambda idx: ctx.nls_sys(0.0, 1.0, True, idx=idx),
+        "nls_lsetup": lambda idx: ctx.nls_lsetup(0.0, 1.0, idx=idx),
+        "nls_sys_setup": lambda idx: ctx.nls_sys_setup(0.0, 1.0, idx=idx),
+        "newton_iter": lambda idx: ctx.newton_iter(1.0, idx=idx),
+        "scale_phi1": lambda idx: ctx.scale_phi1(2.0, idx=idx),
+    }
+
+    def state():
+        return ([ctx.download(f) for f in fields] + [ctx.to_host(dA, (B, n, n)), ctx.to_host(dP, (B, n), dtype=np.int64),
+                ctx.to_host(dX, (B, n))])
+
+    before = state()
+    for bad, dup in (([1, 1], 1), ([0, 2, 0], 0)):
+        with pytest.raises(idahip.IdaHipError, match="system id %d listed twice" % dup):
+            calls[entry](bad)
+        for a, b in zip(before, state()):
+            assert np.array_equal(a.view(np.uint64) if a.dtype == np.float64 else a, b.view(np.uint64) if b.dtype == np.float64 else b)
+    calls[entry]([2, 0])  # the same ids once each: accepted (and the map of seen ids was left clear by the refusals)
+    ctx.close()
+
+
 def test_entry_points_run_on_the_ctx_device_whatever_device_is_current():
     """A ctx belongs to the device it was created on: every entry point switches to it and puts the caller's current
     device back (one host thread driving several GPUs). Needs two visible GPUs to see a switch; on a

@@ -80,3 +80,32 @@ def test_lu_solve_random_against_numpy():
         assert info == 0
         x = O.getrs(lu, piv, a @ xs)
         assert np.allclose(x, xs, rtol=1e-8, atol=1e-10)
+
+
+def test_batched_getrf_equals_one_getrf_per_matrix():
+    """oracle_dense_getrf_batch (the GPU batch tests' checker, many matrices over std::threads) gives the bits of O.getrf matrix by
+    matrix -- pivots, info and factors, NaN payloads included -- on a batch with NaN, infinities, a singular matrix and ties; its
+    getrs counterpart those of O.getrs."""
+    rng = np.random.default_rng(42)
+    n, B = 37, 11
+    mats = rng.standard_normal((B, n, n))
+    mats[1, 5, 5] = np.nan
+    mats[2, 30, 3] = np.nan
+    mats[3, 7, 2] = np.inf
+    mats[3, 9, 2] = -np.inf
+    mats[4, :, 20] = 0.0                                        # singular: info = 21
+    mats[5] = rng.integers(-2, 3, size=(n, n)).astype(float)    # ties and exact zeros
+    mats[6][np.abs(mats[6]) < 1.0] = -0.0
+    mats[6] += np.eye(n) * 3.0
+    cm = np.ascontiguousarray(np.transpose(mats, (0, 2, 1)))
+    info, piv = O.getrf_batch(cm, nthreads=4)
+    rhs = rng.standard_normal((B, n))
+    x = O.getrs_batch(cm, piv, rhs, nthreads=3)
+    assert info[4] == 21 and info[3] == 0
+    for s in range(B):
+        info_o, lu_o, piv_o = O.getrf(mats[s])
+        assert info[s] == info_o, s
+        assert np.array_equal(piv[s], piv_o), s
+        assert np.array_equal(cm[s].T.view(np.uint64), lu_o.view(np.uint64)), s
+        if info_o == 0:
+            assert np.array_equal(x[s].view(np.uint64), O.getrs(lu_o, piv_o, rhs[s]).view(np.uint64)), s
