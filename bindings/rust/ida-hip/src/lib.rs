@@ -167,6 +167,19 @@ impl Ctx {
         Ok(Ctx { raw, n, batch, callbacks: None })
     }
 
+    /// A band context (`idahip_create_band`): Jacobians with lower bandwidth `ml` and upper bandwidth `mu` are stored, factored and
+    /// solved in LAPACK band storage instead of n x n. `Problem::Heat1D` (ml, mu >= 1) or a host-callback problem, 8 < n <= 4096.
+    pub fn new_band(device: i32, n: usize, batch: usize, problem: Problem, ml: usize, mu: usize) -> Result<Self, Error> {
+        let mut raw: *mut sys::idahip_ctx = ptr::null_mut();
+        let rc = unsafe {
+            sys::idahip_create_band(&mut raw, device, n as c_int, batch as c_int, problem.code(), ptr::null_mut(), ml as c_int, mu as c_int)
+        };
+        if rc != 0 || raw.is_null() {
+            return Err(Error::Library { code: rc, message: "idahip_create_band failed (no band form of this problem or size, or no GPU)".to_string() });
+        }
+        Ok(Ctx { raw, n, batch, callbacks: None })
+    }
+
     pub fn n(&self) -> usize {
         self.n
     }

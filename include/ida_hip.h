@@ -52,6 +52,12 @@ typedef int (*idahip_res_fn)(int sys, double tt, const double* yy, const double*
 typedef int (*idahip_jac_fn)(int sys, double tt, double cj, const double* yy, const double* yp, const double* resvec, double* J,
                              void* user);
 
+/* The band form of idahip_jac_fn (a ctx made by idahip_create_band): J written into LAPACK band storage that the library has
+ * zeroed, element (i, j) at AB[j * ldab + ml + mu + i - j] for j - mu <= i <= j + ml, ldab = 2 ml + mu + 1 (the top ml rows of a
+ * column are fill space: leave them zero). */
+typedef int (*idahip_band_jac_fn)(int sys, double tt, double cj, const double* yy, const double* yp, const double* resvec, double* AB,
+                                  int ldab, void* user);
+
 /* ctx-resident vectors of the reference's IdaNLProblem / Ida structs (src/ida_nls.rs:27-59, src/lib.rs:104-126) */
 typedef enum {
     IDAHIP_F_YY = 0,
@@ -69,6 +75,27 @@ typedef enum {
 /* ---- lifetime: LS::new(n) + NLS::new(n, maxiters) + IdaNLProblem::new (src/lib.rs:399-400, src/ida_ls.rs:192) ---- */
 int idahip_create(idahip_ctx** ctx, int device, int n, int batch, idahip_problem kind, void* hip_stream /* or NULL */);
 int idahip_destroy(idahip_ctx* ctx);
+/* A BAND ctx (the SUNLinSol_Band of C IDA; the reference ships only `Dense`, crates/linear/src/traits.rs is where it plugs in):
+ * the same ensemble, but the Jacobian of every system has lower bandwidth ml and upper bandwidth mu and is stored, factored and
+ * solved in LAPACK band storage ([batch][ldab * n], ldab = 2 ml + mu + 1, rust-ida_amd/csrc/band_kernels.hpp) instead of n x n.
+ * Kinds IDAHIP_HEAT1D (ml, mu >= 1) and IDAHIP_HOST_CALLBACK (idahip_set_host_band_problem), 8 < n <= 4096, 0 <= ml, mu < n;
+ * anything else is refused (-2). Exactness: pivots are those of dense_get_rf on the same matrix; factors, solutions and
+ * integrations equal the dense ones by value (-0.0 == +0.0; steps, orders, counters, hused and tn bit-identical) for finite
+ * inputs -- the contract in band_kernels.hpp. Dense-only calls (idahip_download_lu, idahip_set_linear_dense,
+ * idahip_set_host_problem, idahip_ls_setup) return -2 on a band ctx. */
+int idahip_create_band(idahip_ctx** ctx, int device, int n, int batch, idahip_problem kind, void* hip_stream, int ml, int mu);
+/* 1 for a band ctx (*ml, *mu set when non-null), 0 for a dense one, -1 for a null ctx */
+int idahip_band(const idahip_ctx* ctx, int* ml, int* mu);
+/* IDAHIP_HOST_CALLBACK on a band ctx: the residual and the band Jacobian callbacks (both required) */
+int idahip_set_host_band_problem(idahip_ctx* ctx, idahip_res_fn res, idahip_band_jac_fn bjac, void* user);
+/* band factors of one system (hAB [ldab * n]), its pivots (hPiv [n]); a band ctx only */
+int idahip_download_lu_band(idahip_ctx* ctx, int sys, double* hAB, int64_t* hPiv);
+/* LSolver setup / solve in band storage on caller-owned device buffers dAB [batch][ldab * n], dPiv [batch][n], dX / dB [batch][n],
+ * on any ctx (n is the ctx's, no upper limit; 0 <= ml, mu < n). Same list rules, hInfo and return values as idahip_ls_setup /
+ * idahip_ls_solve; the factorisation is in place (the fill rows need nothing on entry), the solve may have dX == dB and ignores tol. */
+int idahip_ls_setup_band(idahip_ctx* ctx, int ml, int mu, double* dAB, int64_t* dPiv, int32_t* hInfo, const int32_t* hIdx, int nsys);
+int idahip_ls_solve_band(idahip_ctx* ctx, int ml, int mu, const double* dAB, const int64_t* dPiv, double* dX, const double* dB, double tol,
+                         const int32_t* hIdx, int nsys);
 /* `count` HIP streams on `device` for contexts that are to work SIDE BY SIDE (idaens_stream_group, ida_ensemble.h). The HIP
  * runtime maps its streams onto a few hardware queues as it sees fit, and two streams on one queue take turns; this call
  * creates streams and keeps those a probe kernel shows to run concurrently with every stream kept before. streams_out[count]

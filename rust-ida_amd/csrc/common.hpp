@@ -67,6 +67,10 @@ struct idahip_ctx {
     uint8_t* lu_dirty = nullptr; // [batch][64][64], n >= 2048: [K][I] = 1 once the 64 x 64 block (rows I, columns K) of `lu` has received a value with non-zero bits (never reset: `lu` starts as zeros and lu_finalize_kernel does not rewrite zeros into blocks that have only ever held zeros)
     uint8_t* lu_zmap = nullptr;  // [batch][64][64], n >= 2048: [K][I] = 1 when the 64 x 64 block (rows I, columns K) of the factors in `lu` may hold a non-zero
     double* lu_l11 = nullptr;
+    // band mode (idahip_create_band): the Jacobian and its factors in LAPACK band storage, [batch][ldab * n] with ldab = 2 ml + mu + 1
+    // (band_kernels.hpp), factored in place; piv is shared with the dense mode. lu, jw and the dense LU's workspace are not allocated.
+    int band = 0, ml = 0, mu = 0, ldab = 0;
+    double* bab = nullptr;
     double *ic_y = nullptr, *ic_yp = nullptr;  // [batch][n] initial conditions kept for idahip_restore_initial (lazy)
     double* dky = nullptr;                     // [batch][n] result buffer of idahip_get_dky (lazy)
     int lu_variant = 4;  // 4: one wave per matrix factors each 64-column super-panel (lu_wavepanel.hpp, default)
@@ -103,6 +107,7 @@ struct idahip_ctx {
     double *A = nullptr, *B = nullptr, *C = nullptr;  // LINEAR_DENSE
     idahip_res_fn cb_res = nullptr;                   // HOST_CALLBACK
     idahip_jac_fn cb_jac = nullptr;
+    idahip_band_jac_fn cb_bjac = nullptr;             // HOST_CALLBACK on a band ctx
     void* cb_user = nullptr;
     double* cb_stage = nullptr;                       // [batch][3][n] device staging of yy, yp, res of the listed systems
     std::vector<double> cb_host;                      // host mirror of cb_stage

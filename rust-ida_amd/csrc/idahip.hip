@@ -4,6 +4,7 @@
 #include "lu_driver.hpp"
 #include "problem_kernels.hpp"
 #include "solve_kernels.hpp"
+#include "band_kernels.hpp"
 #include "vector_kernels.hpp"
 #include "tiny_ida.hpp"
 #include "round_ida.hpp"
@@ -72,11 +73,36 @@ int post_launch(idahip_ctx* c, const char* what) {
     return 0;
 }
 
-}  // namespace
+// Band LU launches (band_kernels.hpp): one lane per system; systems per wavefront as idahip_tiny_solve chooses them -- the fewest
+// (64, 32, ... 1) that keep the wavefront count at or below the device's SIMD count (a chain's steps cost the same for one lane as
+// for 64). IDAHIP_BAND_SPW overrides (measurements; the results do not depend on it).
+int band_spw(const idahip_ctx* c, int nsys) {
+    int spw = 64;
+    const int simds = c->simds > 0 ? c->simds : 1024;
+    while (spw > 1 && (long)(nsys + spw / 2 - 1) / (spw / 2) <= simds) spw >>= 1;
+    if (const char* e = std::getenv("IDAHIP_BAND_SPW")) {
+        const int v = (int)std::strtol(e, nullptr, 10);
+        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) spw = v;
+    }
+    return spw;
+}
 
-extern "C" {
+// batched band getrf of dAB [.][sstride] in place for the listed systems (d_cnt: the list's length on the device, nsys its bound);
+// per-system info into ctx->lu_info
+int band_factor(idahip_ctx* c, double* dAB, long sstride, int64_t* dPiv, long pstride, int ml, int mu, const int* d_idx, int nsys,
+                const int* d_cnt = nullptr) {
+    if (nsys == 0) return 0;
+    BandArgs g;
+    g.ab = dAB; g.sstride = sstride; g.piv = (long long*)dPiv; g.pstride = pstride; g.n = c->n; g.ml = ml; g.mu = mu;
+    g.idx = d_idx; g.nsys = nsys; g.cnt = d_cnt; g.info = c->lu_info;
+    const int spw = band_spw(c, nsys);
+    const dim3 grid((nsys + spw - 1) / spw), blk(spw);
+    if (ml == 1 && mu == 1) hipLaunchKernelGGL((band_getrf_reg_kernel<1, 1>), grid, blk, 0, c->stream, g);
+    else hipLaunchKernelGGL(band_getrf_kernel, grid, blk, 0, c->stream, g);
+    return post_launch(c, "band_getrf");
+}
 
-int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream) {
+int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, bool band, int ml, int mu) {
     if (!out) return -1;
     *out = nullptr;
     if (n < 1 || batch < 1) return -2;
@@ -84,6 +110,9 @@ int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem
     if ((kind == IDAHIP_ROBERTS || kind == IDAHIP_LORENZ63) && n != 3) return -2;
     idahip_ctx* c = new idahip_ctx();
     c->device = device; c->n = n; c->batch = batch; c->kind = kind;
+    if (band) {
+        c->band = 1; c->ml = ml; c->mu = mu; c->ldab = 2 * ml + mu + 1;
+    }
     c->npad16 = (n + 15) & ~15;
     c->list_seen.assign(((size_t)batch + 63) / 64, 0);
     c->lu_superpanel = kind == IDAHIP_HEAT1D ? 1 : 0;
@@ -111,15 +140,17 @@ int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem
     rc |= dalloc(c, &c->yy, bn); rc |= dalloc(c, &c->yp, bn); rc |= dalloc(c, &c->yypredict, bn); rc |= dalloc(c, &c->yppredict, bn);
     rc |= dalloc(c, &c->ewt, bn); rc |= dalloc(c, &c->ee, bn); rc |= dalloc(c, &c->delta, bn); rc |= dalloc(c, &c->savres, bn);
     rc |= dalloc(c, &c->phi, (size_t)MXORDP1 * bn);
-    rc |= dalloc(c, &c->lu, bnn); rc |= dalloc(c, &c->piv, bn); rc |= dalloc(c, &c->perm, bn);
+    rc |= dalloc(c, &c->piv, bn); rc |= dalloc(c, &c->perm, bn);
     rc |= dalloc(c, &c->lu_info, (size_t)batch);
     rc |= dalloc(c, &c->lu_redo, (size_t)batch);
     rc |= dalloc(c, &c->lu_nzb, (size_t)batch);
-    if (n > LU_MAX_N) rc |= dalloc(c, &c->lu_bz, (size_t)batch * 64);
-    if (n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_zmap, (size_t)batch * 4096);
-    if (n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_dirty, (size_t)batch * 4096);
-    if (n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_jwzero, (size_t)batch);
-    if (n > TINY_N) {
+    if (band) rc |= dalloc(c, &c->bab, bn * c->ldab);  // instead of every n x n buffer below
+    if (!band) rc |= dalloc(c, &c->lu, bnn);
+    if (!band && n > LU_MAX_N) rc |= dalloc(c, &c->lu_bz, (size_t)batch * 64);
+    if (!band && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_zmap, (size_t)batch * 4096);
+    if (!band && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_dirty, (size_t)batch * 4096);
+    if (!band && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_jwzero, (size_t)batch);
+    if (!band && n > TINY_N) {
         rc |= dalloc(c, &c->jw, bnn);
         rc |= dalloc(c, &c->lu_pos, bn); rc |= dalloc(c, &c->lu_live, bn); rc |= dalloc(c, &c->lu_prow, bn);
         rc |= dalloc(c, &c->lu_l11, (size_t)batch * L11_STRIDE);
@@ -153,6 +184,7 @@ int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem
     (void)hipMemsetAsync(c->piv, 0, bn * sizeof(int64_t), c->stream);
     (void)hipMemsetAsync(c->perm, 0, bn * sizeof(int32_t), c->stream);
     (void)hipMemsetAsync(c->lu_redo, 0, (size_t)batch * sizeof(int), c->stream);
+    if (c->bab) (void)hipMemsetAsync(c->bab, 0, bn * c->ldab * sizeof(double), c->stream);
     if (c->lu_dirty) {  // the factors start as zeros, and so does the map of their blocks that have ever held anything else
         (void)hipMemsetAsync(c->lu, 0, bnn * sizeof(double), c->stream);
         (void)hipMemsetAsync(c->lu_dirty, 0, (size_t)batch * 4096, c->stream);
@@ -163,13 +195,48 @@ int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem
     return 0;
 }
 
+}  // namespace
+
+extern "C" {
+
+int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream) {
+    return create_ctx(out, device, n, batch, kind, hip_stream, false, 0, 0);
+}
+
+int idahip_create_band(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, int ml, int mu) {
+    if (!out) return -1;
+    *out = nullptr;
+    if (kind != IDAHIP_HEAT1D && kind != IDAHIP_HOST_CALLBACK) {
+        std::fprintf(stderr, "idahip_create_band: problem kind %d has no band form (IDAHIP_HEAT1D or IDAHIP_HOST_CALLBACK)\n", (int)kind);
+        return -2;
+    }
+    if (n <= TINY_N || n > LU_BIG_MAX_N) {
+        std::fprintf(stderr, "idahip_create_band: n = %d outside %d < n <= %d\n", n, TINY_N, LU_BIG_MAX_N);
+        return -2;
+    }
+    if (ml < 0 || mu < 0 || ml >= n || mu >= n || (kind == IDAHIP_HEAT1D && (ml < 1 || mu < 1))) {
+        std::fprintf(stderr, "idahip_create_band: bandwidths ml = %d, mu = %d outside 0 <= ml, mu < n (>= 1 for IDAHIP_HEAT1D)\n", ml, mu);
+        return -2;
+    }
+    return create_ctx(out, device, n, batch, kind, hip_stream, true, ml, mu);
+}
+
+int idahip_band(const idahip_ctx* c, int* ml, int* mu) {
+    if (!c) return -1;
+    if (c->band) {
+        if (ml) *ml = c->ml;
+        if (mu) *mu = c->mu;
+    }
+    return c->band;
+}
+
 int idahip_destroy(idahip_ctx* c) {
     DevGuard dev_guard__(c);
     if (!c) return 0;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
                     c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->ic_y,
-                    c->ic_yp, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
+                    c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -353,6 +420,7 @@ int idahip_set_linear_dense(idahip_ctx* c, int first, int count, const double* h
     DevGuard dev_guard__(c);
     if (!c || !hA || !hB || !hC) return -1;
     if (c->kind != IDAHIP_LINEAR_DENSE) return fail(c, -2, "not a LINEAR_DENSE ctx");
+    if (c->band) return fail(c, -2, "idahip_set_linear_dense on a band ctx");
     if (first < 0 || count < 0 || first + count > c->batch) return fail(c, -2, "system range out of bounds");
     const size_t nn = (size_t)c->n * c->n;
     IDAHIP_HIP(c, hipMemcpy(c->A + first * nn, hA, sizeof(double) * count * nn, hipMemcpyHostToDevice));
@@ -364,8 +432,19 @@ int idahip_set_linear_dense(idahip_ctx* c, int first, int count, const double* h
 int idahip_set_host_problem(idahip_ctx* c, idahip_res_fn res, idahip_jac_fn jac, void* user) {
     if (!c || !res || !jac) return -1;
     if (c->kind != IDAHIP_HOST_CALLBACK) return fail(c, -2, "not an IDAHIP_HOST_CALLBACK ctx");
+    if (c->band) return fail(c, -2, "a band ctx takes a band Jacobian: idahip_set_host_band_problem");
     c->cb_res = res;
     c->cb_jac = jac;
+    c->cb_user = user;
+    return 0;
+}
+
+int idahip_set_host_band_problem(idahip_ctx* c, idahip_res_fn res, idahip_band_jac_fn bjac, void* user) {
+    if (!c || !res || !bjac) return -1;
+    if (c->kind != IDAHIP_HOST_CALLBACK) return fail(c, -2, "not an IDAHIP_HOST_CALLBACK ctx");
+    if (!c->band) return fail(c, -2, "a dense ctx takes a dense Jacobian: idahip_set_host_problem");
+    c->cb_res = res;
+    c->cb_bjac = bjac;
     c->cb_user = user;
     return 0;
 }
@@ -396,9 +475,22 @@ int idahip_download_lu(idahip_ctx* c, int sys, double* hLU, int64_t* hPiv) {
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
+    if (c->band) return fail(c, -2, "idahip_download_lu on a band ctx: idahip_download_lu_band");
     IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
     const size_t nn = (size_t)c->n * c->n;
     if (hLU) IDAHIP_HIP(c, hipMemcpy(hLU, c->lu + sys * nn, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    if (hPiv) IDAHIP_HIP(c, hipMemcpy(hPiv, c->piv + (size_t)sys * c->n, sizeof(int64_t) * c->n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int idahip_download_lu_band(idahip_ctx* c, int sys, double* hAB, int64_t* hPiv) {
+    DevGuard dev_guard__(c);
+    if (!c) return -1;
+    if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
+    if (!c->band) return fail(c, -2, "idahip_download_lu_band on a dense ctx");
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t ne = (size_t)c->ldab * c->n;
+    if (hAB) IDAHIP_HIP(c, hipMemcpy(hAB, c->bab + sys * ne, sizeof(double) * ne, hipMemcpyDeviceToHost));
     if (hPiv) IDAHIP_HIP(c, hipMemcpy(hPiv, c->piv + (size_t)sys * c->n, sizeof(int64_t) * c->n, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -437,6 +529,7 @@ int idahip_ls_setup(idahip_ctx* c, double* dA, int64_t* dPiv, int32_t* hInfo, co
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
     if (!dA || !dPiv || !hInfo) return fail(c, -2, "null argument");
+    if (c->band) return fail(c, -2, "idahip_ls_setup on a band ctx (no dense work matrices): idahip_ls_setup_band");
     if (nsys == 0) return 0;
     const int n = c->n;
     const long nn = (long)n * n;
@@ -501,6 +594,60 @@ int idahip_ls_solve(idahip_ctx* c, const double* dLU, const int64_t* dPiv, doubl
     return ap.finish_async();
 }
 
+int idahip_ls_setup_band(idahip_ctx* c, int ml, int mu, double* dAB, int64_t* dPiv, int32_t* hInfo, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!dAB || !dPiv || !hInfo) return fail(c, -2, "null argument");
+    if (ml < 0 || mu < 0 || ml >= c->n || mu >= c->n) return fail(c, -2, "bandwidths ml = %d, mu = %d outside [0, n)", ml, mu);
+    if (nsys == 0) return 0;
+    const int n = c->n;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_LU, nsys);
+        if ((rc = band_factor(c, dAB, (long)(2 * ml + mu + 1) * n, dPiv, n, ml, mu, d_idx, nsys))) return rc;
+    }
+    std::vector<int32_t> info(c->batch);
+    IDAHIP_HIP(c, hipMemcpyAsync(info.data(), c->lu_info, sizeof(int32_t) * c->batch, hipMemcpyDeviceToHost, c->stream));
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    int any = 0;
+    for (int s = 0; s < nsys; ++s) {
+        hInfo[s] = info[hIdx[s]];
+        any |= hInfo[s] != 0;
+    }
+    return any ? 1 : 0;
+}
+
+int idahip_ls_solve_band(idahip_ctx* c, int ml, int mu, const double* dAB, const int64_t* dPiv, double* dX, const double* dB, double /*tol*/,
+                         const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!dAB || !dPiv || !dX || !dB) return fail(c, -2, "null argument");
+    if (ml < 0 || mu < 0 || ml >= c->n || mu >= c->n) return fail(c, -2, "bandwidths ml = %d, mu = %d outside [0, n)", ml, mu);
+    if (nsys == 0) return 0;
+    const int n = c->n;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
+        const int spw = band_spw(c, nsys);
+        const dim3 grid((nsys + spw - 1) / spw), blk(spw);
+        const long ss = (long)(2 * ml + mu + 1) * n;
+        if (ml == 1 && mu == 1)
+            hipLaunchKernelGGL((band_getrs_kernel<1, 1>), grid, blk, 0, c->stream, dAB, ss, (const long long*)dPiv, (long)n, dX, dB, n, ml, mu, d_idx, nsys);
+        else
+            hipLaunchKernelGGL((band_getrs_kernel<-1, -1>), grid, blk, 0, c->stream, dAB, ss, (const long long*)dPiv, (long)n, dX, dB, n, ml, mu, d_idx, nsys);
+        if ((rc = post_launch(c, "ls_solve_band"))) return rc;
+    }
+    return ap.finish_async();
+}
+
 int idahip_wrms(idahip_ctx* c, const double* dX, const double* dW, double* hOut, const int32_t* hIdx, int nsys) {
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
@@ -536,7 +683,7 @@ namespace {
 // scatters the residuals (launch_sys with c->kind == IDAHIP_HOST_CALLBACK)
 int callback_sys(idahip_ctx* c, const SysArgs& a, const double* hTn, const int32_t* hIdx, int nsys) {
     const int n = c->n;
-    if (!c->cb_res || !c->cb_jac) return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_problem has not been called");
+    if (!c->cb_res || !(c->cb_jac || c->cb_bjac)) return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_problem has not been called");
     const size_t cnt = (size_t)nsys * 3 * n;
     hipLaunchKernelGGL(callback_pre_kernel, dim3(nsys), dim3(256), 0, c->stream, a, c->cb_stage);
     if (c->cb_host.size() < cnt) c->cb_host.resize(cnt);
@@ -554,11 +701,13 @@ int callback_sys(idahip_ctx* c, const SysArgs& a, const double* hTn, const int32
     return post_launch(c, "nls_sys (host callback)");
 }
 
-// Jacobian of a host-callback problem into the LU work matrices (column-major per system)
+// Jacobian of a host-callback problem into the LU work matrices (column-major per system), or on a band ctx into the band
+// storage (ldab * n doubles per system)
 int callback_jac(idahip_ctx* c, double* work, const int* d_idx, const double* hTn, const double* hCj, const int32_t* hIdx, int nsys) {
     const int n = c->n;
-    const size_t nn = (size_t)n * n;
-    if (!c->cb_res || !c->cb_jac) return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_problem has not been called");
+    const size_t nn = c->band ? (size_t)c->ldab * n : (size_t)n * n;
+    if (!c->cb_res || !(c->band ? (bool)c->cb_bjac : (bool)c->cb_jac))
+        return fail(c, -2, "IDAHIP_HOST_CALLBACK: %s has not been called", c->band ? "idahip_set_host_band_problem" : "idahip_set_host_problem");
     const size_t cnt = (size_t)nsys * 3 * n;
     hipLaunchKernelGGL(callback_pack_kernel, dim3(nsys), dim3(256), 0, c->stream, (const double*)c->yy, (const double*)c->yp,
                        (const double*)c->savres, d_idx, n, c->cb_stage);
@@ -589,7 +738,8 @@ int callback_jac(idahip_ctx* c, double* work, const int* d_idx, const double* hT
             const double* hs = h + s * 3 * n;
             double* J = c->cb_jpin + q * nn;
             for (size_t e = 0; e < nn; ++e) J[e] = 0.0;  // J <- 0 (ida_ls.rs:255)
-            if (c->cb_jac(hIdx[s], hTn[s], hCj[s], hs, hs + n, hs + 2 * n, J, c->cb_user) != 0)
+            if ((c->band ? c->cb_bjac(hIdx[s], hTn[s], hCj[s], hs, hs + n, hs + 2 * n, J, c->ldab, c->cb_user)
+                         : c->cb_jac(hIdx[s], hTn[s], hCj[s], hs, hs + n, hs + 2 * n, J, c->cb_user)) != 0)
                 return fail(c, -7, "the user's Jacobian function failed for system %d", hIdx[s]);
         }
         IDAHIP_HIP(c, hipMemcpyAsync(c->cb_jdev, c->cb_jpin, sizeof(double) * m * nn, hipMemcpyHostToDevice, c->stream));
@@ -635,6 +785,14 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
                const double* hCj = nullptr, const int32_t* hIdx = nullptr, const int* d_skip = nullptr) {
     const int n = c->n;
     const long nn = (long)n * n;
+    if (c->band) {  // the band storage is the work matrix: the factorisation runs in place
+        if (c->kind == IDAHIP_HOST_CALLBACK) return callback_jac(c, c->bab, d_idx, hTn, hCj, hIdx, nsys);
+        int chunks = 1;
+        while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
+        hipLaunchKernelGGL(heat_band_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, c->bab, n, c->ml, c->mu, (const double*)c->params, d_idx,
+                           d_cj, chunks, d_skip);
+        return post_launch(c, "band jac");
+    }
     switch (c->kind) {
         case IDAHIP_HOST_CALLBACK:
             return callback_jac(c, work, d_idx, hTn, hCj, hIdx, nsys);
@@ -671,7 +829,8 @@ int factor_and_report(idahip_ctx* c, double* work, const int* d_idx, const int32
     int rc;
     {
         KTimer kt(c, IDAHIP_K_LU, nsys);
-        rc = lu_factor_batched(c, work, nn, c->lu, nn, (long long*)c->piv, n, c->perm, d_idx, nsys);
+        if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, d_idx, nsys);
+        else rc = lu_factor_batched(c, work, nn, c->lu, nn, (long long*)c->piv, n, c->perm, d_idx, nsys);
         if (rc) return rc;
         if ((rc = post_launch(c, "lu"))) return rc;
     }
@@ -767,7 +926,16 @@ int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, in
 // One Newton iteration body for the listed systems (shared by idahip_newton_iter and idahip_newton_iter2)
 static int launch_newton_iter(idahip_ctx* c, const int* d_idx, const double* d_scale, double* d_out, const int* d_skip, int nsys) {
     const int n = c->n;
-    if (n <= TINY_N) {
+    if (c->band) {
+        const int spw = band_spw(c, nsys);
+        const dim3 grid((nsys + spw - 1) / spw), blk(spw);
+        if (c->ml == 1 && c->mu == 1)
+            hipLaunchKernelGGL((band_newton_iter_kernel<1, 1>), grid, blk, 0, c->stream, (const double*)c->bab, (const long long*)c->piv, c->ml, c->mu,
+                               c->delta, c->ee, (const double*)c->ewt, n, d_idx, nsys, d_scale, d_out, d_skip);
+        else
+            hipLaunchKernelGGL((band_newton_iter_kernel<-1, -1>), grid, blk, 0, c->stream, (const double*)c->bab, (const long long*)c->piv, c->ml,
+                               c->mu, c->delta, c->ee, (const double*)c->ewt, n, d_idx, nsys, d_scale, d_out, d_skip);
+    } else if (n <= TINY_N) {
         hipLaunchKernelGGL(tiny_newton_iter_kernel, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, (const double*)c->lu,
                            (const long long*)c->piv, c->delta, c->ee, (const double*)c->ewt, n, d_idx, nsys, d_scale, d_out, d_skip);
     } else if (n % 2 == 0 && n >= 2048) {
@@ -1329,7 +1497,7 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
         // batch needs one in any round -- launches sized for the whole batch cost more than they do at n = 512 (11.4 against
         // 12.3 k iters/s in round 4). The list's length comes back to the host (4 bytes, behind the residual kernels enqueued
         // below: the copy's round trip is hidden) and the LU's launches are sized by it, as the host stepper's are.
-        const bool lu_cnt_on_host = n > LU_MAX_N;
+        const bool lu_cnt_on_host = n > LU_MAX_N && !c->band;  // (the band LU is one launch: its surplus lanes leave on reading the count)
         if (lu_cnt_on_host) {
             IDAHIP_HIP(c, hipMemcpyAsync(c->rnd_host + 2, a.lu_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
             IDAHIP_HIP(c, hipEventRecord(c->ev_cnt, c->stream));
@@ -1362,7 +1530,9 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
                 if (nlu < 0 || nlu > batch) return fail(c, -4, "list length %d outside 0..%d", nlu, batch);
             }
             KTimer kt(c, IDAHIP_K_LU, 0);
-            if ((rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt))) return rc;
+            if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, a.lu_list, nlu, d_cnt);
+            else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt);
+            if (rc) return rc;
             if ((rc = post_launch(c, "lu"))) return rc;
         }
         hipLaunchKernelGGL(round_newton_ctl_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a, 0);

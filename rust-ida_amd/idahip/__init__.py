@@ -23,6 +23,8 @@ KIND = {"roberts": ROBERTS, "lorenz63": LORENZ63, "linear_dense": LINEAR_DENSE, 
 RES_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
 JAC_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                      C.POINTER(C.c_double), C.c_void_p)
+BAND_JAC_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                          C.POINTER(C.c_double), C.c_int, C.c_void_p)
 ROOT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double))
 F_YY, F_YP, F_YYPREDICT, F_YPPREDICT, F_EWT, F_EE, F_DELTA, F_SAVRES, F_PHI0 = range(9)
 K_NEWTON_ITER, K_SYS, K_JAC, K_LU, K_VECTOR, K_SOLVE, K_SYS_JAC = range(7)
@@ -38,6 +40,7 @@ HIP_SYMBOLS = [
     "idahip_timing_enable", "idahip_timing_get", "idahip_timing_reset", "idahip_set_lu_variant", "idahip_snapshot_initial",
     "idahip_tiny_solve", "idahip_pow_batch", "idahip_round_solve", "idahip_lu_variant",
     "idahip_restore_initial", "idahip_ls_type", "idahip_ls_num_iters", "idahip_ls_res_norm", "idahip_timing_build", "idahip_concurrent_streams", "idahip_release_streams", "idahip_stream_pair_share", "idahip_set_lu_superpanel", "idahip_lu_superpanel", "idahip_set_lu_period", "idahip_lu_period",
+    "idahip_create_band", "idahip_band", "idahip_set_host_band_problem", "idahip_download_lu_band", "idahip_ls_setup_band", "idahip_ls_solve_band",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
@@ -79,6 +82,12 @@ def load():
     vp, ci, cd = C.c_void_p, C.c_int, C.c_double
     H.idahip_create.argtypes = [C.POINTER(vp), ci, ci, ci, ci, vp]
     H.idahip_destroy.argtypes = [vp]
+    H.idahip_create_band.argtypes = [C.POINTER(vp), ci, ci, ci, ci, vp, ci, ci]
+    H.idahip_band.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+    H.idahip_set_host_band_problem.argtypes = [vp, RES_FN, BAND_JAC_FN, vp]
+    H.idahip_download_lu_band.argtypes = [vp, ci, dp, i64p]
+    H.idahip_ls_setup_band.argtypes = [vp, ci, ci, vp, vp, i32p, i32p, ci]
+    H.idahip_ls_solve_band.argtypes = [vp, ci, ci, vp, vp, vp, vp, cd, i32p, ci]
     H.idahip_concurrent_streams.argtypes = [ci, ci, C.POINTER(vp), C.POINTER(ci)]
     H.idahip_release_streams.argtypes = [ci, ci, C.POINTER(vp)]
     H.idahip_stream_pair_share.argtypes = [ci, vp, vp, C.POINTER(cd)]
@@ -169,17 +178,35 @@ class IdaHipError(RuntimeError):
 
 
 class Ctx:
-    """One ensemble context on one device (idahip_ctx)."""
+    """One ensemble context on one device (idahip_ctx). band=(ml, mu): a band ctx (idahip_create_band) whose Jacobians are stored,
+    factored and solved in LAPACK band storage."""
 
-    def __init__(self, kind, n, batch, device=0, stream=None):
+    def __init__(self, kind, n, batch, device=0, stream=None, band=None):
         self.H, self.E = load()
         self.n, self.batch = int(n), int(batch)
         self.kind = KIND[kind] if isinstance(kind, str) else int(kind)
         h = C.c_void_p()
-        rc = self.H.idahip_create(C.byref(h), int(device), self.n, self.batch, self.kind, stream)
-        if rc != 0 or not h.value:
-            raise IdaHipError("idahip_create failed (%d) -- is a GPU visible?" % rc)
+        if band is None:
+            self.band = None
+            rc = self.H.idahip_create(C.byref(h), int(device), self.n, self.batch, self.kind, stream)
+            if rc != 0 or not h.value:
+                raise IdaHipError("idahip_create failed (%d) -- is a GPU visible?" % rc)
+        else:
+            self.band = (int(band[0]), int(band[1]))
+            rc = self.H.idahip_create_band(C.byref(h), int(device), self.n, self.batch, self.kind, stream, *self.band)
+            if rc != 0 or not h.value:
+                raise IdaHipError("idahip_create_band failed (%d) -- band form of this kind and size, and a GPU visible?" % rc)
         self.h = h
+
+    @property
+    def ldab(self):
+        return None if self.band is None else 2 * self.band[0] + self.band[1] + 1
+
+    def band_query(self):
+        """idahip_band -> (ml, mu) for a band ctx, None for a dense one."""
+        ml, mu = C.c_int(-1), C.c_int(-1)
+        rc = self.H.idahip_band(self.h, C.byref(ml), C.byref(mu))
+        return (ml.value, mu.value) if rc == 1 else None
 
     def close(self):
         """idahip_destroy. Refused while an Ensemble created on this ctx is still open: libidaens keeps the raw ctx pointer."""
@@ -260,6 +287,43 @@ class Ctx:
         self._cb = (RES_FN(c_res), JAC_FN(c_jac))  # keep the thunks alive as long as the ctx
         self._chk(self.H.idahip_set_host_problem(self.h, self._cb[0], self._cb[1], None), "set_host_problem")
 
+    def set_host_band_problem(self, res, bjac):
+        """IDAHIP_HOST_CALLBACK on a band ctx: res as for set_host_problem; bjac(sys, t, cj, yy, yp, res, ab) fills ab, a zeroed
+        [n][ldab] view of the system's band storage (ab[j, ml + mu + i - j] = dF_i/dy_j + cj dF_i/dy'_j), or returns such an array."""
+        n = self.n
+        self._cb_error = None
+
+        def c_res(sys, t, yy, yp, out, _user):
+            try:
+                r = res(sys, t, np.ctypeslib.as_array(yy, (n,)), np.ctypeslib.as_array(yp, (n,)))
+                np.copyto(np.ctypeslib.as_array(out, (n,)), np.asarray(r, dtype=np.float64).reshape(n))
+                return 0
+            except Exception as e:
+                self._cb_error = e
+                return 1
+
+        def c_bjac(sys, t, cj, yy, yp, rv, AB, ldab, _user):
+            try:
+                view = np.ctypeslib.as_array(AB, (n, ldab))
+                m = bjac(sys, t, cj, np.ctypeslib.as_array(yy, (n,)), np.ctypeslib.as_array(yp, (n,)), np.ctypeslib.as_array(rv, (n,)), view)
+                if m is not None:
+                    np.copyto(view, np.asarray(m, dtype=np.float64).reshape(n, ldab))
+                return 0
+            except Exception as e:
+                self._cb_error = e
+                return 1
+
+        self._cb = (RES_FN(c_res), BAND_JAC_FN(c_bjac))
+        self._chk(self.H.idahip_set_host_band_problem(self.h, self._cb[0], self._cb[1], None), "set_host_band_problem")
+
+    def download_lu_band(self, sys):
+        """Band factors [n][ldab] (row j = column j of the band storage) and pivots of one system of a band ctx."""
+        ld = self.ldab if self.ldab is not None else 1
+        ab = np.empty(self.n * ld)
+        piv = np.empty(self.n, dtype=np.int64)
+        self._chk(self.H.idahip_download_lu_band(self.h, sys, _p(ab), _p(piv, i64p)), "download_lu_band")
+        return ab.reshape(self.n, ld), piv
+
     def upload(self, field, arr, first=0):
         a = _f64(arr).reshape(-1, self.n)
         self._chk(self.H.idahip_upload(self.h, field, first, a.shape[0], _p(a)), "upload")
@@ -309,6 +373,18 @@ class Ctx:
     def ls_solve(self, dLU, dPiv, dX, dB, idx=None):
         idx = self.all_idx() if idx is None else _i32(idx)
         self._chk(self.H.idahip_ls_solve(self.h, dLU, dPiv, dX, dB, 0.0, _p(idx, i32p), idx.size), "ls_solve")
+        self._chk(self.H.idahip_sync(self.h), "sync")
+
+    def ls_setup_band(self, ml, mu, dAB, dPiv, idx=None):
+        """In-place band getrf of caller-owned device buffers dAB [batch][ldab * n], dPiv [batch][n] -> (rc, info)."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        info = np.zeros(idx.size, dtype=np.int32)
+        rc = self._chk(self.H.idahip_ls_setup_band(self.h, int(ml), int(mu), dAB, dPiv, _p(info, i32p), _p(idx, i32p), idx.size), "ls_setup_band")
+        return rc, info
+
+    def ls_solve_band(self, ml, mu, dAB, dPiv, dX, dB, idx=None):
+        idx = self.all_idx() if idx is None else _i32(idx)
+        self._chk(self.H.idahip_ls_solve_band(self.h, int(ml), int(mu), dAB, dPiv, dX, dB, 0.0, _p(idx, i32p), idx.size), "ls_solve_band")
         self._chk(self.H.idahip_sync(self.h), "sync")
 
     def wrms(self, dX, dW, idx=None):
@@ -463,6 +539,50 @@ class Ctx:
             self.H.idahip_timing_get(self.h, k, C.byref(ms), C.byref(la), C.byref(sy))
             out[name] = {"ms": ms.value, "launches": la.value, "systems": sy.value}
         return out
+
+
+# ---- band storage helpers (pure numpy; LAPACK dgbtrf layout, include/ida_hip.h idahip_create_band)
+def band_ldab(ml, mu):
+    return 2 * int(ml) + int(mu) + 1
+
+
+def band_pack(dense, ml, mu):
+    """dense [..., n, n] (logical row, column) -> band storage [..., n, ldab] (row j = column j of the storage:
+    ab[..., j, ml + mu + i - j] = A(i, j) for j - mu <= i <= j + ml). Entries outside the band are dropped, fill rows are zero."""
+    dense = np.asarray(dense, dtype=np.float64)
+    n = dense.shape[-1]
+    kv, ld = int(ml) + int(mu), band_ldab(ml, mu)
+    ab = np.zeros(dense.shape[:-2] + (n, ld))
+    for j in range(n):
+        lo, hi = max(0, j - int(mu)), min(n - 1, j + int(ml))
+        ab[..., j, kv + lo - j:kv + hi - j + 1] = dense[..., lo:hi + 1, j]
+    return ab
+
+
+def band_unpack(ab, n, ml, mu, fill=False):
+    """Inverse of band_pack -> dense [..., n, n]; fill=True also unpacks the fill rows (U's entries up to ml + mu above the diagonal)."""
+    ab = np.asarray(ab, dtype=np.float64).reshape(np.shape(ab)[:-2] + (n, band_ldab(ml, mu)))
+    kv = int(ml) + int(mu)
+    top = kv if fill else int(mu)
+    dense = np.zeros(ab.shape[:-2] + (n, n))
+    for j in range(n):
+        lo, hi = max(0, j - top), min(n - 1, j + int(ml))
+        dense[..., lo:hi + 1, j] = ab[..., j, kv + lo - j:kv + hi - j + 1]
+    return dense
+
+
+def band_expand_factors(ab, piv, n, ml, mu):
+    """Band factors and pivots (one system) -> the dense factors dense_get_rf leaves: U (with fill) as stored, and L with every
+    LATER row swap applied to it (the band kernels leave each multiplier where it was computed, as LAPACK does). [n][n] logical."""
+    d = band_unpack(ab, n, ml, mu, fill=True)
+    piv = np.asarray(piv, dtype=np.int64)
+    L = np.tril(d, -1)
+    U = np.triu(d)
+    for j in range(n):
+        p = int(piv[j])
+        if p != j:
+            L[[j, p], :j] = L[[p, j], :j]
+    return L + U
 
 
 COUNTERS = {"nst": 0, "nre": 1, "nje": 2, "nsetups": 3, "nni": 4, "netf": 5, "ncfn": 6, "n_attempts": 7, "nls_nconvfails": 8,

@@ -275,14 +275,19 @@ def heat1d(n=4096, batch=256):
             "atol": np.array([1.0e-8]), "touts": 0.01 * np.arange(1, 11)}
 
 
-def make_ctx(prob, device=0, stream=None):
+def make_ctx(prob, device=0, stream=None, band=False):
     """Create a device context for a generated problem and load its data (import kept local: this module is also
-    used by CPU-only tests)."""
+    used by CPU-only tests). band=True: a band ctx -- (1, 1) for heat1d, prob["band"] for a host-callback problem with a band
+    Jacobian prob["bjac"]; a (ml, mu) pair is taken as given."""
     from . import Ctx
     batch = prob["yy0"].shape[0]
-    ctx = Ctx(prob["kind"], prob["n"], batch, device=device, stream=stream)
+    if band is True:
+        band = (1, 1) if prob["kind"] == "heat1d" else tuple(prob["band"])
+    ctx = Ctx(prob["kind"], prob["n"], batch, device=device, stream=stream, band=band or None)
     ctx.set_tolerances(prob["rtol"], prob["atol"])
-    if prob["kind"] == "linear_dense":
+    if prob["kind"] == "host_callback" and band:
+        ctx.set_host_band_problem(prob["res"], prob["bjac"])
+    elif prob["kind"] == "linear_dense":
         step = max(1, (1 << 28) // (8 * prob["n"] * prob["n"]))  # <= 256 MiB per matrix upload
         for f in range(0, batch, step):
             ctx.set_linear_dense(prob["A"][f:f + step], prob["B"][f:f + step], prob["c"][f:f + step], first=f)
