@@ -87,9 +87,39 @@ pub trait HostProblem {
     fn jac(&self, sys: usize, tt: f64, cj: f64, yy: &[f64], yp: &[f64], resvec: &[f64], jac_colmajor: &mut [f64]);
 }
 
+/// A user problem with a residual and no Jacobian: the context forms difference-quotient Jacobians from the residual
+/// (C IDA's idaLsDenseDQJac / idaLsBandDQJac; `Ctx::set_host_residual`).
+pub trait HostResidual {
+    fn res(&self, sys: usize, tt: f64, yy: &[f64], yp: &[f64], resval: &mut [f64]);
+}
+
 struct CallbackBox {
     n: usize,
     problem: Box<dyn HostProblem>,
+}
+
+struct ResidualBox {
+    n: usize,
+    problem: Box<dyn HostResidual>,
+}
+
+unsafe extern "C" fn res_only_trampoline(s: c_int, tt: c_double, yy: *const c_double, yp: *const c_double, r: *mut c_double, user: *mut c_void) -> c_int {
+    let cb = &*(user as *const ResidualBox);
+    let n = cb.n;
+    let out = catch_unwind(AssertUnwindSafe(|| {
+        cb.problem.res(
+            s as usize,
+            tt,
+            std::slice::from_raw_parts(yy, n),
+            std::slice::from_raw_parts(yp, n),
+            std::slice::from_raw_parts_mut(r, n),
+        )
+    }));
+    if out.is_ok() {
+        0
+    } else {
+        1
+    }
 }
 
 unsafe extern "C" fn res_trampoline(s: c_int, tt: c_double, yy: *const c_double, yp: *const c_double, r: *mut c_double, user: *mut c_void) -> c_int {
@@ -147,6 +177,7 @@ pub struct Ctx {
     n: usize,
     batch: usize,
     callbacks: Option<Box<CallbackBox>>,
+    residual: Option<Box<ResidualBox>>,
 }
 
 // A ctx may move between threads; every method takes `&mut self` like the reference's solver objects, so it is not Sync.
@@ -164,7 +195,7 @@ impl Ctx {
         if rc != 0 || raw.is_null() {
             return Err(Error::Library { code: rc, message: "idahip_create failed (no GPU visible, or bad size)".to_string() });
         }
-        Ok(Ctx { raw, n, batch, callbacks: None })
+        Ok(Ctx { raw, n, batch, callbacks: None, residual: None })
     }
 
     /// A band context (`idahip_create_band`): Jacobians with lower bandwidth `ml` and upper bandwidth `mu` are stored, factored and
@@ -177,7 +208,7 @@ impl Ctx {
         if rc != 0 || raw.is_null() {
             return Err(Error::Library { code: rc, message: "idahip_create_band failed (no band form of this problem or size, or no GPU)".to_string() });
         }
-        Ok(Ctx { raw, n, batch, callbacks: None })
+        Ok(Ctx { raw, n, batch, callbacks: None, residual: None })
     }
 
     pub fn n(&self) -> usize {
@@ -245,6 +276,17 @@ impl Ctx {
         Ok(())
     }
 
+    /// The user problem of a [`Problem::HostCallback`] context (dense or band) given by its residual alone: the context forms
+    /// difference-quotient Jacobians from then on.
+    pub fn set_host_residual(&mut self, problem: Box<dyn HostResidual>) -> Result<(), Error> {
+        let cb = Box::new(ResidualBox { n: self.n, problem });
+        let user = &*cb as *const ResidualBox as *mut c_void;
+        let rc = unsafe { sys::idahip_set_host_residual(self.raw, Some(res_only_trampoline), user) };
+        self.check(rc)?;
+        self.residual = Some(cb);
+        Ok(())
+    }
+
     /// 4 = default, 3 = cross-check pipeline; both bit-identical to dense_get_rf.
     pub fn set_lu_variant(&mut self, variant: i32) -> Result<(), Error> {
         let rc = unsafe { sys::idahip_set_lu_variant(self.raw, variant) };
@@ -262,6 +304,13 @@ impl Ctx {
     /// for ensembles whose factorisations are latency bound).
     pub fn set_lu_period(&mut self, rounds: i32) -> Result<(), Error> {
         let rc = unsafe { sys::idahip_set_lu_period(self.raw, rounds) };
+        self.check(rc).map(|_| ())
+    }
+
+    /// Difference-quotient Jacobians (C IDA's idaLsDenseDQJac / idaLsBandDQJac) for every Jacobian this ctx forms.
+    /// (Like the rest of this crate, not compiled in this repository's checks.)
+    pub fn set_jacobian_dq(&mut self, on: bool) -> Result<(), Error> {
+        let rc = unsafe { sys::idahip_set_jacobian_dq(self.raw, on as i32) };
         self.check(rc).map(|_| ())
     }
 }

@@ -143,7 +143,8 @@ enum {
     IDAENS_C_NCONV_JCUR = 13 /* Q3/Q4: Newton's ConvergenceRecover with a current Jacobian, treated as recoverable          */,
     IDAENS_C_NFAIL_FIRST = 14 /* Q5: failed attempts before the first step (reset() rescales phi[1] only)                   */,
     IDAENS_C_NLI = 15 /* idaLsSolve: linear iterations (0 with a direct LSolver, src/ida_ls.rs:389-400) */,
-    IDAENS_C_NCFL = 16 /* idaLsSolve: linear convergence failures (src/ida_ls.rs:413-415) */
+    IDAENS_C_NCFL = 16 /* idaLsSolve: linear convergence failures (src/ida_ls.rs:413-415) */,
+    IDAENS_C_NRE_DQ = 17 /* residual evaluations of difference-quotient Jacobians (C IDA's nreDQ; idahip_set_jacobian_dq) */
 };
 int idaens_get_counter(const idaens* e, int which, int64_t* out);
 enum { IDAENS_R_TN = 0, IDAENS_R_HUSED = 1, IDAENS_R_HH = 2, IDAENS_R_H0U = 3, IDAENS_R_TOLSF = 4 };

@@ -171,6 +171,33 @@ int idahip_nls_sys_setup(idahip_ctx* ctx, const double* hTn, const double* hCj, 
  *          (its `powf` must be the platform libm's).                                                   */
 int idahip_nls_sys(idahip_ctx* ctx, const double* hTn, const double* hCj, int reset_ee, const int32_t* hIdx, int nsys);
 int idahip_nls_lsetup(idahip_ctx* ctx, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys);
+
+/* ---- Difference-quotient Jacobians: C IDA's idaLsDenseDQJac (dense ctx) and idaLsBandDQJac (band ctx) ----
+ * With the mode on, every Jacobian the ctx forms -- idahip_nls_lsetup_dq, the device steppers, libidaens -- is a DQ one, for every
+ * problem kind; with it off (the default) nothing changes. The definition (SUNDIALS ida_ls.c), at the ctx's yy, yp, ewt and
+ * rr = savres (the residual at tn that idahip_nls_sys left), with srur = sqrt(DBL_EPSILON), MAX(a, b) = a > b ? a : b:
+ *   inc_j = MAX(srur * MAX(|yy_j|, |hh*yp_j|), 1/ewt_j);  if (hh*yp_j < 0) inc_j = -inc_j;  inc_j = (yy_j + inc_j) - yy_j;
+ *   column j perturbed: yy_j + inc_j, yp_j + cj*inc_j.
+ *   dense: one residual rtemp per column; J(:,j) = N_VLinearSum(1/inc_j, rtemp, -1/inc_j, rr) (the serial vector's case order:
+ *          rtemp - rr for 1/inc = 1, rr - rtemp for -1, (1/inc)*(rtemp + rr) for +-0, (1/inc)*(rtemp - rr) otherwise).
+ *   band:  width = ml + mu + 1; group g < min(width, n) perturbs every column j = g (mod width) at once and takes one residual;
+ *          J(i,j) = (1/inc_j)*(rtemp_i - rr_i) for max(0, j-mu) <= i <= min(n-1, j+ml); every other band entry +0.0.
+ * A dense DQ Jacobian costs n residual evaluations, a band one min(width, n); libidaens counts them in IDAENS_C_NRE_DQ (C IDA's
+ * nreDQ), not in nre. The heat kernel writes, on a dense ctx, only rows j-1..j+1 of column j, as its analytic kernel does:
+ * entries that the definition gives as -0.0 there are +0.0. Constraints (which flip inc's sign in C IDA) do not exist here.
+ * A DQ ctx refuses idahip_nls_lsetup and idahip_nls_sys_setup (-2: they carry no step sizes); idahip_nls_lsetup_dq is
+ * idahip_nls_lsetup with them, and returns -2 on a ctx without DQ. */
+int idahip_set_jacobian_dq(idahip_ctx* ctx, int on);
+int idahip_jacobian_dq(const idahip_ctx* ctx);  /* 1 on, 0 off */
+/* IDAHIP_HOST_CALLBACK, dense or band ctx: a residual and no Jacobian. Turns DQ on: idahip_set_jacobian_dq(ctx, 0) then returns
+ * -2, until idahip_set_host_problem / idahip_set_host_band_problem registers a Jacobian again (which leaves the mode as it is). */
+int idahip_set_host_residual(idahip_ctx* ctx, idahip_res_fn res, void* user);
+int idahip_nls_lsetup_dq(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx,
+                         int nsys);
+/* The DQ Jacobian of the listed systems at the ctx-resident state, to host memory: hJ [nsys][n*n] column-major, or on a band ctx
+ * [nsys][ldab*n] in the band storage of idahip_download_lu_band. Works whatever the mode (a check of an analytic Jacobian);
+ * leaves the ctx's work matrices and factors alone. */
+int idahip_jac_dq(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hHh, double* hJ, const int32_t* hIdx, int nsys);
 int idahip_newton_iter(idahip_ctx* ctx, const double* hScale, double* hDelnrm, const int32_t* hIdx, int nsys);
 /* The first two iterations of Newton::solve in one call, without the host in between (first slice):
  *   newton body (m = 0) -> idaNlsConvTest -> NLProblem::sys -> newton body (m = 1) -> idaNlsConvTest

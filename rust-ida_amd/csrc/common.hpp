@@ -113,6 +113,14 @@ struct idahip_ctx {
     std::vector<double> cb_host;                      // host mirror of cb_stage
     double *cb_jpin = nullptr, *cb_jdev = nullptr;    // pinned / device staging of a chunk of user Jacobians (lazy)
     size_t cb_jcap = 0;                               // systems the two staging buffers hold
+    // difference-quotient Jacobians (idahip_set_jacobian_dq, dq_kernels.hpp): every Jacobian this ctx forms is a DQ one
+    int jac_dq = 0;
+    int dq_locked = 0;                                // idahip_set_host_residual: no analytic Jacobian exists, DQ stays on
+    double* dq_stage = nullptr;                       // host callbacks: [copies][3][n] perturbed yy, yp and their residual (lazy)
+    size_t dq_stage_cap = 0;                          // doubles
+    double* dq_out = nullptr;                         // idahip_jac_dq: a chunk of Jacobians before they go to the host (lazy)
+    size_t dq_out_cap = 0;                            // doubles
+    double* dq_hh = nullptr;                          // idahip_round_solve: [batch] step sizes gathered from the records (lazy)
 
     // check_list's map of the ids seen in one list: one bit per system, sized at idahip_create and all clear between calls
     std::vector<uint64_t> list_seen;

@@ -5,6 +5,7 @@
 #include "problem_kernels.hpp"
 #include "solve_kernels.hpp"
 #include "band_kernels.hpp"
+#include "dq_kernels.hpp"
 #include "vector_kernels.hpp"
 #include "tiny_ida.hpp"
 #include "round_ida.hpp"
@@ -234,7 +235,7 @@ int idahip_destroy(idahip_ctx* c) {
     DevGuard dev_guard__(c);
     if (!c) return 0;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* ptrs[] = {c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
+    void* ptrs[] = {c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
                     c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->ic_y,
                     c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d};
@@ -435,7 +436,21 @@ int idahip_set_host_problem(idahip_ctx* c, idahip_res_fn res, idahip_jac_fn jac,
     if (c->band) return fail(c, -2, "a band ctx takes a band Jacobian: idahip_set_host_band_problem");
     c->cb_res = res;
     c->cb_jac = jac;
+    c->cb_bjac = nullptr;
     c->cb_user = user;
+    c->dq_locked = 0;  // a Jacobian exists again: the mode may be switched off (it is left as it is)
+    return 0;
+}
+
+int idahip_set_host_residual(idahip_ctx* c, idahip_res_fn res, void* user) {
+    if (!c || !res) return -1;
+    if (c->kind != IDAHIP_HOST_CALLBACK) return fail(c, -2, "not an IDAHIP_HOST_CALLBACK ctx");
+    c->cb_res = res;
+    c->cb_jac = nullptr;
+    c->cb_bjac = nullptr;
+    c->cb_user = user;
+    c->jac_dq = 1;
+    c->dq_locked = 1;
     return 0;
 }
 
@@ -444,8 +459,10 @@ int idahip_set_host_band_problem(idahip_ctx* c, idahip_res_fn res, idahip_band_j
     if (c->kind != IDAHIP_HOST_CALLBACK) return fail(c, -2, "not an IDAHIP_HOST_CALLBACK ctx");
     if (!c->band) return fail(c, -2, "a dense ctx takes a dense Jacobian: idahip_set_host_problem");
     c->cb_res = res;
+    c->cb_jac = nullptr;
     c->cb_bjac = bjac;
     c->cb_user = user;
+    c->dq_locked = 0;
     return 0;
 }
 
@@ -683,7 +700,8 @@ namespace {
 // scatters the residuals (launch_sys with c->kind == IDAHIP_HOST_CALLBACK)
 int callback_sys(idahip_ctx* c, const SysArgs& a, const double* hTn, const int32_t* hIdx, int nsys) {
     const int n = c->n;
-    if (!c->cb_res || !(c->cb_jac || c->cb_bjac)) return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_problem has not been called");
+    if (!c->cb_res || !(c->cb_jac || c->cb_bjac || c->dq_locked))
+        return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_problem has not been called");
     const size_t cnt = (size_t)nsys * 3 * n;
     hipLaunchKernelGGL(callback_pre_kernel, dim3(nsys), dim3(256), 0, c->stream, a, c->cb_stage);
     if (c->cb_host.size() < cnt) c->cb_host.resize(cnt);
@@ -780,11 +798,128 @@ int launch_sys(idahip_ctx* c, const SysArgs& a, int nsys, double* jac_out, const
     return post_launch(c, "nls_sys");
 }
 
+
+// ------------------------------------------------------------------------------------------------ difference-quotient Jacobians
+// (dq_kernels.hpp; idahip_set_jacobian_dq)
+
+// residual evaluations of one DQ Jacobian of this ctx (what C IDA adds to nreDQ)
+long dq_evals(const idahip_ctx* c) { return c->band ? std::min(c->ml + c->mu + 1, c->n) : c->n; }
+
+int dq_grow(idahip_ctx* c, double** p, size_t* cap, size_t want) {
+    if (*cap >= want) return 0;
+    if (*p) IDAHIP_HIP(c, hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    if (hipMalloc((void**)p, want * sizeof(double)) != hipSuccess) {
+        *p = nullptr;
+        return fail(c, -100, "DQ staging of %zu doubles", want);
+    }
+    *cap = want;
+    return 0;
+}
+
+// Host-callback problems: dq_pack_kernel writes perturbed copies of (yy, yp), the host calls the user's residual on each copy,
+// dq_scatter_kernel differences the residuals into the Jacobian. Dense: up to G columns of m systems per pass, as many as the
+// bounded staging holds; band: one group of every system per pass. The host does no arithmetic on the entries.
+int callback_dq_jac(idahip_ctx* c, const DqArgs& d0, const double* hTn, const int32_t* hIdx, int nsys) {
+    const int n = c->n;
+    if (!c->cb_res) return fail(c, -2, "IDAHIP_HOST_CALLBACK: no residual registered (idahip_set_host_residual)");
+    if (!hTn || !hIdx) return fail(c, -2, "a host-callback DQ Jacobian needs the systems' tn and ids on the host");
+    const size_t per = 3 * (size_t)n;
+    const size_t copies = std::max<size_t>(1, ((size_t)32 << 20) / (per * sizeof(double)));  // staging <= 32 MB (or one copy)
+    const int ngroups = (int)dq_evals(c);
+    const int msys = (int)std::min<size_t>((size_t)nsys, copies);
+    const int G = c->band ? 1 : (int)std::max<size_t>(1, std::min<size_t>((size_t)n, copies / msys));
+    int rc = dq_grow(c, &c->dq_stage, &c->dq_stage_cap, (size_t)msys * G * per);
+    if (rc) return rc;
+    if (c->cb_host.size() < (size_t)msys * G * per) c->cb_host.resize((size_t)msys * G * per);
+    double* h = c->cb_host.data();
+    const size_t mat = c->band ? (size_t)c->ldab * n : (size_t)n * n;
+    for (int s0 = 0; s0 < nsys; s0 += msys) {
+        const int m = std::min(msys, nsys - s0);
+        DqArgs d = d0;
+        d.idx += s0; d.cj += s0; d.hh += s0;
+        if (d.compact) d.out += (size_t)s0 * mat;
+        for (int j0 = 0; j0 < ngroups; j0 += G) {
+            const int g = std::min(G, ngroups - j0);
+            const size_t cnt = (size_t)m * g * per;
+            hipLaunchKernelGGL(dq_pack_kernel, dim3(m, g), dim3(256), 0, c->stream, d, j0, g, c->dq_stage);
+            IDAHIP_HIP(c, hipMemcpyAsync(h, c->dq_stage, sizeof(double) * cnt, hipMemcpyDeviceToHost, c->stream));
+            IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+            for (int q = 0; q < m * g; ++q) {
+                double* hs = h + (size_t)q * per;
+                const int sp = s0 + q / g;
+                if (c->cb_res(hIdx[sp], hTn[sp], hs, hs + n, hs + 2 * n, c->cb_user) != 0)
+                    return fail(c, -7, "the user's residual function failed for system %d (DQ Jacobian)", hIdx[sp]);
+            }
+            IDAHIP_HIP(c, hipMemcpyAsync(c->dq_stage, h, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(dq_scatter_kernel, dim3(m, g), dim3(256), 0, c->stream, d, j0, g, (const double*)c->dq_stage);
+            IDAHIP_HIP(c, hipStreamSynchronize(c->stream));  // the host staging is filled again
+        }
+    }
+    return post_launch(c, "DQ jac (host callback)");
+}
+
+// DQ Jacobians of the listed systems at the ctx's yy, yp, ewt and savres: into `out` by system id (the work matrices or the band
+// storage) or, with `compact`, by list position. d_hh: the systems' step sizes, per list position.
+int launch_dq_jac(idahip_ctx* c, double* out, bool compact, const int* d_idx, const double* d_cj, const double* d_hh, int nsys,
+                  const double* hTn, const int32_t* hIdx, const int* d_skip) {
+    const int n = c->n;
+    if (nsys == 0) return 0;
+    DqArgs d;
+    d.yy = c->yy; d.yp = c->yp; d.ewt = c->ewt; d.rr = c->savres;
+    d.idx = d_idx; d.cj = d_cj; d.hh = d_hh; d.skip = d_skip;
+    d.out = out; d.compact = compact ? 1 : 0; d.n = n;
+    d.ml = c->band ? c->ml : 0; d.mu = c->band ? c->mu : 0; d.ld = c->band ? c->ldab : 0;
+    if (c->kind == IDAHIP_HOST_CALLBACK) return callback_dq_jac(c, d, hTn, hIdx, nsys);
+    if (c->band) {  // (idahip_create_band: IDAHIP_HEAT1D is the band ctx's only device kind)
+        int chunks = 1;
+        while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
+        hipLaunchKernelGGL(heat_band_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
+        return post_launch(c, "band DQ jac");
+    }
+    switch (c->kind) {
+        case IDAHIP_ROBERTS:
+            hipLaunchKernelGGL(tiny_dq_jac_kernel<IDAHIP_ROBERTS>, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, d, (const double*)nullptr, 0, nsys);
+            break;
+        case IDAHIP_LORENZ63:
+            hipLaunchKernelGGL(tiny_dq_jac_kernel<IDAHIP_LORENZ63>, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, d, (const double*)c->params, 3, nsys);
+            break;
+        case IDAHIP_LINEAR_DENSE: {
+            const int tiles = (n + LDQ_T - 1) / LDQ_T;
+            const size_t mat = (size_t)n * n;
+            for (int s0 = 0; s0 < nsys; s0 += 65535) {  // (the list runs along the grid's y dimension)
+                const int m = std::min(65535, nsys - s0);
+                DqArgs e = d;
+                e.idx += s0; e.cj += s0; e.hh += s0;
+                if (e.skip) e.skip += s0;
+                if (e.compact) e.out += (size_t)s0 * mat;
+                hipLaunchKernelGGL(linear_dq_jac_kernel, dim3(tiles * tiles, m), dim3(256), 0, c->stream, e, (const double*)c->A,
+                                   (const double*)c->B, (const double*)c->C, tiles);
+            }
+            break;
+        }
+        case IDAHIP_HEAT1D: {
+            int chunks = 1;
+            while ((long)nsys * chunks < 2048 && chunks < n) chunks *= 2;
+            hipLaunchKernelGGL(heat_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks,
+                               (!compact && out == c->jw) ? (const int*)c->lu_jwzero : nullptr);
+            break;
+        }
+        default: return fail(c, -2, "no DQ Jacobian for problem kind %d", (int)c->kind);
+    }
+    return post_launch(c, "DQ jac");
+}
+
 // Jacobian kernels of IdaNLProblem::setup (jac at the current yy, yp, cj) into the LU work matrix
 int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj, int nsys, const double* hTn = nullptr,
-               const double* hCj = nullptr, const int32_t* hIdx = nullptr, const int* d_skip = nullptr) {
+               const double* hCj = nullptr, const int32_t* hIdx = nullptr, const int* d_skip = nullptr, const double* d_hh = nullptr) {
     const int n = c->n;
     const long nn = (long)n * n;
+    if (c->jac_dq) {  // every Jacobian of a DQ ctx is a DQ one: dense into the work matrix, band into the band storage
+        if (!d_hh) return fail(c, -2, "a DQ Jacobian needs the systems' step sizes");
+        return launch_dq_jac(c, c->band ? c->bab : work, false, d_idx, d_cj, d_hh, nsys, hTn, hIdx, d_skip);
+    }
     if (c->band) {  // the band storage is the work matrix: the factorisation runs in place
         if (c->kind == IDAHIP_HOST_CALLBACK) return callback_jac(c, c->bab, d_idx, hTn, hCj, hIdx, nsys);
         int chunks = 1;
@@ -878,6 +1013,7 @@ int idahip_nls_lsetup(idahip_ctx* c, const double* hTn, const double* hCj, int32
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
     if (!hTn || !hCj || !hInfo) return fail(c, -2, "null argument");
+    if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_nls_lsetup_dq");
     if (nsys == 0) return 0;
     const int n = c->n;
     ArgPack ap;
@@ -899,6 +1035,7 @@ int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, in
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
     if (!hTn || !hCj || !hInfo) return fail(c, -2, "null argument");
+    if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_nls_sys, then idahip_nls_lsetup_dq");
     if (nsys == 0) return 0;
     const int n = c->n;
     ArgPack ap;
@@ -922,6 +1059,65 @@ int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, in
     }
     return factor_and_report(c, work, a.idx, hIdx, nsys, hInfo);
 }
+
+int idahip_nls_lsetup_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx,
+                         int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hTn || !hCj || !hHh || !hInfo) return fail(c, -2, "null argument");
+    if (!c->jac_dq) return fail(c, -2, "idahip_nls_lsetup_dq on a ctx with analytic Jacobians (idahip_set_jacobian_dq)");
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    const double* d_cj = ap.in(hCj, nsys);
+    const double* d_hh = ap.in(hHh, nsys);
+    if ((rc = ap.upload())) return rc;
+    double* work = (c->n <= TINY_N) ? c->lu : c->jw;
+    {
+        KTimer kt(c, IDAHIP_K_JAC, nsys);
+        if ((rc = launch_jac(c, work, d_idx, d_cj, nsys, hTn, hCj, hIdx, nullptr, d_hh))) return rc;
+    }
+    return factor_and_report(c, work, d_idx, hIdx, nsys, hInfo);
+}
+
+int idahip_jac_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, double* hJ, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hTn || !hCj || !hHh || !hJ) return fail(c, -2, "null argument");
+    if (nsys == 0) return 0;
+    const size_t mat = c->band ? (size_t)c->ldab * c->n : (size_t)c->n * c->n;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    const double* d_cj = ap.in(hCj, nsys);
+    const double* d_hh = ap.in(hHh, nsys);
+    if ((rc = ap.upload())) return rc;
+    // a chunk of systems at a time through a buffer of its own: the ctx's work matrices and factors are left as they are
+    const int m = (int)std::max<size_t>(1, std::min<size_t>((size_t)nsys, ((size_t)256 << 20) / (mat * sizeof(double))));
+    if ((rc = dq_grow(c, &c->dq_out, &c->dq_out_cap, (size_t)m * mat))) return rc;
+    for (int s0 = 0; s0 < nsys; s0 += m) {
+        const int k = std::min(m, nsys - s0);
+        {
+            KTimer kt(c, IDAHIP_K_JAC, k);
+            if ((rc = launch_dq_jac(c, c->dq_out, true, d_idx + s0, d_cj + s0, d_hh + s0, k, hTn + s0, hIdx + s0, nullptr))) return rc;
+        }
+        IDAHIP_HIP(c, hipMemcpyAsync(hJ + (size_t)s0 * mat, c->dq_out, sizeof(double) * k * mat, hipMemcpyDeviceToHost, c->stream));
+        IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return ap.finish_async();
+}
+
+int idahip_set_jacobian_dq(idahip_ctx* c, int on) {
+    if (!c) return -1;
+    if (!on && c->dq_locked) return fail(c, -2, "the ctx has a residual and no Jacobian (idahip_set_host_residual): DQ stays on");
+    c->jac_dq = on ? 1 : 0;
+    return 0;
+}
+
+int idahip_jacobian_dq(const idahip_ctx* c) { return c ? c->jac_dq : -1; }
 
 // One Newton iteration body for the listed systems (shared by idahip_newton_iter and idahip_newton_iter2)
 static int launch_newton_iter(idahip_ctx* c, const int* d_idx, const double* d_scale, double* d_out, const int* d_skip, int nsys) {
@@ -1346,6 +1542,7 @@ int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_
     a.ic_y = c->ic_y; a.ic_yp = c->ic_yp;
     a.f = flow_args(c, call);
     a.roots = (idahip_root_state*)c->tiny_roots;
+    a.jac_dq = c->jac_dq;
     a.max_rounds = call->max_rounds;
     a.round_base = call->round_base;
     a.yout = hYout ? c->tiny_yout : nullptr;
@@ -1463,7 +1660,8 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     a.yout = hYout ? c->tiny_yout : nullptr;
     a.ypout = hYPout ? c->tiny_ypout : nullptr;
     a.round_base = call->round_base;
-    a.fused_jac = c->kind == IDAHIP_LINEAR_DENSE ? 1 : 0;
+    a.fused_jac = (c->kind == IDAHIP_LINEAR_DENSE && !c->jac_dq) ? 1 : 0;
+    if (c->jac_dq && !c->dq_hh && (rc = dalloc(c, &c->dq_hh, (size_t)batch))) return rc;
     a.lu_period = c->lu_period;
     a.roots = (idahip_root_state*)c->tiny_roots;
     int* ib = c->rnd_i;
@@ -1507,7 +1705,7 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
             sa.reset_ee = 1; sa.skip = a.skipP;
             if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
         }
-        if (c->kind == IDAHIP_LINEAR_DENSE) {
+        if (a.fused_jac) {
             KTimer kt(c, IDAHIP_K_SYS_JAC, 0);
             sa.skip = a.skipL;
             if ((rc = launch_sys(c, sa, batch, c->jw))) return rc;
@@ -1518,7 +1716,10 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
                 if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
             }
             KTimer kt(c, IDAHIP_K_JAC, 0);
-            if ((rc = launch_jac(c, c->jw, a.ident, a.cj, batch, nullptr, nullptr, nullptr, a.skipL))) return rc;
+            if (c->jac_dq)  // the systems' hh from their records, and their nre_dq
+                hipLaunchKernelGGL(dq_round_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh,
+                                   batch, dq_evals(c));
+            if ((rc = launch_jac(c, c->jw, a.ident, a.cj, batch, nullptr, nullptr, nullptr, a.skipL, c->dq_hh))) return rc;
         }
         {
             int nlu = batch;

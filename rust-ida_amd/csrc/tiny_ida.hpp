@@ -20,6 +20,7 @@
 // cases): user root functions, IDA_ONE_STEP, host-callback problems, per-step traces.
 #pragma once
 #include "ida_flow.hpp"
+#include "dq_kernels.hpp"
 #include "lu_kernels.hpp"
 #include "problem_kernels.hpp"
 #include "solve_kernels.hpp"
@@ -42,6 +43,7 @@ struct TinyIdaArgs {
     double *yout, *ypout;        // [ntout][batch][n] or null: y, y' at every tout reached
     long long* rounds_done;      // [batch] rounds this system took part in during this launch
     idahip_root_state* roots;    // [batch] or null (f.nrt == 0)
+    int jac_dq;                  // idahip_set_jacobian_dq: difference-quotient Jacobians (dq_kernels.hpp)
 };
 
 // vector backend of IdaFlow: one thread owns system b (the arithmetic of vector_kernels.hpp, element for element)
@@ -225,8 +227,17 @@ struct TinyNewton {
     __device__ int lsetup() const {
         double y[TINY_N], J[TINY_N * TINY_N];
         for (int i = 0; i < n; ++i) y[i] = a.v.yy[vb + i];
-        if (KIND == IDAHIP_ROBERTS) roberts_jac(s.cj, y, J);
-        else lorenz_jac(a.params + (long)b * a.nparam, s.cj, y, J);
+        const double* prm = KIND == IDAHIP_ROBERTS ? nullptr : a.params + (long)b * a.nparam;
+        if (a.jac_dq) {  // idaLsDenseDQJac at (yy, yp, savres) with the attempt's hh: n residual evaluations
+            double yp[3], w[3], r0[3];
+            for (int i = 0; i < 3; ++i) { yp[i] = a.v.yp[vb + i]; w[i] = a.v.ewt[vb + i]; r0[i] = a.savres[vb + i]; }
+            tiny_dq_jac<KIND>(y, yp, w, r0, s.cj, s.hh, prm, J);
+            s.nre_dq += 3;
+        } else if (KIND == IDAHIP_ROBERTS) {
+            roberts_jac(s.cj, y, J);
+        } else {
+            lorenz_jac(prm, s.cj, y, J);
+        }
         double* M = a.lu + lub;
         for (int e = 0; e < n * n; ++e) M[e] = J[e];
         int lperm[TINY_N];

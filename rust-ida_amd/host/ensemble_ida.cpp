@@ -412,27 +412,50 @@ int r_check3(idaens* e, int b) {
     return ier;
 }
 
+// residual evaluations of one band DQ Jacobian (idaLsBandDQJac): min(ml + mu + 1, n)
+long dq_band_evals(idaens* e) {
+    int ml = 0, mu = 0;
+    idahip_band(e->ctx, &ml, &mu);
+    return std::min<long>((long)ml + mu + 1, (long)e->n);
+}
+
 // ---------------------------------------------------------------- the batched Newton solve (newton.rs:51-167)
 // `act`: systems taking a step attempt this round, with s.call_lsetup decided. Sets s.nls_ret.
 int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
     std::vector<Sys>& S = e->sys;
     std::vector<int32_t> R(act), I, C, L, P;
     std::vector<uint8_t> jbad(e->batch, 0);
-    std::vector<double> tn, cj, sc, nrm;
+    std::vector<double> tn, cj, hh, sc, nrm;
     std::vector<int32_t> info;
     while (!R.empty() || !I.empty()) {
         if (!R.empty()) {
             // sys(y0), y <- y0 = 0 (newton.rs:73); the systems whose Newton solve then calls setup (call_lsetup) get both
             // in one device call, the others sys alone
             L.clear(); P.clear();
-            for (int b : R) (S[b].call_lsetup ? L : P).push_back(b);
+            // a DQ ctx (idahip_set_jacobian_dq): sys for all of them, then the setups with their step sizes
+            const bool dq = idahip_jacobian_dq(e->ctx) > 0;
+            for (int b : R) (S[b].call_lsetup && !dq ? L : P).push_back(b);
             if (!P.empty()) {
                 tn.clear(); cj.clear();
                 for (int b : P) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); }
                 ENS_CALL(e, idahip_nls_sys(e->ctx, tn.data(), cj.data(), 1, P.data(), (int)P.size()));
             }
             for (int b : R) S[b].nre += 1;
-            if (!L.empty()) {
+            if (dq)
+                for (int b : R)
+                    if (S[b].call_lsetup) L.push_back(b);
+            if (!L.empty() && dq) {
+                tn.clear(); cj.clear(); hh.clear();
+                for (int b : L) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); hh.push_back(S[b].hh); }
+                info.assign(L.size(), 0);
+                ENS_CALL(e, idahip_nls_lsetup_dq(e->ctx, tn.data(), cj.data(), hh.data(), info.data(), L.data(), (int)L.size()));
+                const long evals = idahip_band(e->ctx, nullptr, nullptr) > 0 ? dq_band_evals(e) : (long)e->n;
+                for (size_t q = 0; q < L.size(); ++q) {
+                    Sys& s = S[L[q]];
+                    s.nre_dq += evals;
+                    after_lsetup(s, info[q]);
+                }
+            } else if (!L.empty()) {
                 tn.clear(); cj.clear();
                 for (int b : L) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); }
                 info.assign(L.size(), 0);
@@ -1400,6 +1423,7 @@ int idaens_get_counter(const idaens* e, int which, int64_t* out) {
             case IDAENS_C_NFAIL_FIRST: v = s.nfail_first; break;
             case IDAENS_C_NLI: v = s.nli; break;
             case IDAENS_C_NCFL: v = s.ncfl; break;
+            case IDAENS_C_NRE_DQ: v = s.nre_dq; break;
             default: return -2;
         }
         out[b] = v;

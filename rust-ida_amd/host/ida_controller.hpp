@@ -67,6 +67,7 @@ struct SysCore {
     // --- IdaNLProblem / IdaLProblem scalars (src/ida_nls.rs:27-59, src/ida_ls.rs:84-105)
     double cj = 0.0, cjold = 0.0, cjratio = 0.0, ss = 0.0, oldnrm = 0.0, toldel = 0.0;
     long nre = 0, nsetups = 0, nje = 0;
+    long nre_dq = 0;  // residual evaluations of difference-quotient Jacobians (C IDA's nreDQ), not counted in nre
     long nli = 0, ncfl = 0;  // idaLsSolve's counters (ida_ls.rs:389-418): linear iterations, linear convergence failures
     // --- Newton (crates/nonlinear/src/newton.rs:14-32)
     bool jcur = false;

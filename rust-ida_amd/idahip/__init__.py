@@ -41,6 +41,7 @@ HIP_SYMBOLS = [
     "idahip_tiny_solve", "idahip_pow_batch", "idahip_round_solve", "idahip_lu_variant",
     "idahip_restore_initial", "idahip_ls_type", "idahip_ls_num_iters", "idahip_ls_res_norm", "idahip_timing_build", "idahip_concurrent_streams", "idahip_release_streams", "idahip_stream_pair_share", "idahip_set_lu_superpanel", "idahip_lu_superpanel", "idahip_set_lu_period", "idahip_lu_period",
     "idahip_create_band", "idahip_band", "idahip_set_host_band_problem", "idahip_download_lu_band", "idahip_ls_setup_band", "idahip_ls_solve_band",
+    "idahip_set_jacobian_dq", "idahip_jacobian_dq", "idahip_set_host_residual", "idahip_jac_dq", "idahip_nls_lsetup_dq",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
@@ -136,6 +137,11 @@ def load():
     H.idahip_pow_batch.argtypes = [vp, dp, dp, dp, C.c_size_t]
     H.idahip_newton_iter2.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, i32p, i32p, ci]
     H.idahip_set_host_problem.argtypes = [vp, RES_FN, JAC_FN, vp]
+    H.idahip_set_jacobian_dq.argtypes = [vp, ci]
+    H.idahip_jacobian_dq.argtypes = [vp]
+    H.idahip_set_host_residual.argtypes = [vp, RES_FN, vp]
+    H.idahip_jac_dq.argtypes = [vp, dp, dp, dp, dp, i32p, ci]
+    H.idahip_nls_lsetup_dq.argtypes = [vp, dp, dp, dp, i32p, i32p, ci]
     H.idahip_timing_enable.argtypes = [vp, ci]
     H.idahip_timing_get.argtypes = [vp, ci, dp, i64p, i64p]
     H.idahip_timing_reset.argtypes = [vp]
@@ -286,6 +292,49 @@ class Ctx:
 
         self._cb = (RES_FN(c_res), JAC_FN(c_jac))  # keep the thunks alive as long as the ctx
         self._chk(self.H.idahip_set_host_problem(self.h, self._cb[0], self._cb[1], None), "set_host_problem")
+
+    def set_host_residual(self, res):
+        """IDAHIP_HOST_CALLBACK, dense or band ctx: a residual res(sys, t, yy, yp) -> vector and no Jacobian. The ctx forms
+        difference-quotient Jacobians from then on (set_jacobian_dq(False) is refused)."""
+        n = self.n
+        self._cb_error = None
+
+        def c_res(sys, t, yy, yp, out, _user):
+            try:
+                r = res(sys, t, np.ctypeslib.as_array(yy, (n,)), np.ctypeslib.as_array(yp, (n,)))
+                np.copyto(np.ctypeslib.as_array(out, (n,)), np.asarray(r, dtype=np.float64).reshape(n))
+                return 0
+            except Exception as e:
+                self._cb_error = e
+                return 1
+
+        self._cb = (RES_FN(c_res),)
+        self._chk(self.H.idahip_set_host_residual(self.h, self._cb[0], None), "set_host_residual")
+
+    def set_jacobian_dq(self, on=True):
+        """Difference-quotient Jacobians (C IDA's idaLsDenseDQJac / idaLsBandDQJac) for every Jacobian this ctx forms."""
+        self._chk(self.H.idahip_set_jacobian_dq(self.h, int(bool(on))), "set_jacobian_dq")
+
+    def jacobian_dq(self):
+        return bool(self._chk(self.H.idahip_jacobian_dq(self.h), "jacobian_dq"))
+
+    def jac_dq(self, tn, cj, hh, idx=None):
+        """The DQ Jacobian of the listed systems at the ctx-resident yy, yp, ewt and savres: [len(idx)][n][n] with
+        J[s, j, i] = J_s(i, j) (column-major per system), or on a band ctx [len(idx)][n][ldab] (the band storage)."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        tn, cj, hh = (_f64(np.broadcast_to(v, idx.shape)) for v in (tn, cj, hh))
+        per = self.ldab if self.band else self.n
+        out = np.zeros((idx.size, self.n, per), dtype=np.float64)
+        self._chk(self.H.idahip_jac_dq(self.h, _p(tn), _p(cj), _p(hh), _p(out), _p(idx, i32p), idx.size), "jac_dq")
+        return out
+
+    def nls_lsetup_dq(self, tn, cj, hh, idx=None):
+        """nls_lsetup on a DQ ctx: the systems' step sizes hh go with tn and cj."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        tn, cj, hh = (_f64(np.broadcast_to(v, idx.shape)) for v in (tn, cj, hh))
+        info = np.zeros(idx.size, dtype=np.int32)
+        rc = self._chk(self.H.idahip_nls_lsetup_dq(self.h, _p(tn), _p(cj), _p(hh), _p(info, i32p), _p(idx, i32p), idx.size), "nls_lsetup_dq")
+        return rc, info
 
     def set_host_band_problem(self, res, bjac):
         """IDAHIP_HOST_CALLBACK on a band ctx: res as for set_host_problem; bjac(sys, t, cj, yy, yp, res, ab) fills ab, a zeroed
@@ -586,7 +635,8 @@ def band_expand_factors(ab, piv, n, ml, mu):
 
 
 COUNTERS = {"nst": 0, "nre": 1, "nje": 2, "nsetups": 3, "nni": 4, "netf": 5, "ncfn": 6, "n_attempts": 7, "nls_nconvfails": 8,
-            "kused": 9, "kk": 10, "nge": 11, "nlufail": 12, "nconv_jcur": 13, "nfail_first": 14, "nli": 15, "ncfl": 16}
+            "kused": 9, "kk": 10, "nge": 11, "nlufail": 12, "nconv_jcur": 13, "nfail_first": 14, "nli": 15, "ncfl": 16,
+            "nre_dq": 17}
 REALS = {"tn": 0, "hused": 1, "hh": 2, "h0u": 3, "tolsf": 4}
 
 
