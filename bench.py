@@ -5,6 +5,11 @@ Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (
 by torch.distributed.run, one rank per GPU; started by hand without a launcher (`python bench.py --gpus 2`, no WORLD_SIZE in
 the environment) it starts the N ranks itself as child processes, before anything of torch or HIP is loaded.
 
+Such a plain run does only what `value` needs: it generates and uploads the inputs, calibrates and spins up the stream, runs the
+W warm-up and the K timed steps, writes --dump-outputs when asked and prints the line. Everything else the benchmark measures or
+checks comes with --full, after the same timed steps: the kernels' own figures, the verification pass (ensemble_result,
+--results-npz), the whole-pass figures and the CPU baseline (N = 1), the groups' stream-share probe.
+
 Workload (BASELINE.json configs[2]): synthetic random linear dense index-1 DAE
 F = A y' + B y - c, N = 512, batch B = 4096 systems per GPU (distinct matrices per system, all device resident),
 rtol 1e-6, atol 1e-8, integrated from t = 0 to t = 1 with outputs every 0.1 (ten Ida::solve calls per system, handed over
@@ -18,12 +23,12 @@ What is timed.
                for it, 1..4 triangular solves + WRMS norms -> error test -> complete_step or restore, for every one of the B
                systems). value = Newton iterations of all systems on all ranks during the K timed steps / max over ranks of
                the wall time of those steps, inputs resident in HBM, NO event timers or extra synchronisation inside.
-  whole_pass   SURVEY 8(d)'s protocol next to it (N = 1 only): the whole ensemble from fresh state, t = 0 -> 1, median of 10
+  whole_pass   (--full) SURVEY 8(d)'s protocol next to it (N = 1 only): the whole ensemble from fresh state, t = 0 -> 1, median of 10
                passes (--passes; Newton iterations of the pass / its wall time).
   kernel_classes_rank0, roofline, lu_plus_solve
-               measured in further, untimed repetitions of the K steps with HIP-event timers on the ctx stream: once per
+               (--full) measured in further, untimed repetitions of the K steps with HIP-event timers on the ctx stream: once per
                kernel class, once per kernel of the LU (the dominant kernel's `roofline`).
-  device_controller, newton_fusion  (N = 1 only) the whole pass again with the lock-step HOST stepper (idaens_set_device_controller(0))
+  device_controller, newton_fusion  (--full, N = 1 only) the whole pass again with the lock-step HOST stepper (idaens_set_device_controller(0))
                and, on top of that, with one host round trip per Newton iteration: the before/after of moving the controller to the
                device. Same work, same results.
 Scheduling (results do not depend on either): the rank's systems run as --groups ensembles side by side on the device and a
@@ -434,6 +439,106 @@ WORKLOADS = {
 }
 
 
+def kernel_figures(args, world, G, count, tim, tim2, value, iters_all, elapsed_max):
+    """(--full) The kernels' own figures of the line, from the two timer passes (tim: per kernel class, tim2: per kernel of the
+    LU): kernel_classes_rank0, lu_kernels_rank0, the dominant kernel's roofline, lu_plus_solve and, for config 3, hbm_roofline."""
+    ab = algorithmic_bytes(args.n, args.workload)
+    cls_names = ("newton_iter", "sys", "sys_jac", "jac", "lu", "vector")
+    total_ms = sum(tim[k]["ms"] for k in cls_names)
+    classes = {}
+    for k in cls_names:
+        v = tim[k]
+        ent = {"ms": round(v["ms"], 3), "calls": v["launches"], "systems": v["systems"],
+               "share_of_device_time": round(v["ms"] / total_ms, 4) if total_ms > 0 else None}
+        if ab.get(k) and v["ms"] > 0:
+            gbs = round(ab[k] * v["systems"] / (v["ms"] * 1e-3) / 1e9, 1)
+            if args.workload == "heat1d" and k == "newton_iter":
+                # the factors of the banded Jacobian are zero almost everywhere and the solves leave all-zero 64 x 64 blocks out
+                # (exactly: solve_kernels.hpp): the dense byte count is not what moves, so no fraction of the peak is claimed
+                ent["GB/s_dense_equivalent"] = gbs
+            else:
+                ent["GB/s"] = gbs
+                ent["frac_of_hbm_peak"] = round(gbs / HBM_PEAK_GBS, 4)
+        classes[k] = ent
+    lu_kernels = {}
+    for k in ("lu_panel", "lu_trail", "lu_finalize"):
+        v = tim2[k]
+        lu_kernels[k] = {"ms": round(v["ms"], 3), "launches": v["launches"], "matrix_launches": v["systems"]}
+    # the dominant kernel: by device time among the classes' kernels, with the LU split into its kernels
+    lu_sub_ms = sum(tim2[k]["ms"] for k in ("lu_panel", "lu_trail", "lu_finalize"))
+    scale = tim["lu"]["ms"] / lu_sub_ms if lu_sub_ms > 0 else 0.0  # level-2 pass -> level-1 pass (same work, fewer syncs)
+    cand = {k: tim[k]["ms"] for k in ("newton_iter", "sys", "sys_jac", "jac")}
+    cand.update({k: tim2[k]["ms"] * scale for k in ("lu_panel", "lu_trail", "lu_finalize")})
+    dom = max(cand, key=cand.get)
+    if dom == "lu_trail" and args.n > 8 and args.workload != "heat1d":
+        flops, nbytes, nl = trailing_work(args.n)
+        mats = tim2["lu"]["systems"]                    # matrices factorised in the level-2 pass
+        v = tim2["lu_trail"]
+        tfl = flops * mats / (v["ms"] * 1e-3) / 1e12
+        tr = profiled_traffic("lu_trail64w_kernel") if (args.workload == "linear_dense" and args.n == 512) else None
+        roof = {"bound": "valu", "kernel": "lu_trail64w_kernel<%d> (rank-64 trailing update + U12 solve of the batched getrf)" % (1024 if args.n <= 1024 else 4096),
+                "share_of_device_time": round(cand[dom] / total_ms, 4),
+                "achieved": round(tfl, 2), "peak": VALU_UNFUSED_TFLOPS, "unit": "TFLOP/s", "frac": round(tfl / VALU_UNFUSED_TFLOPS, 4),
+                "peak_note": "fp64 vector ceiling of the reference's arithmetic: a multiply and a subtract per update (dense.rs:151), "
+                             "half of the 78.6 TFLOP/s FMA peak at 2.4 GHz; the chip holds about 1.8 GHz in this kernel",
+                "frac_of_fma_peak": round(tfl / VALU_FMA_TFLOPS, 4),
+                "avg_launch_ms": round(v["ms"] / max(1, v["launches"]), 4), "launches": v["launches"],
+                "algorithmic_flops_per_matrix": flops, "algorithmic_bytes_per_matrix": nbytes,
+                "hbm_GB/s_on_algorithmic_bytes": round(nbytes * mats / (v["ms"] * 1e-3) / 1e9, 1),
+                "traffic": None if tr is None else int(tr["hbm_bytes_per_matrix"] * mats / max(1, v["launches"])),
+                "traffic_bytes_per_matrix": None if tr is None else tr["hbm_bytes_per_matrix"],
+                "traffic_source": None if tr is None else "%s (rocprofv3 --pmc passes of this command at commit %s)" % (tr["source"], tr["commit"])}
+    elif args.n <= 8:
+        # the device-resident stepper: one kernel does everything; timed under the "vector" class
+        d = tim["vector"]
+        nb = 24 * args.n * args.n + 80 * args.n  # algorithmic bytes of one Newton iteration (SURVEY 8(d))
+        ach = nb * iters_all / (elapsed_max * 1e9) if elapsed_max > 0 else 0.0
+        roof = {"bound": "hbm", "kernel": "tiny_ida_kernel (the whole of Ida::solve, one thread per system, controller on the device)",
+                "share_of_device_time": 1.0, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 6),
+                "traffic": None, "avg_launch_ms": round(d["ms"] / max(1, d["launches"]), 4),
+                "note": "latency bound: 72-byte matrices, one thread per system (SURVEY 8(d): the roofline fraction is meaningless "
+                        "for this configuration; iterations per second is the figure)"}
+    else:
+        cls = "lu" if dom.startswith("lu_") else dom  # (banded workload: the getrf as a whole on its algorithmic bytes)
+        d = tim[cls]
+        ach = ab.get(cls, 0) * d["systems"] / (d["ms"] * 1e-3) / 1e9 if d["ms"] > 0 else 0.0
+        roof = {"bound": "hbm", "kernel": {"sys": "linear_sys_kernel<2, false>", "sys_jac": "linear_sys_kernel<2, true>",
+                                           "newton_iter": "newton_iter_kernel<2>", "jac": "linear_jac_kernel",
+                                           "lu": "batched getrf (all its kernels: panel, trailing update, row scatter)"}.get(cls, cls),
+                "share_of_device_time": round((d["ms"] if cls == "lu" else cand[dom]) / total_ms, 4) if total_ms > 0 else None,
+                "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
+                "avg_launch_ms": round(d["ms"] / max(1, d["launches"]), 4)}
+    figs = {
+        "roofline": roof,
+        "kernel_classes_rank0": classes,
+        "lu_kernels_rank0": lu_kernels,
+        "kernel_figures_measured_on": ("the %d groups' one ensemble" % G if G == 1 else
+                                       "ONE ensemble of all %d systems of the rank, alone on the device, after the timed region (K rounds with per-class "
+                                       "event timers, K more with per-kernel timers for the LU): kernel_classes_rank0, lu_kernels_rank0, roofline, "
+                                       "lu_plus_solve and hbm_roofline's iterations per setup are the kernels' own figures at whole-batch launch sizes; "
+                                       "`value` runs the same kernels as %d groups side by side" % (count, G)),
+        "lu_plus_solve": lu_plus_solve(tim, args.n, "unfused", dense=args.workload != "heat1d") if args.n > 8 else None,
+    }
+    if args.workload == "linear_dense":
+        # north_star: the rate as a fraction of the HBM roofline. BASELINE.md section 3: one Newton iteration moves 24 N^2 + 80 N
+        # bytes (solve + residual), a linear-solver setup (40 N^2 + 8 N bytes: Jacobian + factor) is shared by the r iterations
+        # measured per setup in this run
+        N = args.n
+        it_bytes, ls_bytes = 24 * N * N + 80 * N, 40 * N * N + 8 * N
+        n_it = tim["newton_iter"]["systems"]
+        n_ls = tim["lu"]["systems"]
+        r = n_it / n_ls if n_ls else None
+        per_gpu = 8.0e12 / it_bytes
+        figs["hbm_roofline"] = {
+            "iters_per_s_per_gpu": round(per_gpu), "frac": value / (world * per_gpu),
+            "newton_iters_per_lsetup": None if r is None else round(r, 2),
+            "iters_per_s_per_gpu_with_lsetup": None if r is None else round(8.0e12 / (it_bytes + ls_bytes / r)),
+            "frac_with_lsetup": None if r is None else value / (world * 8.0e12 / (it_bytes + ls_bytes / r)),
+            "note": "8 TB/s over the algorithmic bytes of BASELINE.md section 3; the factorisation itself is bound by the fp64 vector "
+                    "pipe at this N, not by HBM (`roofline`, `lu_plus_solve`)"}
+    return figs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -443,17 +548,23 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="systems per GPU")
     ap.add_argument("--workload", choices=tuple(WORKLOADS), default="linear_dense",
                     help="linear_dense = config 3 (the headline, N=512 B=4096); heat1d = config 4 (N=4096 B=256); lorenz63 = config 2 (N=3 B=1024)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the whole-pass figures (N = 1 extras)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the benchmark measures or checks: the kernels' own figures "
+                         "(kernel_classes_rank0, lu_kernels_rank0, roofline, lu_plus_solve, hbm_roofline), the verification pass "
+                         "(ensemble_result), the whole-pass figures and the CPU baseline (N = 1), the groups' stream-share probe; "
+                         "without it a run does only what `value` needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the whole-pass figures (N = 1 extras)")
     ap.add_argument("--groups", type=int, default=None,
                     help="ensembles per GPU, each with 1/groups of the rank's systems on its own HIP stream and host thread "
                          "(idaens_stream_group; default: %s)" % ", ".join("%s %d" % kv for kv in DEFAULT_GROUPS.items()))
     ap.add_argument("--lu-period", type=int, default=None, help="linear setups only in every k-th round of the device lock-step stepper "
                     "(default: %s)" % ", ".join("%s %d" % kv for kv in DEFAULT_LU_PERIOD.items()))
-    ap.add_argument("--passes", type=int, default=10, help="whole passes timed for `whole_pass` (SURVEY 8(d): >= 10 repetitions on fresh state, median)")
+    ap.add_argument("--passes", type=int, default=10, help="whole passes timed for `whole_pass` with --full (SURVEY 8(d): >= 10 repetitions "
+                    "on fresh state, median)")
     ap.add_argument("--results-npz", default=None,
-                    help="rank 0 writes the concatenated per-system results of the ensemble's verification pass (nst, nni, y(tout), y'(tout) in "
-                         "global system order, SURVEY 8(e): 'host concatenates') to this file")
+                    help="with --full: rank 0 writes the concatenated per-system results of the ensemble's verification pass (nst, nni, y(tout), "
+                         "y'(tout) in global system order, SURVEY 8(e): 'host concatenates') to this file")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed stream computed in its last step as DIR/<name>.npy (float64): y and y' "
                          "of every system, its time tn, last step size hused and counters, and `system`, the global id of each row; at most "
@@ -464,6 +575,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.results_npz and not args.full:
+        ap.error("--results-npz writes the results of the verification pass, which only --full runs")
     dn, db = {"linear_dense": (512, 4096), "heat1d": (4096, 256), "lorenz63": (3, 1024)}[args.workload]
     args.n = dn if args.n is None else args.n
     args.batch = db if args.batch is None else args.batch
@@ -510,22 +623,26 @@ def main():
         gstreams, nconc = (idahip.concurrent_streams(G, dev_early) if G > 1 else ([None], 1))
     except idahip.IdaHipError:  # the probe could not run: ordinary streams (every context creates its own), and the line says so
         gstreams, nconc = [None] * G, 0
-    # (diagnostic in the line: the least even share of the chip between two of the groups' streams, 1 = interleaved dispatch)
-    try:
-        share_min = None if nconc == 0 else min([idahip.stream_pair_share(gstreams[i], gstreams[j], dev_early) for i in range(G) for j in range(G) if i != j], default=None)
-    except idahip.IdaHipError:  # a diagnostic must not stop the run
-        share_min = None
+    # (--full, diagnostic in the line: the least even share of the chip between two of the groups' streams, 1 = interleaved dispatch)
+    share_min = None
+    if args.full:
+        try:
+            share_min = None if nconc == 0 else min([idahip.stream_pair_share(gstreams[i], gstreams[j], dev_early) for i in range(G) for j in range(G) if i != j], default=None)
+        except idahip.IdaHipError:  # a diagnostic must not stop the run
+            share_min = None
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    # (--full, more than one group) one more context with ALL of the rank's systems: the per-kernel timers run on that one, at the
+    # launch sizes the roofline figures of earlier rounds are quoted for
+    want_kctx = args.full and G > 1
     if args.workload == "linear_dense":
         # the shard's matrices go from the generator to the device a slice (<= 2 GiB) at a time: the process never holds the
         # 17 GB host copy of its shard (eight ranks of a node would hold 137 GB), only the calibration / CPU-baseline sample
-        keep = max(Runner.CALIBRATION_SYSTEMS, nsmall if (rank == 0 and world == 1 and not args.no_cpu_baseline) else 0)
+        keep = max(Runner.CALIBRATION_SYSTEMS, nsmall if want_cpu else 0)
         rehearse_early = os.environ.get("IDAHIP_BENCH_REHEARSE") == "1"
-        # every group's context, and (more than one group) one context with ALL of the rank's systems: the per-kernel timers
-        # run on that one, at the launch sizes the roofline figures of earlier rounds are quoted for
-        parts = [(goff[g], gsz[g], gstreams[g]) for g in range(G)] + ([(0, count, None)] if G > 1 else [])
+        parts = [(goff[g], gsz[g], gstreams[g]) for g in range(G)] + ([(0, count, None)] if want_kctx else [])
         made = problems.make_ctxs_linear_dense_streamed(args.n, first, count, parts, procs=procs, device=0 if rehearse_early else local_rank, keep=keep)
         stream_ctxs, probs = [m[0] for m in made[:G]], [m[1] for m in made[:G]]
-        full_ctx, full_prob = made[G] if G > 1 else (None, None)
+        full_ctx, full_prob = made[G] if want_kctx else (None, None)
         prob = probs[0]
     else:
         full = problems.heat1d(n=args.n, batch=args.batch * world) if args.workload == "heat1d" else problems.lorenz63(batch=args.batch * world)
@@ -537,7 +654,7 @@ def main():
     t_gen = time.time() - t0
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu:
         small = {k: (v[:nsmall] if isinstance(v, np.ndarray) and v.ndim >= 2 and v.shape[0] >= nsmall else v) for k, v in prob.items()}
         cpu = cpu_baseline(small, ncpu)
 
@@ -569,11 +686,13 @@ def main():
     if stream_ctxs is None:
         stream_ctxs = [problems.make_ctx(p_, device=local_rank, stream=gstreams[g]) for g, p_ in enumerate(probs)]
     run = Runner(probs, local_rank, ctxs=stream_ctxs, serial=os.environ.get("IDAHIP_BENCH_SERIAL_GROUPS") == "1")
-    # the kernels' own figures (kernel_classes_rank0, lu_kernels_rank0, roofline, lu_plus_solve) are measured on ONE ensemble of all
-    # of the rank's systems, alone on the device, after the timed region: a kernel's event-to-event time is only its own when
+    # (--full) the kernels' own figures (kernel_classes_rank0, lu_kernels_rank0, roofline, lu_plus_solve) are measured on ONE ensemble
+    # of all of the rank's systems, alone on the device, after the timed region: a kernel's event-to-event time is only its own when
     # no other stream shares the chip, and the launch sizes are then those of a whole batch
     Runner.STAGGER = run.stagger
-    krun = run if G == 1 else Runner([full_prob], local_rank, ctxs=[full_ctx] if full_ctx is not None else None)
+    krun = None
+    if args.full:
+        krun = run if G == 1 else Runner([full_prob], local_rank, ctxs=[full_ctx] if full_ctx is not None else None)
     for p_ in probs + [prob]:  # host copies of the matrices are no longer needed
         p_.pop("A", None)
         p_.pop("B", None)
@@ -608,20 +727,22 @@ def main():
             dump = {"dir": args.dump_outputs, "systems": int(rows.size), "total_systems": args.batch * world,
                     "bytes": write_outputs(args.dump_outputs, parts)}
 
-    # ---- untimed repetitions of the same K steps with event timers: per kernel class, then per kernel of the LU
-    tim = krun.timed_steps(args.steps, 1)
-    tim2 = krun.timed_steps(args.steps, 2)
-    if TIME_ALL:
-        tim = tim2  # the timers were never reset: both are totals over every launch of the process
+    # ---- (--full) untimed repetitions of the same K steps with event timers: per kernel class, then per kernel of the LU
+    tim = tim2 = None
+    if args.full:
+        tim = krun.timed_steps(args.steps, 1)
+        tim2 = krun.timed_steps(args.steps, 2)
+        if TIME_ALL:
+            tim = tim2  # the timers were never reset: both are totals over every launch of the process
 
-    # ---- "each shard D2H-copies y(tout), y'(tout) and counters; host concatenates". Untimed: every rank
+    # ---- (--full) SURVEY 8(e): "each shard D2H-copies y(tout), y'(tout) and counters; host concatenates". Untimed: every rank
     # integrates its shard once from fresh state through the whole output schedule (a result that does not depend on how
     # the ensemble is sharded, unlike the state of a stream after K rounds; it reuses the stream's device context, so it comes
     # after everything that continues the stream), rank 0 gathers digests of every rank's block
     # and its counter sums -- a shard with wrong inputs or a wrong device shows here -- and, on request, the arrays themselves.
     # (not in the profile runs -- IDAHIP_BENCH_TIME_ALL=1 --: the kernel trace of such a run is compared with the timers' totals,
     # and the timers are off during a whole pass)
-    want_vp = not TIME_ALL
+    want_vp = args.full and not TIME_ALL
     vp = run.whole_pass(4) if want_vp else None
     vcnt = vp["counts"] if want_vp else np.zeros((6, count), dtype=np.int64)  # rows: nst, netf, ncfn, nni, nsetups, kused
     shard = {"rank": rank, "first": first, "count": count, "device": device_record(torch, local_rank),
@@ -642,7 +763,7 @@ def main():
 
 
     extras = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         passes = ([vp] if want_vp else []) + [run.whole_pass(4) for _ in range(max(1, args.passes) - (1 if want_vp else 0))]
         rates = [p["iters"] / p["seconds"] for p in passes]
         # the same passes with one host round trip per Newton iteration (idaens_set_fused_newton(0)): the before/after of the
@@ -677,72 +798,6 @@ def main():
         }
 
     if rank == 0:
-        ab = algorithmic_bytes(args.n, args.workload)
-        cls_names = ("newton_iter", "sys", "sys_jac", "jac", "lu", "vector")
-        total_ms = sum(tim[k]["ms"] for k in cls_names)
-        classes = {}
-        for k in cls_names:
-            v = tim[k]
-            ent = {"ms": round(v["ms"], 3), "calls": v["launches"], "systems": v["systems"],
-                   "share_of_device_time": round(v["ms"] / total_ms, 4) if total_ms > 0 else None}
-            if ab.get(k) and v["ms"] > 0:
-                gbs = round(ab[k] * v["systems"] / (v["ms"] * 1e-3) / 1e9, 1)
-                if args.workload == "heat1d" and k == "newton_iter":
-                    # the factors of the banded Jacobian are zero almost everywhere and the solves leave all-zero 64 x 64 blocks out
-                    # (exactly: solve_kernels.hpp): the dense byte count is not what moves, so no fraction of the peak is claimed
-                    ent["GB/s_dense_equivalent"] = gbs
-                else:
-                    ent["GB/s"] = gbs
-                    ent["frac_of_hbm_peak"] = round(gbs / HBM_PEAK_GBS, 4)
-            classes[k] = ent
-        lu_kernels = {}
-        for k in ("lu_panel", "lu_trail", "lu_finalize"):
-            v = tim2[k]
-            lu_kernels[k] = {"ms": round(v["ms"], 3), "launches": v["launches"], "matrix_launches": v["systems"]}
-        # the dominant kernel: by device time among the classes' kernels, with the LU split into its kernels
-        lu_sub_ms = sum(tim2[k]["ms"] for k in ("lu_panel", "lu_trail", "lu_finalize"))
-        scale = tim["lu"]["ms"] / lu_sub_ms if lu_sub_ms > 0 else 0.0  # level-2 pass -> level-1 pass (same work, fewer syncs)
-        cand = {k: tim[k]["ms"] for k in ("newton_iter", "sys", "sys_jac", "jac")}
-        cand.update({k: tim2[k]["ms"] * scale for k in ("lu_panel", "lu_trail", "lu_finalize")})
-        dom = max(cand, key=cand.get)
-        if dom == "lu_trail" and args.n > 8 and args.workload != "heat1d":
-            flops, nbytes, nl = trailing_work(args.n)
-            mats = tim2["lu"]["systems"]                    # matrices factorised in the level-2 pass
-            v = tim2["lu_trail"]
-            tfl = flops * mats / (v["ms"] * 1e-3) / 1e12
-            tr = profiled_traffic("lu_trail64w_kernel") if (args.workload == "linear_dense" and args.n == 512) else None
-            roof = {"bound": "valu", "kernel": "lu_trail64w_kernel<%d> (rank-64 trailing update + U12 solve of the batched getrf)" % (1024 if args.n <= 1024 else 4096),
-                    "share_of_device_time": round(cand[dom] / total_ms, 4),
-                    "achieved": round(tfl, 2), "peak": VALU_UNFUSED_TFLOPS, "unit": "TFLOP/s", "frac": round(tfl / VALU_UNFUSED_TFLOPS, 4),
-                    "peak_note": "fp64 vector ceiling of the reference's arithmetic: a multiply and a subtract per update (dense.rs:151), "
-                                 "half of the 78.6 TFLOP/s FMA peak at 2.4 GHz; the chip holds about 1.8 GHz in this kernel",
-                    "frac_of_fma_peak": round(tfl / VALU_FMA_TFLOPS, 4),
-                    "avg_launch_ms": round(v["ms"] / max(1, v["launches"]), 4), "launches": v["launches"],
-                    "algorithmic_flops_per_matrix": flops, "algorithmic_bytes_per_matrix": nbytes,
-                    "hbm_GB/s_on_algorithmic_bytes": round(nbytes * mats / (v["ms"] * 1e-3) / 1e9, 1),
-                    "traffic": None if tr is None else int(tr["hbm_bytes_per_matrix"] * mats / max(1, v["launches"])),
-                    "traffic_bytes_per_matrix": None if tr is None else tr["hbm_bytes_per_matrix"],
-                    "traffic_source": None if tr is None else "%s (rocprofv3 --pmc passes of this command at commit %s)" % (tr["source"], tr["commit"])}
-        elif args.n <= 8:
-            # the device-resident stepper: one kernel does everything; timed under the "vector" class
-            d = tim["vector"]
-            nb = 24 * args.n * args.n + 80 * args.n  # algorithmic bytes of one Newton iteration
-            ach = nb * iters_all / (elapsed_max * 1e9) if elapsed_max > 0 else 0.0
-            roof = {"bound": "hbm", "kernel": "tiny_ida_kernel (the whole of Ida::solve, one thread per system, controller on the device)",
-                    "share_of_device_time": 1.0, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 6),
-                    "traffic": None, "avg_launch_ms": round(d["ms"] / max(1, d["launches"]), 4),
-                    "note": "latency bound: 72-byte matrices, one thread per system (SURVEY 8(d): the roofline fraction is meaningless "
-                            "for this configuration; iterations per second is the figure)"}
-        else:
-            cls = "lu" if dom.startswith("lu_") else dom  # (banded workload: the getrf as a whole on its algorithmic bytes)
-            d = tim[cls]
-            ach = ab.get(cls, 0) * d["systems"] / (d["ms"] * 1e-3) / 1e9 if d["ms"] > 0 else 0.0
-            roof = {"bound": "hbm", "kernel": {"sys": "linear_sys_kernel<2, false>", "sys_jac": "linear_sys_kernel<2, true>",
-                                               "newton_iter": "newton_iter_kernel<2>", "jac": "linear_jac_kernel",
-                                               "lu": "batched getrf (all its kernels: panel, trailing update, row scatter)"}.get(cls, cls),
-                    "share_of_device_time": round((d["ms"] if cls == "lu" else cand[dom]) / total_ms, 4) if total_ms > 0 else None,
-                    "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                    "avg_launch_ms": round(d["ms"] / max(1, d["launches"]), 4)}
         name, wl = WORKLOADS[args.workload]
         out = {
             "metric": name % (args.n, args.batch),
@@ -757,10 +812,11 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": args.full,
             "config": {"workload": wl % (args.n, args.batch), "n": args.n, "batch_per_gpu": args.batch, "total_batch": args.batch * world,
                        "sharding": "independent systems, contiguous block per rank, no collective",
                        "lu_period": args.lu_period,
-                       "groups_per_gpu": args.groups, "group_sizes": gsz, "mutually_concurrent_streams": nconc, "least_pairwise_stream_share": None if share_min is None else round(share_min, 3),
+                       "groups_per_gpu": args.groups, "group_sizes": gsz, "mutually_concurrent_streams": nconc,
                        "groups": "the rank's systems run as %d ensemble(s) side by side on the one device, each on its own HIP stream and host "
                                  "thread (idaens_stream_group): every system is integrated exactly as alone; the groups only fill each other's idle "
                                  "stretches of a lock-step round%s" % (args.groups, " -- here they take turns (serial)" if run.serial else "")},
@@ -770,45 +826,22 @@ def main():
                                                  "devices": [sh["device"] for sh in shards],
                                                  "generator_processes": procs, "cores_available_to_rank0": cores,
                                                  "process_group": backend + " (barrier and two scalars only; no data-path collective)"},
-            "ensemble_result": None if not want_vp else {
-                "systems": sum(sh["count"] for sh in shards), "shards": [{k: sh[k] for k in ("rank", "first", "count", "sum_nst", "sum_nni", "sum_nsetups", "sha256_yy", "sha256_counters")} for sh in shards],
-                "sum_nst": sum(sh["sum_nst"] for sh in shards), "sum_nni": sum(sh["sum_nni"] for sh in shards),
-                "note": "SURVEY 8(e): every rank integrates its shard once from fresh state through the whole schedule (untimed) and rank 0 "
-                        "concatenates: digests of y(tout) and of the counters (nst, netf, ncfn, nni, nsetups, kused) per shard, in rank = global "
-                        "system order; --results-npz writes the concatenated arrays (tests/test_gpu_bench_ranks.py compares them with a "
-                        "single-process run)"},
-            "roofline": roof,
-            "kernel_classes_rank0": classes,
-            "lu_kernels_rank0": lu_kernels,
-            "kernel_figures_measured_on": ("the %d groups' one ensemble" % G if G == 1 else
-                                           "ONE ensemble of all %d systems of the rank, alone on the device, after the timed region (K rounds with per-class "
-                                           "event timers, K more with per-kernel timers for the LU): kernel_classes_rank0, lu_kernels_rank0, roofline, "
-                                           "lu_plus_solve and hbm_roofline's iterations per setup are the kernels' own figures at whole-batch launch sizes; "
-                                           "`value` runs the same kernels as %d groups side by side" % (count, G)),
-            "lu_plus_solve": lu_plus_solve(tim, args.n, "unfused", dense=args.workload != "heat1d") if args.n > 8 else None,
-            "cpu_baseline": cpu,
             "input_generation_s": round(t_gen, 1),
             "stream": {"stagger_rounds": run.stagger, "spin_up_rounds": max(Runner.SPIN_UP, 3 * run.stagger),
                        "note": "first starts spread over one median integration length (rounds), measured on the device on the "
                                "first %d systems before the stream starts; then the untimed spin-up, W warm-up and K timed rounds" % Runner.CALIBRATION_SYSTEMS},
         }
-        if args.workload == "linear_dense":
-            # north_star: the rate as a fraction of the HBM roofline. BASELINE.md section 3: one Newton iteration moves 24 N^2 + 80 N
-            # bytes (solve + residual), a linear-solver setup (40 N^2 + 8 N bytes: Jacobian + factor) is shared by the r iterations
-            # measured per setup in this run
-            N = args.n
-            it_bytes, ls_bytes = 24 * N * N + 80 * N, 40 * N * N + 8 * N
-            n_it = tim["newton_iter"]["systems"]
-            n_ls = tim["lu"]["systems"]
-            r = n_it / n_ls if n_ls else None
-            per_gpu = 8.0e12 / it_bytes
-            out["hbm_roofline"] = {
-                "iters_per_s_per_gpu": round(per_gpu), "frac": out["value"] / (world * per_gpu),
-                "newton_iters_per_lsetup": None if r is None else round(r, 2),
-                "iters_per_s_per_gpu_with_lsetup": None if r is None else round(8.0e12 / (it_bytes + ls_bytes / r)),
-                "frac_with_lsetup": None if r is None else out["value"] / (world * 8.0e12 / (it_bytes + ls_bytes / r)),
-                "note": "8 TB/s over the algorithmic bytes of BASELINE.md section 3; the factorisation itself is bound by the fp64 vector "
-                        "pipe at this N, not by HBM (`roofline`, `lu_plus_solve`)"}
+        if args.full:
+            out["config"]["least_pairwise_stream_share"] = None if share_min is None else round(share_min, 3)
+            out["ensemble_result"] = None if not want_vp else {
+                "systems": sum(sh["count"] for sh in shards), "shards": [{k: sh[k] for k in ("rank", "first", "count", "sum_nst", "sum_nni", "sum_nsetups", "sha256_yy", "sha256_counters")} for sh in shards],
+                "sum_nst": sum(sh["sum_nst"] for sh in shards), "sum_nni": sum(sh["sum_nni"] for sh in shards),
+                "note": "SURVEY 8(e): every rank integrates its shard once from fresh state through the whole schedule (untimed) and rank 0 "
+                        "concatenates: digests of y(tout) and of the counters (nst, netf, ncfn, nni, nsetups, kused) per shard, in rank = global "
+                        "system order; --results-npz writes the concatenated arrays (tests/test_gpu_bench_ranks.py compares them with a "
+                        "single-process run)"}
+            out.update(kernel_figures(args, world, G, count, tim, tim2, out["value"], iters_all, elapsed_max))
+            out["cpu_baseline"] = cpu
         if dump:
             out["dump_outputs"] = dump
         if extras:

@@ -130,3 +130,14 @@ def test_dump_outputs_stays_within_64_mb_with_a_fixed_sample(tmp_path):
 def test_steps_below_one_are_refused():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 2 and "--steps must be at least 1" in out.stderr
+
+
+def test_full_is_an_option_and_results_npz_needs_it(tmp_path):
+    """A plain run does only what `value` needs; the verification pass whose results --results-npz writes comes with --full, so
+    asking for the file without --full is refused before anything is generated or loaded."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout
+    npz = str(tmp_path / "results.npz")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--results-npz", npz], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "only --full runs" in out.stderr
+    assert not os.path.exists(npz)

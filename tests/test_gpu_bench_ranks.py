@@ -20,7 +20,7 @@ def test_bench_ranks_rehearsal(ranks, tmp_path):
     env = dict(os.environ, IDAHIP_BENCH_REHEARSE="1", IDAHIP_GEN_PROCS="1")
     npz = str(tmp_path / "results.npz")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--n", "64", "--batch", "64", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-extras", "--results-npz", npz], capture_output=True, text=True, env=env, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-extras", "--results-npz", npz], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == ranks and line["steps"] == 2 and line["scaling"] == "weak" and line["value"] > 0
@@ -55,3 +55,20 @@ def test_bench_ranks_rehearsal(ranks, tmp_path):
         assert sh["sha256_yy"] == hashlib.sha256(np.ascontiguousarray(ens.yy()[64 * r:64 * (r + 1)]).tobytes()).hexdigest()
     ens.close()
     ctx.close()
+
+
+def test_bench_ranks_plain_line(tmp_path):
+    """The same two-rank start without --full: the line has the headline and every rank's own figures, and none of the verification
+    pass's (which only --full runs)."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ, IDAHIP_BENCH_REHEARSE="1", IDAHIP_GEN_PROCS="1")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "64", "--batch", "64", "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["n_gpus"] == 2 and line["steps"] == 2 and line["value"] > 0 and line["full"] is False and "ensemble_result" not in line
+    pr = line["per_rank"]
+    assert len(pr["newton_iters"]) == 2 and all(v > 0 for v in pr["newton_iters"]) and sum(pr["newton_iters"]) == line["newton_iters_timed"]
+    assert len(pr["input_generation_s"]) == 2 and len(pr["devices"]) == 2 and pr["process_group"].startswith("gloo")

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/${ROUND_DIR:-r5}/rt_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export IDAHIP_GEN_PROCS=1
-timeout -k 10 900 rocprofv3 --kernel-trace -d $OUT -o rt --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 0 --no-cpu-baseline --no-extras "$@" > $OUT/bench.json 2> $OUT/err.txt
+timeout -k 10 900 rocprofv3 --kernel-trace -d $OUT -o rt --output-format csv -- python3 $ROOT/bench.py --full --steps 3 --warmup 0 --no-cpu-baseline --no-extras "$@" > $OUT/bench.json 2> $OUT/err.txt
 python3 - "$OUT" <<'P'
 import csv, sys, os
 p = None

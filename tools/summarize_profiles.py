@@ -99,7 +99,7 @@ res = {"commit": os.environ.get("GIT_COMMIT", "unknown"), "kernel_sources_sha": 
        "lu_wavepanel_kernels_together": _panels,
        "lu_hbm_bytes_per_matrix": {name: int((d["hbm_read_GB_total"] + d["hbm_write_GB_total"]) * 1e9 / max(1, lu_mats))
                                    for name, d in k.items() if name.startswith("lu_") and "hbm_read_GB_total" in d},
-       "note": "kernel stats and PMC passes are separate runs of the same command (python3 bench.py --steps 40 --warmup 0 "
+       "note": "kernel stats and PMC passes are separate runs of the same command (python3 bench.py --full --steps 40 --warmup 0 "
                "--no-cpu-baseline --no-extras under IDAHIP_BENCH_TIME_ALL=1: the per-kernel LU timers cover every launch of the process)"}
 res["lu_hbm_bytes_per_matrix"]["all LU kernels"] = sum(res["lu_hbm_bytes_per_matrix"].values())
 json.dump(res, open(out, "w"), indent=1)
