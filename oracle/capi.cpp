@@ -148,6 +148,29 @@ int oracle_newton_test(const double* y0, const double* w, double tol, int maxite
     return r;
 }
 
+// -------------------------------------------------------------------------------------------- bare problems
+// Residual::res / Jacobian::jac of one problem of make_problem, without an Ida object around it: the seam that pins the Python
+// restatements of the residuals and Jacobians (tests/dq_ref.py) on problems.hpp bit for bit.
+//   out: [n];  J: [n*n] column-major, zeroed here first as idaLsSetup does (ida_ls.rs:252-255)
+int oracle_problem_res(int kind, int n, const double* params, const double* A, const double* B, const double* c, double tt,
+                       const double* yy, const double* yp, double* out) {
+    if (kind < 0 || kind > 3 || (kind == 3 && !params)) return -1;
+    std::unique_ptr<Problem> p = make_problem(kind, n, params, A, B, c);
+    if (p->model_size() != n) return -1;
+    p->res(tt, yy, yp, out);
+    return 0;
+}
+int oracle_problem_jac(int kind, int n, const double* params, const double* A, const double* B, const double* c, double tt, double cj,
+                       const double* yy, const double* yp, const double* rr, double* J) {
+    if (kind < 0 || kind > 3 || (kind == 3 && !params)) return -1;
+    std::unique_ptr<Problem> p = make_problem(kind, n, params, A, B, c);
+    if (p->model_size() != n) return -1;
+    const size_t nn = (size_t)n * n;
+    for (size_t e = 0; e < nn; ++e) J[e] = 0.0;
+    p->jac(tt, cj, yy, yp, rr, J);
+    return 0;
+}
+
 // -------------------------------------------------------------------------------------------- Ida object
 void* oracle_ida_create(int kind, int n, const double* params, const double* A, const double* B, const double* c,
                         const double* yy0, const double* yp0, double rtol, const double* atol, int natol) {

@@ -99,6 +99,10 @@ def lib():
     L.oracle_run_ensemble.restype = C.c_double
     L.oracle_time_lu_solve.argtypes = [dp, dp, C.c_int, C.c_int, C.c_int, i32p]
     L.oracle_time_lu_solve.restype = C.c_double
+    L.oracle_problem_res.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, C.c_double, dp, dp, dp]
+    L.oracle_problem_res.restype = C.c_int
+    L.oracle_problem_jac.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, C.c_double, C.c_double, dp, dp, dp, dp]
+    L.oracle_problem_jac.restype = C.c_int
     L.oracle_hardware_concurrency.argtypes = []
     L.oracle_hardware_concurrency.restype = C.c_int
     _LIB = L
@@ -161,6 +165,26 @@ def getrs_batch(cm, piv, b, nthreads=None):
 def wrms(x, w):
     x, w = f64(x), f64(w)
     return lib().oracle_norm_wrms(_ptr(x), _ptr(w), x.size)
+
+
+def problem_res(kind, n, yy, yp, tt=0.0, params=None, A=None, B=None, c=None):
+    """Residual::res of one bare problem (oracle/problems.hpp) -> [n]. A, B: [n][n] column-major."""
+    yy, yp = f64(yy), f64(yp)
+    p_, A_, B_, c_ = (None if v is None else f64(v) for v in (params, A, B, c))
+    out = np.zeros(n)
+    assert lib().oracle_problem_res(KIND[kind], n, _ptr(p_), _ptr(A_), _ptr(B_), _ptr(c_), float(tt), _ptr(yy), _ptr(yp), _ptr(out)) == 0
+    return out
+
+
+def problem_jac(kind, n, cj, yy, yp, rr=None, tt=0.0, params=None, A=None, B=None, c=None):
+    """Jacobian::jac of one bare problem into a zeroed matrix -> [n][n] column-major (J[j, i] = J(i, j))."""
+    yy, yp = f64(yy), f64(yp)
+    rr = np.zeros(n) if rr is None else f64(rr)
+    p_, A_, B_, c_ = (None if v is None else f64(v) for v in (params, A, B, c))
+    J = np.empty((n, n))
+    assert lib().oracle_problem_jac(KIND[kind], n, _ptr(p_), _ptr(A_), _ptr(B_), _ptr(c_), float(tt), float(cj), _ptr(yy), _ptr(yp),
+                                    _ptr(rr), _ptr(J)) == 0
+    return J
 
 
 class OracleIda:

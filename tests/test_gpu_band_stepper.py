@@ -16,10 +16,12 @@ def sample(p, ids):
 
 
 def integrate_and_compare(ens, p, touts, ids):
-    """ens integrates every system of p; the systems `ids` are checked against the oracle at every output."""
+    """ens integrates every system of p; the systems `ids` are checked against the oracle at every output. A host-callback problem
+    names the oracle's problem in p["oracle_kind"] (heat1d when absent). Returns the oracle's run."""
     q = sample(p, ids)
-    ref = O.run_ensemble(q["kind"] if q["kind"] != "host_callback" else "heat1d", q["n"], q["yy0"], q["yp0"], q["rtol"], q["atol"], touts,
-                         params=q["params"], nthreads=min(len(ids), 16))
+    kind = q["kind"] if q["kind"] != "host_callback" else q.get("oracle_kind", "heat1d")
+    ref = O.run_ensemble(kind, q["n"], q["yy0"], q["yp0"], q["rtol"], q["atol"], touts, params=q.get("params"), A=q.get("A"), B=q.get("B"),
+                         c=q.get("c"), nthreads=min(len(ids), 16))
     assert (ref["status"] == 0).all()
     for i, t in enumerate(touts):
         status, tret = ens.solve(float(t))
@@ -29,6 +31,7 @@ def integrate_and_compare(ens, p, touts, ids):
     for k in CNT:
         assert np.array_equal(c[k][ids], ref["counters"][k]), k
     assert np.array_equal(c["kused"][ids], ref["kused"]) and np.array_equal(ens.real("hused")[ids], ref["hused"])
+    return ref
 
 
 def spread(B, k=8):

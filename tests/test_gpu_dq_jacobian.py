@@ -231,8 +231,21 @@ def test_host_stepper_counts_dq_evaluations(band):
     assert np.array_equal(c["nre_dq"], c["nje"] * R.dq_evals(n, band))
     assert np.array_equal(calls, c["nre"] + c["nre_dq"])
     assert (c["nre"] >= c["nni"]).all() and (c["nre"] < c["nre_dq"]).all()
+    yy = ens.yy()
     ens.close()
     ctx.close()
+    if band == (2, 1):  # the band DQ Jacobian of the heat problem equals the dense one by value (test_dq_ref.py): so does the run
+        dense = idahip.Ctx("host_callback", n, B)
+        dense.set_tolerances(p["rtol"], p["atol"])
+        dense.set_host_residual(lambda s, t, y, yp: R.heat_res(float(coef[s]), y, yp))
+        ens = idahip.Ensemble(dense, p["yy0"], p["yp0"])
+        st, _ = ens.solve(0.02)
+        assert (st == 0).all()
+        assert np.array_equal(yy, ens.yy())  # by value
+        for k in ("nst", "nje", "nsetups", "nni", "netf", "ncfn", "kused"):
+            assert np.array_equal(c[k], ens.counter(k)), k
+        ens.close()
+        dense.close()
 
 
 def test_heat_dq_setups_after_a_factorisation_that_left_the_work_matrix_zero():

@@ -58,7 +58,7 @@ def close_to_oracle(r, p, touts, rel=1e-3):
     assert (r["c"]["nre_dq"] > 0).all()
 
 
-@pytest.mark.parametrize("band,n", [(None, 257), ((1, 1), 257), (None, 2048)])
+@pytest.mark.parametrize("band,n", [(None, 257), ((1, 1), 257), ((2, 3), 257), (None, 2048)])
 def test_heat_three_paths_agree(band, n):
     from idahip import problems
     p = problems.heat1d(n=n, batch=4 if n < 1024 else 2)
