@@ -11,8 +11,8 @@
 #if !defined(IDAHIP_TIMING_BUILD) &&                                                                                   \
     (defined(IDAHIP_EXP_NOPRO) || defined(IDAHIP_EXP_NOUPD) || defined(IDAHIP_EXP_NOGATHER) || defined(IDAHIP_EXP_NODIAG) || \
      defined(IDAHIP_EXP_NOSWEEP) || defined(IDAHIP_STAMPS) || defined(IDAHIP_TRAIL_PIPE) || defined(IDAHIP_TRAIL_QUAD) ||   \
-     defined(IDAHIP_WP_RING) || defined(IDAHIP_US_PAD) || defined(IDAHIP_SYS_UNR))
-#error "IDAHIP_EXP_* / IDAHIP_STAMPS / IDAHIP_TRAIL_* / IDAHIP_WP_RING / IDAHIP_US_PAD / IDAHIP_SYS_UNR are timing-build switches: add -DIDAHIP_TIMING_BUILD (the library then reports itself as one and is not a product)"
+     defined(IDAHIP_WP_RING) || defined(IDAHIP_US_PAD) || defined(IDAHIP_SYS_UNR) || defined(IDAHIP_TRAIL_AHEAD))
+#error "IDAHIP_EXP_* / IDAHIP_STAMPS / IDAHIP_TRAIL_* (IDAHIP_TRAIL_AHEAD: 0..3) / IDAHIP_WP_RING / IDAHIP_US_PAD / IDAHIP_SYS_UNR are timing-build switches: add -DIDAHIP_TIMING_BUILD (the library then reports itself as one and is not a product)"
 #endif
 
 namespace idahip {
@@ -73,6 +73,12 @@ constexpr bool TRAIL_QUAD = true;
 constexpr int US_PAD = IDAHIP_US_PAD;
 #else
 constexpr int US_PAD = 2;
+#endif
+// lu_trail64w_kernel, solve in registers: steps by which the LDS reads of the multipliers run ahead of step kk (product: 1, then 3)
+#ifdef IDAHIP_TRAIL_AHEAD
+constexpr int trail_ahead(int kk) { return IDAHIP_TRAIL_AHEAD; }
+#else
+constexpr int trail_ahead(int kk) { return kk < 32 ? 1 : 3; }
 #endif
 // lu_wavepanel_kernel: deep multiplier prefetch rings (product: depth 2 for every slot count)
 #ifdef IDAHIP_WP_RING

@@ -924,9 +924,23 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     const int sm = slot % wpm, mi = (slot / wpm) * 8 + xcd;
     const int cbi = sm < ncb ? sm : (sm - ncb) / hs;
     const int split = sm < ncb ? 0 : 1 + (sm - ncb) % hs;
-    if (mi >= (w.cnt ? ldc(w.cnt) : nsys)) return;
-    const int b = w.idx[mi];
-    if (w.info[b] != 0) return;
+    constexpr bool BUF = MAXROWS <= 1024;  // n <= 1024: the work matrix through buffer descriptors, short start-up chain
+    constexpr bool FASTP = BUF && tb::TRAIL_QUAD && !tb::NOPRO;  // the FAST prologue below is compiled in
+    // n <= 1024: the list's length and its entry are requested together (idx has nsys entries: the clamped read is inside it
+    // whatever the count says), and so is, below, everything that hangs on the matrix's id: info, the pivot rows' numbers, L11
+    // and the live list -- two trips to memory before the gather instead of four
+    const int cntv = w.cnt ? ldc(w.cnt) : nsys;
+    int b;
+    if constexpr (BUF) {
+        b = w.idx[mi < nsys ? mi : nsys - 1];
+        asm volatile("" : "+s"(b));  // (keeps the load in front of the count's test: one wait for the two)
+        if (mi >= cntv) return;
+    } else {
+        if (mi >= cntv) return;
+        b = w.idx[mi];
+    }
+    const int infov = w.info[b];
+    if (!FASTP && infov != 0) return;  // (FASTP: tested once the loads that do not depend on it are on their way)
     // nsplit > 1: the strips of live rows of one (matrix, column block) are dealt to nsplit workgroups when the matrix has
     // shown itself banded -- at most a quarter of the column blocks of the first super-panel's update (k0 == 0, counted in
     // nzb by lu_u12_zero_kernel) had a non-zero pivot-row entry -- and the block is one of the first few, next to the panel, where a band has its
@@ -972,9 +986,35 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     __shared__ unsigned s_kmask[2];  // slow path: bit k of word R0 / 32 set = pivot row R0 + k has a non-zero entry in this column block
     __shared__ unsigned long long s_cmask[2];  // slow path: bit c set = column c of the block has a non-zero entry among pivot rows R0 .. R0 + 31
 
-    if (MAXROWS <= 1024)
-        for (int i = t; i < mrem; i += 256) s_live[i] = (unsigned short)live[i];
+    // n <= 1024: the live list, at most four entries per thread, requested at once (stored to LDS in front of the first barrier)
+    int livr[4];
+    if constexpr (BUF) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) livr[i] = live[t + 256 * i < n ? t + 256 * i : n - 1];  // (unconditional: no branch around a load)
+    }
+    auto store_live = [&]() {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s_live[t + 256 * i] = (unsigned short)livr[i];  // (all MAXROWS entries: nothing reads beyond 16 * nstrips)
+    };
+    if constexpr (BUF && !FASTP) store_live();  // (timing builds without the FAST prologue)
     const int s0 = wave + 4 * split, sstep = 4 * nsp;  // this wave's strips: s0, s0 + sstep, ...
+
+    // n <= 1024: every access to the work matrix in the strips goes through a buffer descriptor with a 32-bit byte offset per
+    // lane and no vector address arithmetic. rsA covers the matrix (multipliers: scalar column offset, per-lane row + kq
+    // columns); rsC[j] starts at column cb0 + 16 j and ends with the block, so that a lane whose column q + 16 j lies beyond
+    // the block's last column is out of its range -- it reads +0.0 and its store is dropped by the range check, as is every
+    // access of a row beyond the live list (offset OOB): no clamp, no select, and nothing is ever stored in such a lane's name.
+    constexpr unsigned OOB = 0x80000000u;  // OR-ed into an offset (all of them are below 2^23): beyond every descriptor's range
+    constexpr int RSFLAGS = 0x00020000;
+    __amdgpu_buffer_rsrc_t rsA, rsC[4];
+    if constexpr (BUF) {
+        rsA = __builtin_amdgcn_make_buffer_rsrc(A, 0, n * n * 8, RSFLAGS);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int nc = ncols - 16 * j;
+            rsC[j] = __builtin_amdgcn_make_buffer_rsrc(A + (long)(cb0 + 16 * j) * n, 0, (nc > 0 ? nc : 0) * n * 8, RSFLAGS);
+        }
+    }
 
     // ---- this lane's share of a strip: rows a + 4i, columns q + 16j
     const int a = lane & 3, q = lane >> 2;
@@ -993,24 +1033,58 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     double lreg[LPT], creg[4][4];
     int crow[4];
     bool rok[4];
+    unsigned lvo = OOB;  // n <= 1024: the same for the strip's multipliers: row lr16 of the strip, column kq of a group of four
+    const unsigned qn8 = (unsigned)(q * n) * 8u, kqn8 = (unsigned)(kq * n) * 8u;
 
     auto load_L = [&](int s, int h) {  // one k-chunk of the strip's multipliers
-        const int lr = s * 16 + lr16;
-        const int lrow = s_live[lr < mrem ? lr : mrem - 1];
+        if constexpr (BUF) {
+            if (h == 0) {  // (h == 1 follows h == 0 of the same strip. The index stays inside s_live: 16 * nstrips <= MAXROWS)
+                // the lane's number once more from the hardware (two instructions per strip): carried through the chunks in a
+                // register, lr16 was the one value the strip loop spilled and waited for
+                int ln;
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(ln));
+                const int lr = s * 16 + (ln & 15);
+                const unsigned lrow = s_live[lr];
+                lvo = (lrow * 8u + kqn8) | ((unsigned)(mrem - 1 - lr) & OOB);
+            }
 #pragma unroll
-        for (int i = 0; i < LPT; ++i) lreg[i] = A[(k0 + h * KC + 4 * i + kq) * n + lrow];
+            for (int i = 0; i < LPT; ++i) lreg[i] = buf_load_f64(rsA, lvo, (k0 + h * KC + 4 * i) * n * 8);
+        } else {
+            const int lr = s * 16 + lr16;
+            const int lrow = s_live[lr < mrem ? lr : mrem - 1];
+#pragma unroll
+            for (int i = 0; i < LPT; ++i) lreg[i] = A[(k0 + h * KC + 4 * i + kq) * n + lrow];
+        }
     };
-    auto load_C = [&](int s) {
+    // n <= 1024: byte offset of row a + 4i of strip s, in column q, from the first column of a 16-column group (OOB: no such row)
+    auto row_offsets = [&](int s, unsigned (&vo)[4]) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int ri = s * 16 + a + 4 * i;
-            rok[i] = ri < mrem;
-            crow[i] = s_live[rok[i] ? ri : mrem - 1];
+            const unsigned row = s_live[ri];  // (inside s_live, see load_L)
+            vo[i] = (row * 8u + qn8) | ((unsigned)(mrem - 1 - ri) & OOB);  // (the sign of mrem - 1 - ri: set from row mrem on)
         }
+    };
+    auto load_C = [&](int s) {
+        if constexpr (BUF) {
+            unsigned cvo[4];
+            row_offsets(s, cvo);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) creg[i][j] = A[coff[j] + crow[i]];
+                for (int i = 0; i < 4; ++i) creg[i][j] = buf_load_f64(rsC[j], cvo[i], 0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int ri = s * 16 + a + 4 * i;
+                rok[i] = ri < mrem;
+                crow[i] = s_live[rok[i] ? ri : mrem - 1];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) creg[i][j] = A[coff[j] + crow[i]];
+        }
     };
 
 
@@ -1026,23 +1100,32 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     // way and, if one was zero, nothing has been stored: the prologue below starts over with the rule applied per entry.
     __shared__ int s_fz[4];
     bool fast_ok = false;
-    if constexpr (MAXROWS <= 1024 && tb::TRAIL_QUAD) {
-      if (!NOPRO) {
+    if constexpr (FASTP) {
+      {
         const int part = lane & 3, qc = wave * 16 + (lane >> 2);
         const bool real = qc < ncols;
         double l11r[16], u[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) l11r[i] = l11[i * 256 + t];
+        int pr[16];  // the lane's pivot rows: one load per lane, no select among four scalars
+#pragma unroll
+        for (int i = 0; i < 16; ++i) pr[i] = prow[4 * i + part];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(pr[i]));  // (the loads stay in front of the test below: one trip to memory for info and these)
+        if (infov != 0) return;
         {
-            const double* __restrict__ colp = A + (long)(cb0 + (real ? qc : 0)) * n;
+            // this wave's 16 columns through a descriptor that ends with the block: a lane without a column reads +0.0 (it
+            // is kept out of the zero test and stores 0.0 below)
+            const int nc = ncols - 16 * wave;
+            const __amdgpu_buffer_rsrc_t rsG =
+                __builtin_amdgcn_make_buffer_rsrc(A + (long)(cb0 + 16 * wave) * n, 0, (nc > 0 ? nc : 0) * n * 8, RSFLAGS);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int p0 = ldc(prow + 4 * i), p1 = ldc(prow + 4 * i + 1), p2 = ldc(prow + 4 * i + 2), p3 = ldc(prow + 4 * i + 3);
-                const int pr = part == 0 ? p0 : part == 1 ? p1 : part == 2 ? p2 : p3;
-                if constexpr (tb::NOGATHER) u[i] = 1.0e-3 * (double)(1 + ((i + pr) & 7));  // timing build
-                else u[i] = colp[pr];
+                if constexpr (tb::NOGATHER) u[i] = 1.0e-3 * (double)(1 + ((i + pr[i]) & 7));  // timing build
+                else u[i] = buf_load_f64(rsG, (unsigned)pr[i] * 8u + qn8, 0);
             }
         }
+        store_live();
         double* __restrict__ Lq = &Us[0][0];  // [64][66]: row kk, entry of pivot row k at (k & 3) * 16 + (k >> 2) + 2 * ((k & 3) >> 1)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -1058,19 +1141,36 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
         }
         const double* __restrict__ Lp = Lq + part * 16 + 2 * (part >> 1);
         bool anyz = false;
+        // The multipliers of step kk do not depend on the solve: they are requested from LDS ahead of their use, one step
+        // ahead in the first half of the solve (a step has up to 16 of them per lane) and three in the second (8 or fewer),
+        // into a ring of four register sets of which the first half uses two -- at most 32 doubles in flight or in use.
+        // The fences keep the requests where they are written; the compiler counts the waits (lgkmcnt) per use.
+        double lm[4][16];
+        auto fetch = [&](auto st) {
+            constexpr int f = decltype(st)::value;
+            static_for<(f >> 2) + ((f & 3) == 3 ? 1 : 0), 16>([&](auto it) {
+                constexpr int i = decltype(it)::value;
+                lm[f & 3][i] = Lp[f * 66 + i];
+            });
+        };
         static_for<0, 64>([&](auto kt) {
             constexpr int kk = decltype(kt)::value;
             constexpr int p0 = kk & 3, i0 = kk >> 2;
+            constexpr int lo = kk == 0 ? 0 : (kk - 1 + tb::trail_ahead(kk - 1) < 63 ? kk + tb::trail_ahead(kk - 1) : 64);
+            constexpr int hi = kk + tb::trail_ahead(kk) < 63 ? kk + tb::trail_ahead(kk) : 63;
+            static_for<lo, hi + 1>(fetch);
+            __builtin_amdgcn_sched_barrier(0);
             const double ukk = dpp_mov_f64<p0 * 0x55, 0xf>(u[i0]);  // quad_perm: [p0, p0, p0, p0]
             anyz = anyz || (ukk == 0.0);
             if constexpr (p0 < 3) {  // row 4 i0 + part is below row kk for the quad's lanes part > p0 only
-                const double tn = upd(u[i0], ukk, Lp[kk * 66 + i0]);
+                const double tn = upd(u[i0], ukk, lm[kk & 3][i0]);
                 u[i0] = (part > p0) ? tn : u[i0];
             }
             static_for<i0 + 1, 16>([&](auto it) {
                 constexpr int i = decltype(it)::value;
-                u[i] = upd(u[i], ukk, Lp[kk * 66 + i]);
+                u[i] = upd(u[i], ukk, lm[kk & 3][i]);
             });
+            __builtin_amdgcn_sched_barrier(0);
         });
         TSTAMP(2);
         const unsigned long long zb = __ballot(anyz && real);
@@ -1195,8 +1295,11 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
         }
     };
 
+    // n <= 1024: this path is the rare one (an exact zero among the pivot-row entries) and its first strip is requested once, for
+    // all waves, behind the last barrier below -- a request in flight across the solves is 48 registers that wave 0's solve
+    // has to spill
     if (wave == 0 && !NOPRO) trsm32(0);
-    else if (s0 < nstrips) {  // live rows only (untouched by the U12 stores), in flight behind the solves
+    else if (!BUF && s0 < nstrips) {  // live rows only (untouched by the U12 stores), in flight behind the solves
         load_C(s0);
         load_L(s0, 0);
     }
@@ -1234,13 +1337,17 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     lds_barrier();
     if (wave == 0) {
         trsm32(KC);
-        if (s0 < nstrips) {
+        if (!BUF && s0 < nstrips) {
             load_C(s0);
             load_L(s0, 0);
         }
     }
     }
     lds_barrier();  // last workgroup barrier: from here on a wave touches only Us (read-only) and its own strip of Ls
+    if constexpr (BUF) {  // (unconditional: s0 <= 3 stays inside s_live, and rows beyond the live list are out of range)
+        load_C(s0);
+        load_L(s0, 0);
+    }
     }  // !fast_ok
     const bool slow = s_anyzero != 0;
     // The solved pivot rows are final and nothing reads them in the work matrix again: they go straight to their place in
@@ -1375,11 +1482,22 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
             load_L(s + sstep, 0);
         }
         chunk(c, KC);
+        if constexpr (BUF) {
+            // the rows' offsets once more from the live list: four registers less to carry through the two chunks, where the
+            // kernel sits at its register limit, than keeping them from load_C
+            unsigned svo[4];
+            row_offsets(s, svo);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (cok[j] && sok[i]) A[coff[j] + srow[i]] = c[i][j];
+                for (int i = 0; i < 4; ++i) buf_store_f64(rsC[j], svo[i], 0, c[i][j]);  // no such row or column: out of range, dropped
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (cok[j] && sok[i]) A[coff[j] + srow[i]] = c[i][j];
+        }
     }
     TSTAMP(7);
 #undef TSTAMP
