@@ -313,6 +313,16 @@ impl Ctx {
         let rc = unsafe { sys::idahip_set_jacobian_dq(self.raw, on as i32) };
         self.check(rc).map(|_| ())
     }
+
+    /// C IDA's `IDASetId`: `id[i]` = 1.0 for a differential component, 0.0 for an algebraic one, shared by the ensemble
+    /// (`HipEnsemble::calc_ic` with `IcOpt::YaYdpInit`); `None` clears it.
+    pub fn set_id(&mut self, id: Option<&[f64]>) -> Result<(), Error> {
+        if let Some(v) = id {
+            assert_eq!(v.len(), self.n);
+        }
+        let rc = unsafe { sys::idahip_set_id(self.raw, id.map_or(ptr::null(), |v| v.as_ptr())) };
+        self.check(rc).map(|_| ())
+    }
 }
 
 impl Drop for Ctx {
@@ -447,6 +457,15 @@ impl<D: DimName> Drop for HipDense<D> {
 /// Status of one system after a `solve` call (`IdaSolveStatus`, src/lib.rs:58-64, and the `IdaError` codes).
 pub type Status = i32;
 
+/// What `HipEnsemble::calc_ic` computes (C IDA's `icopt`).
+#[derive(Clone, Copy, Debug)]
+pub enum IcOpt {
+    /// the algebraic components of y0 and the differential components of y0' (needs `Ctx::set_id`)
+    YaYdpInit,
+    /// y0, for the y0' given
+    YInit,
+}
+
 /// Counters of `Ida` (src/ida_io.rs:11-117) that `HipEnsemble::counter` returns per system.
 #[derive(Clone, Copy, Debug)]
 pub enum Counter {
@@ -548,6 +567,22 @@ impl HipEnsemble {
             return Err(Error::Library { code: rc, message: self.last_error() });
         }
         Ok((status, tret))
+    }
+
+    /// Consistent initial conditions for every system before the first `solve` (C IDA's `IDACalcIC`; `tout1`: the first output
+    /// time): the status per system -- 0, or `IDAENS_CONV_FAIL`, `_LINESEARCH_FAIL`, `_NO_RECOVERY`, `_ILL_INPUT`, `_BAD_EWT`. A
+    /// system that failed keeps the values it was created with; `yy` / `yp` return the corrected ones.
+    pub fn calc_ic(&mut self, icopt: IcOpt, tout1: f64) -> Result<Vec<Status>, Error> {
+        let code = match icopt {
+            IcOpt::YaYdpInit => sys::IDAENS_YA_YDP_INIT,
+            IcOpt::YInit => sys::IDAENS_Y_INIT,
+        };
+        let mut status = vec![0i32; self.ctx.batch];
+        let rc = unsafe { sys::idaens_calc_ic(self.raw, code, tout1, status.as_mut_ptr()) };
+        if rc < 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(status)
     }
 
     /// Root functions g_i = y[comps[i]] - thresholds[i] (the family of examples/roberts.rs), before the first `solve`.

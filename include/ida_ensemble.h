@@ -39,7 +39,10 @@ enum {
     IDAENS_CLOSE_ROOTS = -10, /* IdaError::CloseRoots (impl_r_check.rs:199) */
     IDAENS_RTFUNC_FAIL = -12, /* a host root function returned non-zero (C IDA's IDA_RTFUNC_FAIL; the reference has the check
                                  commented out, impl_r_check.rs:83) */
+    IDAENS_LINESEARCH_FAIL = -13, /* idaens_calc_ic: the line search failed (C IDA's IDA_LINESEARCH_FAIL) */
+    IDAENS_NO_RECOVERY = -14,     /* idaens_calc_ic: a singular Jacobian at the smallest step size tried (IDA_NO_RECOVERY) */
     IDAENS_ILL_INPUT = -22,
+    IDAENS_BAD_EWT = -24, /* idaens_calc_ic: a component of the error weights is <= 0 (IDA_BAD_EWT) */
     IDAENS_BAD_K = -25,
     IDAENS_BAD_T = -26
 };
@@ -88,6 +91,24 @@ int idaens_get_roots(const idaens* e, int32_t* out /* [batch][nroots] */);
  * (impl_r_check.rs) is per-system scalar work on the host either way: roots are rare events of single systems. */
 typedef int (*idaens_root_fn)(void* user, int32_t sys, double t, const double* yy, const double* yp, int32_t nroots, double* gout);
 int idaens_set_root_fn(idaens* e, int nroots, idaens_root_fn fn, void* user);
+
+/* Consistent initial conditions for every system: C IDA's IDACalcIC (the reference has none, src/lib.rs:328-335), as DESIGN.md
+ * section 4f defines it -- no constraints, sysindex = 1, line search always on.
+ *   IDAENS_YA_YDP_INIT: given the differential components of y0 (idahip_set_id: id_i = 1), compute the algebraic components of y0
+ *                       and the differential components of y0' such that F(t0, y0, y0') = 0;
+ *   IDAENS_Y_INIT:      given y0', compute y0.
+ * tout1: the first output time; only its distance from t0 matters (it scales the step size hic of the Jacobian's cj = 1/hic).
+ * To be called before the first solve / solve_schedule / stream call of the ensemble. Refused (negative return, error text, nothing
+ * launched or changed) for an unknown icopt, for IDAENS_YA_YDP_INIT on a ctx without an id, and after the first solve call; a
+ * host callback that returns non-zero aborts the call with -7. Otherwise returns 0 and hStatus[batch] holds IDAENS_SUCCESS,
+ * IDAENS_CONV_FAIL, IDAENS_LINESEARCH_FAIL, IDAENS_NO_RECOVERY, IDAENS_BAD_EWT or IDAENS_ILL_INPUT (tout1 too close to t0) per
+ * system. A negative status here is NOT sticky: a system that failed keeps the yy0, yp0 it was created with and may be integrated,
+ * or the caller uploads other guesses with a new idaens_create. For a system with status 0 the device's phi[0], phi[1], yy, yp
+ * and ewt hold the corrected values (idaens_get_yy / _yp return them) and the snapshot that idaens_stream's restarts begin from
+ * is renewed. The work counts in nre, nsetups, nje, nni, ncfn (nre_dq on a DQ ctx) and IDAENS_C_NBACKTR; nothing else of the
+ * controller state changes -- the first solve computes its own initial step size. */
+enum { IDAENS_YA_YDP_INIT = 1, IDAENS_Y_INIT = 2 };
+int idaens_calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus /* [batch] */);
 
 /* Ida::solve(tout, &mut tret, itask) for every system (src/impl_solve.rs:69-376). hTret/hStatus: [batch].
  * max_rounds > 0 bounds the number of lock-step attempt rounds (systems still stepping report IDAENS_UNFINISHED and
@@ -144,7 +165,8 @@ enum {
     IDAENS_C_NFAIL_FIRST = 14 /* Q5: failed attempts before the first step (reset() rescales phi[1] only)                   */,
     IDAENS_C_NLI = 15 /* idaLsSolve: linear iterations (0 with a direct LSolver, src/ida_ls.rs:389-400) */,
     IDAENS_C_NCFL = 16 /* idaLsSolve: linear convergence failures (src/ida_ls.rs:413-415) */,
-    IDAENS_C_NRE_DQ = 17 /* residual evaluations of difference-quotient Jacobians (C IDA's nreDQ; idahip_set_jacobian_dq) */
+    IDAENS_C_NRE_DQ = 17 /* residual evaluations of difference-quotient Jacobians (C IDA's nreDQ; idahip_set_jacobian_dq) */,
+    IDAENS_C_NBACKTR = 18 /* line-search backtracks of idaens_calc_ic (C IDA's nbacktr) */
 };
 int idaens_get_counter(const idaens* e, int which, int64_t* out);
 enum { IDAENS_R_TN = 0, IDAENS_R_HUSED = 1, IDAENS_R_HH = 2, IDAENS_R_H0U = 3, IDAENS_R_TOLSF = 4 };

@@ -116,6 +116,11 @@ int idahip_kind(const idahip_ctx* ctx); /* the idahip_problem the ctx was create
 
 /* TolControlSS (natol == 1) / TolControlSV (natol == n), src/tol_control.rs:6-82; shared by the ensemble */
 int idahip_set_tolerances(idahip_ctx* ctx, double rtol, const double* hAtol, int natol);
+/* C IDA's IDASetId: hId[i] = 1.0 marks component i as differential, 0.0 as algebraic (any other value: -2); shared by the
+ * ensemble, as the tolerances are; NULL clears it. Read by idahip_ic_trial / idaens_calc_ic with IDAHIP_IC_YA_YDP only. */
+int idahip_set_id(idahip_ctx* ctx, const double* hId /* [n] or NULL */);
+/* 1 if an id is set (hId, when non-null, receives it), 0 if not, -1 for a null ctx */
+int idahip_id(const idahip_ctx* ctx, double* hId);
 /* per-system problem parameters, systems [first, first+count): LORENZ63 [count][3], HEAT1D [count][1] */
 int idahip_set_problem_params(idahip_ctx* ctx, int first, int count, const double* hParams, int nparam);
 /* LINEAR_DENSE data, systems [first, first+count): hA, hB [count][n*n] column-major, hC [count][n] */
@@ -246,6 +251,37 @@ int idahip_get_dky(idahip_ctx* ctx, const int32_t* hKfirst, const int32_t* hKlas
  * initial conditions were uploaded); idahip_restore_initial puts the listed systems back to it. */
 int idahip_snapshot_initial(idahip_ctx* ctx);
 int idahip_restore_initial(idahip_ctx* ctx, const int32_t* hIdx, int nsys);
+
+/* ---- Consistent initial conditions: the device side of C IDA's IDACalcIC (the reference has none) ----
+ * The Newton / line-search state machine of DESIGN.md section 4f runs per system on the host (libidaens: idaens_calc_ic); these are
+ * its batched vector steps, for any problem kind, on a dense or a band ctx, with analytic or DQ Jacobians. They run before the first
+ * step of the listed systems and keep the iterate (y0, y0') in phi[2], phi[3], delnew in phi[4] and the direction in `delta`;
+ * phi[0], phi[1] hold the guess until idahip_ic_commit. Norms come back as sqrt(sum / n) with the sum taken left to right.
+ *   begin : ewt = ewt_set(phi[0]), hEwtBad[s] != 0 if a component is <= 0; hYpnorm[s] = ||phi[1]||_wrms(ewt); iterate = (phi[0], phi[1])
+ *   reset : iterate = (phi[0], phi[1])
+ *   res   : yy, yp = the iterate; delta = savres = F(tn, yy, yp)
+ *   setup : yy, yp = the iterate; delta = savres; J = dF/dy + cj dF/dy' there, factored with the ctx's LU (hInfo / return value as
+ *           idahip_nls_lsetup); _dq: the DQ Jacobian of a DQ ctx with hh = hHh[s] and rr = savres (-2 on the wrong kind of ctx, as
+ *           idahip_nls_lsetup / idahip_nls_lsetup_dq)
+ *   solve : delta = J^-1 delta (getrs, no scaling); hFnorm[s] = ||delta||_wrms(ewt)
+ *   trial : the line search's trial point into yy, yp -- with IDAHIP_IC_YA_YDP, id_i == 1: y_i = y0_i, y'_i = y0'_i - (cj*lambda)*delta_i;
+ *           every other component, and every component with IDAHIP_IC_Y: y_i = y0_i - lambda*delta_i, y'_i = y0'_i --; savres = F
+ *           there; delnew = J^-1 savres; hFnormp[s] = ||delnew||_wrms(ewt). One launch for the built-in problems on a dense ctx, two on
+ *           a band ctx; a host-callback residual is called on the host as in idahip_nls_sys. IDAHIP_IC_YA_YDP needs idahip_set_id.
+ *   accept: iterate y = yy, with IDAHIP_IC_YA_YDP also iterate y' = yp; delta = delnew
+ *   commit: ewt = ewt_set(iterate y), hEwtBad as in begin; phi[0] = yy = iterate y, phi[1] = yp = iterate y' */
+typedef enum { IDAHIP_IC_YA_YDP = 1, IDAHIP_IC_Y = 2 } idahip_icopt;
+int idahip_ic_begin(idahip_ctx* ctx, double* hYpnorm, int32_t* hEwtBad, const int32_t* hIdx, int nsys);
+int idahip_ic_reset(idahip_ctx* ctx, const int32_t* hIdx, int nsys);
+int idahip_ic_res(idahip_ctx* ctx, const double* hTn, const double* hCj, const int32_t* hIdx, int nsys);
+int idahip_ic_setup(idahip_ctx* ctx, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys);
+int idahip_ic_setup_dq(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx,
+                       int nsys);
+int idahip_ic_solve(idahip_ctx* ctx, double* hFnorm, const int32_t* hIdx, int nsys);
+int idahip_ic_trial(idahip_ctx* ctx, int icopt, const double* hTn, const double* hCj, const double* hLambda, double* hFnormp,
+                    const int32_t* hIdx, int nsys);
+int idahip_ic_accept(idahip_ctx* ctx, int icopt, const int32_t* hIdx, int nsys);
+int idahip_ic_commit(idahip_ctx* ctx, int32_t* hEwtBad, const int32_t* hIdx, int nsys);
 
 /* ---- device-resident stepper for small systems (n <= 8, IDAHIP_ROBERTS / IDAHIP_LORENZ63) ----
  * The whole of Ida::solve (src/impl_solve.rs:69-376: first-call block, loop-top checks, Ida::step with its attempt loop,

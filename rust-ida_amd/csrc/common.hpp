@@ -50,6 +50,9 @@ struct idahip_ctx {
     double rtol = 0.0;
     double atol_s = 0.0;
     double* d_atol_v = nullptr;  // [n] or null
+    // idahip_set_id: 1.0 differential / 0.0 algebraic component, shared by the ensemble (idaens_calc_ic)
+    double* d_id = nullptr;      // [n] or null
+    std::vector<double> h_id;    // host copy (empty: no id set)
 
     // state vectors [batch][n]
     double *yy = nullptr, *yp = nullptr, *yypredict = nullptr, *yppredict = nullptr, *ewt = nullptr, *ee = nullptr,

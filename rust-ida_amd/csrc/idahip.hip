@@ -7,6 +7,7 @@
 #include "band_kernels.hpp"
 #include "dq_kernels.hpp"
 #include "vector_kernels.hpp"
+#include "ic_kernels.hpp"
 #include "tiny_ida.hpp"
 #include "round_ida.hpp"
 
@@ -236,7 +237,7 @@ int idahip_destroy(idahip_ctx* c) {
     if (!c) return 0;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
-                    c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->ic_y,
+                    c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->ic_y,
                     c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d};
     for (void* p : ptrs)
@@ -406,6 +407,29 @@ int idahip_set_tolerances(idahip_ctx* c, double rtol, const double* hAtol, int n
         IDAHIP_HIP(c, hipMemcpy(c->d_atol_v, hAtol, sizeof(double) * c->n, hipMemcpyHostToDevice));
     }
     return 0;
+}
+
+int idahip_set_id(idahip_ctx* c, const double* hId) {
+    DevGuard dev_guard__(c);
+    if (!c) return -1;
+    if (!hId) {
+        c->h_id.clear();
+        return 0;
+    }
+    for (int i = 0; i < c->n; ++i)
+        if (!(hId[i] == 0.0 || hId[i] == 1.0)) return fail(c, -2, "id[%d] = %g: 1.0 (differential) or 0.0 (algebraic)", i, hId[i]);
+    if (!c->d_id) { int rc = dalloc(c, &c->d_id, (size_t)c->n); if (rc) return rc; }
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    IDAHIP_HIP(c, hipMemcpy(c->d_id, hId, sizeof(double) * c->n, hipMemcpyHostToDevice));
+    c->h_id.assign(hId, hId + c->n);
+    return 0;
+}
+
+int idahip_id(const idahip_ctx* c, double* hId) {
+    if (!c) return -1;
+    if (c->h_id.empty()) return 0;
+    if (hId) std::memcpy(hId, c->h_id.data(), sizeof(double) * c->n);
+    return 1;
 }
 
 int idahip_set_problem_params(idahip_ctx* c, int first, int count, const double* hParams, int nparam) {
@@ -698,12 +722,14 @@ namespace {
 // residual kernels of IdaNLProblem::sys; jac_out != nullptr (linear dense, column-major work matrix only) also forms J
 // residual of a host-callback problem: device forms and packs yy, yp; host calls the user's res per listed system; device
 // scatters the residuals (launch_sys with c->kind == IDAHIP_HOST_CALLBACK)
-int callback_sys(idahip_ctx* c, const SysArgs& a, const double* hTn, const int32_t* hIdx, int nsys) {
+// (ic: the same round trip with the IC front end, idahip_ic_res / idahip_ic_trial)
+int callback_sys(idahip_ctx* c, const SysArgs& a, const double* hTn, const int32_t* hIdx, int nsys, const SysArgsIC* ic = nullptr) {
     const int n = c->n;
     if (!c->cb_res || !(c->cb_jac || c->cb_bjac || c->dq_locked))
         return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_problem has not been called");
     const size_t cnt = (size_t)nsys * 3 * n;
-    hipLaunchKernelGGL(callback_pre_kernel, dim3(nsys), dim3(256), 0, c->stream, a, c->cb_stage);
+    if (ic) hipLaunchKernelGGL(ic_callback_pre_kernel, dim3(nsys), dim3(256), 0, c->stream, *ic, c->cb_stage);
+    else hipLaunchKernelGGL(callback_pre_kernel, dim3(nsys), dim3(256), 0, c->stream, a, c->cb_stage);
     if (c->cb_host.size() < cnt) c->cb_host.resize(cnt);
     double* h = c->cb_host.data();
     IDAHIP_HIP(c, hipMemcpyAsync(h, c->cb_stage, sizeof(double) * cnt, hipMemcpyDeviceToHost, c->stream));
@@ -1462,6 +1488,304 @@ int idahip_restore_initial(idahip_ctx* c, const int32_t* hIdx, int nsys) {
         if ((rc = post_launch(c, "restore_initial"))) return rc;
     }
     return ap.finish_async();
+}
+
+// ------------------------------------------------------------------------------------------------ consistent initial conditions
+// (ic_kernels.hpp; driven by idaens_calc_ic)
+namespace {
+
+IcVecs ic_vecs(idahip_ctx* c) {
+    const size_t bn = (size_t)c->batch * c->n;
+    IcVecs v;
+    v.y0 = c->phi + 2 * bn; v.yp0 = c->phi + 3 * bn; v.delnew = c->phi + 4 * bn; v.savres = c->savres;
+    return v;
+}
+
+// the residual kernels' IC front end: lambda == nullptr: the residual at the iterate into delta and savres; else the residual at
+// the trial point into delnew and savres
+void fill_ic_args(idahip_ctx* c, SysArgsIC& a, const double* d_lambda, int icopt) {
+    const IcVecs v = ic_vecs(c);
+    a.yypredict = v.y0; a.yppredict = v.yp0; a.yy = c->yy; a.yp = c->yp; a.ee = nullptr;
+    a.delta = d_lambda ? v.delnew : c->delta;
+    a.savres = c->savres; a.n = c->n; a.reset_ee = 0;
+    a.dir = c->delta; a.lambda = d_lambda;
+    a.id = (icopt == IDAHIP_IC_YA_YDP) ? c->d_id : nullptr;
+}
+
+// delta-like vector x <- J^-1 x with the ctx's factors, d_out[s] = sum (x_i ewt_i)^2
+int launch_ic_solve(idahip_ctx* c, double* x, const int* d_idx, double* d_out, int nsys) {
+    const int n = c->n;
+    if (c->band) {
+        const int spw = band_spw(c, nsys);
+        const dim3 grid((nsys + spw - 1) / spw), blk(spw);
+        if (c->ml == 1 && c->mu == 1)
+            hipLaunchKernelGGL((ic_band_solve_kernel<1, 1>), grid, blk, 0, c->stream, (const double*)c->bab, (const long long*)c->piv, c->ml, c->mu, x,
+                               (const double*)c->ewt, n, d_idx, nsys, d_out);
+        else
+            hipLaunchKernelGGL((ic_band_solve_kernel<-1, -1>), grid, blk, 0, c->stream, (const double*)c->bab, (const long long*)c->piv, c->ml, c->mu, x,
+                               (const double*)c->ewt, n, d_idx, nsys, d_out);
+    } else if (n <= TINY_N) {
+        hipLaunchKernelGGL(ic_tiny_solve_kernel, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, (const double*)c->lu, (const long long*)c->piv, x,
+                           (const double*)c->ewt, n, d_idx, nsys, d_out);
+    } else if (n % 2 == 0) {
+        hipLaunchKernelGGL(ic_solve_kernel<2>, dim3(nsys), dim3(256), 2 * sizeof(double) * n, c->stream, (const double*)c->lu, (const int*)c->perm, x,
+                           (const double*)c->ewt, n, d_idx, d_out);
+    } else {
+        hipLaunchKernelGGL(ic_solve_kernel<1>, dim3(nsys), dim3(256), 2 * sizeof(double) * n, c->stream, (const double*)c->lu, (const int*)c->perm, x,
+                           (const double*)c->ewt, n, d_idx, d_out);
+    }
+    return post_launch(c, "ic_solve");
+}
+
+// can the residual kernel of this ctx also solve (SysArgsIC::lu)? The built-in problems on a dense ctx
+bool ic_fusable(const idahip_ctx* c) {
+    if (c->band || c->kind == IDAHIP_HOST_CALLBACK) return false;
+    return c->n > TINY_N || c->kind == IDAHIP_ROBERTS || c->kind == IDAHIP_LORENZ63;
+}
+
+// the residual at the point the front end forms; with a.lu set (ic_fusable), the solve and the norm as well
+int launch_ic_sys(idahip_ctx* c, const SysArgsIC& a, int nsys, const double* hTn, const int32_t* hIdx) {
+    const int n = c->n;
+    switch (c->kind) {
+        case IDAHIP_HOST_CALLBACK:
+            return callback_sys(c, a, hTn, hIdx, nsys, &a);
+        case IDAHIP_ROBERTS:
+            hipLaunchKernelGGL(ic_tiny_sys_kernel<IDAHIP_ROBERTS>, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, a, (const double*)nullptr, 0, nsys);
+            break;
+        case IDAHIP_LORENZ63:
+            hipLaunchKernelGGL(ic_tiny_sys_kernel<IDAHIP_LORENZ63>, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, a, (const double*)c->params, 3, nsys);
+            break;
+        case IDAHIP_LINEAR_DENSE: {
+            const size_t shm = 2 * sizeof(double) * n;
+            const double *A = c->A, *B = c->B, *C = c->C;
+            if (n % 2 == 0) hipLaunchKernelGGL((linear_sys_kernel<2, false, SysArgsIC>), dim3(nsys), dim3(256), shm, c->stream, a, A, B, C, (double*)nullptr);
+            else hipLaunchKernelGGL((linear_sys_kernel<1, false, SysArgsIC>), dim3(nsys), dim3(256), shm, c->stream, a, A, B, C, (double*)nullptr);
+            break;
+        }
+        case IDAHIP_HEAT1D: {
+            const size_t shm = (a.lu ? 2 : 1) * sizeof(double) * n;
+            if (n % 2 == 0) hipLaunchKernelGGL(ic_heat_sys_kernel<2>, dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
+            else hipLaunchKernelGGL(ic_heat_sys_kernel<1>, dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
+            break;
+        }
+    }
+    return post_launch(c, "ic_res");
+}
+
+int ic_check_opt(idahip_ctx* c, int icopt) {
+    if (icopt != IDAHIP_IC_YA_YDP && icopt != IDAHIP_IC_Y) return fail(c, -2, "unknown icopt %d", icopt);
+    if (icopt == IDAHIP_IC_YA_YDP && c->h_id.empty()) return fail(c, -2, "IDAHIP_IC_YA_YDP needs the id vector (idahip_set_id)");
+    return 0;
+}
+
+// setup at the iterate: shared by idahip_ic_setup and idahip_ic_setup_dq (hHh != nullptr)
+int ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx, int nsys) {
+    ArgPack ap;
+    int rc;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    const double* d_cj = ap.in(hCj, nsys);
+    const double* d_hh = hHh ? ap.in(hHh, nsys) : nullptr;
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+        hipLaunchKernelGGL(ic_point_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), d_idx);
+        if ((rc = post_launch(c, "ic_point"))) return rc;
+    }
+    double* work = (c->n <= TINY_N) ? c->lu : c->jw;
+    {
+        KTimer kt(c, IDAHIP_K_JAC, nsys);
+        if ((rc = launch_jac(c, work, d_idx, d_cj, nsys, hTn, hCj, hIdx, nullptr, d_hh))) return rc;
+    }
+    return factor_and_report(c, work, d_idx, hIdx, nsys, hInfo);
+}
+
+}  // namespace
+
+int idahip_ic_begin(idahip_ctx* c, double* hYpnorm, int32_t* hEwtBad, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hYpnorm || !hEwtBad) return fail(c, -2, "null argument");
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    double* d_out = ap.out<double>(nsys);
+    int* d_bad = ap.out<int>(nsys);
+    if ((rc = ap.ok())) return rc;
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+        hipLaunchKernelGGL(ic_begin_kernel, dim3(nsys), dim3(256), sizeof(double) * c->n, c->stream, vec_state(c), ic_vecs(c), d_idx, d_out, d_bad);
+        if ((rc = post_launch(c, "ic_begin"))) return rc;
+    }
+    if ((rc = ap.fetch())) return rc;
+    const double* h = ap.host_of(d_out);
+    const int* hb = ap.host_of(d_bad);
+    for (int s = 0; s < nsys; ++s) {
+        hYpnorm[s] = sqrt(h[s] / (double)c->n);
+        hEwtBad[s] = hb[s];
+    }
+    return 0;
+}
+
+int idahip_ic_reset(idahip_ctx* c, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+        hipLaunchKernelGGL(ic_reset_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), d_idx);
+        if ((rc = post_launch(c, "ic_reset"))) return rc;
+    }
+    return ap.finish_async();
+}
+
+int idahip_ic_res(idahip_ctx* c, const double* hTn, const double* hCj, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hTn || !hCj) return fail(c, -2, "null argument");
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    SysArgsIC a;
+    a.idx = ap.in(hIdx, nsys);
+    a.tn = ap.in(hTn, nsys);
+    a.cj = ap.in(hCj, nsys);
+    if ((rc = ap.upload())) return rc;
+    fill_ic_args(c, a, nullptr, IDAHIP_IC_Y);
+    {
+        KTimer kt(c, IDAHIP_K_SYS, nsys);
+        if ((rc = launch_ic_sys(c, a, nsys, hTn, hIdx))) return rc;
+    }
+    return ap.finish_async();
+}
+
+int idahip_ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hTn || !hCj || !hInfo) return fail(c, -2, "null argument");
+    if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_ic_setup_dq");
+    if (nsys == 0) return 0;
+    return ic_setup(c, hTn, hCj, nullptr, hInfo, hIdx, nsys);
+}
+
+int idahip_ic_setup_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hTn || !hCj || !hHh || !hInfo) return fail(c, -2, "null argument");
+    if (!c->jac_dq) return fail(c, -2, "idahip_ic_setup_dq on a ctx with analytic Jacobians (idahip_set_jacobian_dq)");
+    if (nsys == 0) return 0;
+    return ic_setup(c, hTn, hCj, hHh, hInfo, hIdx, nsys);
+}
+
+int idahip_ic_solve(idahip_ctx* c, double* hFnorm, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hFnorm) return fail(c, -2, "null argument");
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    double* d_out = ap.out<double>(nsys);
+    if ((rc = ap.ok())) return rc;
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
+        if ((rc = launch_ic_solve(c, c->delta, d_idx, d_out, nsys))) return rc;
+    }
+    if ((rc = ap.fetch())) return rc;
+    const double* h = ap.host_of(d_out);
+    for (int s = 0; s < nsys; ++s) hFnorm[s] = sqrt(h[s] / (double)c->n);
+    return 0;
+}
+
+int idahip_ic_trial(idahip_ctx* c, int icopt, const double* hTn, const double* hCj, const double* hLambda, double* hFnormp,
+                    const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hTn || !hCj || !hLambda || !hFnormp) return fail(c, -2, "null argument");
+    if ((rc = ic_check_opt(c, icopt))) return rc;
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    SysArgsIC a;
+    a.idx = ap.in(hIdx, nsys);
+    a.tn = ap.in(hTn, nsys);
+    a.cj = ap.in(hCj, nsys);
+    const double* d_lambda = ap.in(hLambda, nsys);
+    double* d_out = ap.out<double>(nsys);
+    if ((rc = ap.ok())) return rc;
+    if ((rc = ap.upload())) return rc;
+    fill_ic_args(c, a, d_lambda, icopt);
+    const bool fused = ic_fusable(c);
+    if (fused) {
+        a.lu = c->lu; a.perm = c->perm; a.piv = (const long long*)c->piv; a.ewt = c->ewt; a.out = d_out;
+    }
+    {
+        KTimer kt(c, IDAHIP_K_SYS, nsys);
+        if ((rc = launch_ic_sys(c, a, nsys, hTn, hIdx))) return rc;
+    }
+    if (!fused) {
+        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
+        if ((rc = launch_ic_solve(c, a.delta, a.idx, d_out, nsys))) return rc;
+    }
+    if ((rc = ap.fetch())) return rc;
+    const double* h = ap.host_of(d_out);
+    for (int s = 0; s < nsys; ++s) hFnormp[s] = sqrt(h[s] / (double)c->n);
+    return 0;
+}
+
+int idahip_ic_accept(idahip_ctx* c, int icopt, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (icopt != IDAHIP_IC_YA_YDP && icopt != IDAHIP_IC_Y) return fail(c, -2, "unknown icopt %d", icopt);
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+        hipLaunchKernelGGL(ic_accept_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), icopt == IDAHIP_IC_YA_YDP ? 1 : 0, d_idx);
+        if ((rc = post_launch(c, "ic_accept"))) return rc;
+    }
+    return ap.finish_async();
+}
+
+int idahip_ic_commit(idahip_ctx* c, int32_t* hEwtBad, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hEwtBad) return fail(c, -2, "null argument");
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    int* d_bad = ap.out<int>(nsys);
+    if ((rc = ap.ok())) return rc;
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+        hipLaunchKernelGGL(ic_commit_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), d_idx, d_bad);
+        if ((rc = post_launch(c, "ic_commit"))) return rc;
+    }
+    if ((rc = ap.fetch())) return rc;
+    const int* hb = ap.host_of(d_bad);
+    for (int s = 0; s < nsys; ++s) hEwtBad[s] = hb[s];
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- device-resident stepper (n <= 8)

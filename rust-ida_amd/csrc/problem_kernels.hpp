@@ -11,6 +11,7 @@
 //   Heat1D       <- SURVEY.md 8(d) config 4.
 #pragma once
 #include "common.hpp"
+#include "solve_kernels.hpp"
 
 namespace idahip {
 
@@ -28,7 +29,56 @@ struct SysArgs {
     int n;
     int reset_ee;
     const int* skip = nullptr;  // optional, per list position: nonzero = leave this system alone (idahip_newton_iter2)
+    static constexpr bool IC = false;
 };
+
+// The same kernels' front end for IDACalcIC (ic_kernels.hpp, idahip_ic_res / idahip_ic_trial): the point the residual is taken at
+// is the line search's trial point, formed from the iterate (y0, y0') kept in `yypredict` / `yppredict`, the Newton direction
+// `dir` and the step length lambda of the list position -- DESIGN.md section 4f:
+//     id_i == 1 (differential, IDAENS_YA_YDP_INIT):  y_i = y0_i,                  y'_i = y0'_i - (cj*lambda)*dir_i
+//     otherwise (algebraic, or IDAENS_Y_INIT):       y_i = y0_i - lambda*dir_i,   y'_i = y0'_i
+// lambda == nullptr: the iterate itself. The point goes to yy / yp, the residual to `delta` (which the caller points at the buffer
+// it solves in place) and `savres`; `ee` and reset_ee are not used.
+struct SysArgsIC : SysArgs {
+    const double* dir;     // [batch][n]
+    const double* lambda;  // [nsys] or null
+    const double* id;      // [n] shared by the ensemble, or null: no component is differential (IDAENS_Y_INIT)
+    // the trial in one launch (kernels that give a system to one workgroup or one thread): with lu set, the residual is followed by
+    // delta <- LU^-1 delta with the ctx's factors and out[s] = sum_i (delta_i ewt_i)^2, left to right
+    const double* lu = nullptr;
+    const int* perm = nullptr;        // n > 8
+    const long long* piv = nullptr;   // n <= 8
+    const double* ewt = nullptr;
+    double* out = nullptr;
+    static constexpr bool IC = true;
+};
+
+// component e = b*n + i of list position s: the point (y, y') the residual is evaluated at, stored to yy / yp
+template <class ARGS>
+__device__ __forceinline__ void sys_point(const ARGS& a, int s, long e, int i, double cj, double& y, double& yp) {
+    if constexpr (ARGS::IC) {
+        const double y0 = a.yypredict[e], yp0 = a.yppredict[e];
+        if (a.lambda) {
+            const double lam = a.lambda[s], d = a.dir[e];
+            const bool differential = a.id && a.id[i] == 1.0;
+            y = differential ? y0 : y0 - lam * d;
+            yp = differential ? yp0 - (cj * lam) * d : yp0;
+        } else {
+            y = y0;
+            yp = yp0;
+        }
+    } else {
+        double yc = a.ee[e];
+        if (a.reset_ee) {
+            yc = 0.0;
+            a.ee[e] = 0.0;
+        }
+        y = a.yypredict[e] + yc;
+        yp = a.yppredict[e] + cj * yc;
+    }
+    a.yy[e] = y;
+    a.yp[e] = yp;
+}
 
 // ------------------------------------------------------------------------------------------------ tiny problems
 __device__ __forceinline__ void roberts_res(const double* yy, const double* yp, double* r) {
@@ -55,8 +105,8 @@ __device__ __forceinline__ void lorenz_jac(const double* prm, double cj, const d
     J[2] = -y[1];         J[5] = -y[0];      J[8] = b + cj;
 }
 
-template <int KIND>
-__global__ void tiny_sys_kernel(SysArgs a, const double* __restrict__ params, int nparam, int nsys) {
+template <int KIND, class ARGS>
+__device__ __forceinline__ void tiny_sys_body(ARGS a, const double* __restrict__ params, int nparam, int nsys) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nsys) return;
     if (a.skip && a.skip[s] != 0) return;
@@ -64,23 +114,20 @@ __global__ void tiny_sys_kernel(SysArgs a, const double* __restrict__ params, in
     const long vb = (long)b * 3;
     const double cj = a.cj[s];
     double yy[3], yp[3], r[3];
-    for (int i = 0; i < 3; ++i) {
-        double yc = a.ee[vb + i];
-        if (a.reset_ee) {
-            yc = 0.0;
-            a.ee[vb + i] = 0.0;
-        }
-        yy[i] = a.yypredict[vb + i] + yc;
-        yp[i] = a.yppredict[vb + i] + cj * yc;
-        a.yy[vb + i] = yy[i];
-        a.yp[vb + i] = yp[i];
-    }
+    for (int i = 0; i < 3; ++i) sys_point(a, s, vb + i, i, cj, yy[i], yp[i]);
     if (KIND == IDAHIP_ROBERTS) roberts_res(yy, yp, r);
     else lorenz_res(params + (long)b * nparam, yy, yp, r);
     for (int i = 0; i < 3; ++i) {
         a.delta[vb + i] = r[i];
         a.savres[vb + i] = r[i];
     }
+    if constexpr (ARGS::IC) {
+        if (a.lu) a.out[s] = ic_tiny_solve(a.lu, a.piv, a.delta, a.ewt, 3, b);
+    }
+}
+template <int KIND>
+__global__ void tiny_sys_kernel(SysArgs a, const double* __restrict__ params, int nparam, int nsys) {
+    tiny_sys_body<KIND>(a, params, nparam, nsys);
 }
 
 // J <- 0; jac(tn, cj, yy, yp, res) -- into mats[b] (column-major)
@@ -101,8 +148,9 @@ __global__ void tiny_jac_kernel(double* mats, const double* __restrict__ yy, con
 // One workgroup (256 threads) per system; thread t owns rows {VEC*t + v + VEC*256*pass}; sweeps columns j ascending.
 // WITH_JAC: the sweep also writes the Newton matrix J = B + cj*A (mul, then add -- as linear_jac_kernel) to Jout, column-
 // major: when the reference's Newton::solve calls setup right after sys (call_lsetup), A and B are read once for both.
-template <int VEC, bool WITH_JAC>
-__global__ __launch_bounds__(256) void linear_sys_kernel(SysArgs a, const double* __restrict__ A, const double* __restrict__ Bm,
+// ARGS = SysArgsIC (ic_kernels.hpp): the IC front end, and with a.lu set the solve of the trial in the same launch.
+template <int VEC, bool WITH_JAC, class ARGS = SysArgs>
+__global__ __launch_bounds__(256) void linear_sys_kernel(ARGS a, const double* __restrict__ A, const double* __restrict__ Bm,
                                                          const double* __restrict__ C, double* __restrict__ Jout) {
     extern __shared__ __align__(16) double sm[];
     // columns in flight per thread: 16 x 2 matrices x 16 B = 512 B per thread, 128 KB per workgroup. (8: a lone workgroup -- the
@@ -118,15 +166,8 @@ __global__ __launch_bounds__(256) void linear_sys_kernel(SysArgs a, const double
     const double cj = a.cj[blockIdx.x];
     const int t = threadIdx.x;
     for (int i = t; i < n; i += 256) {
-        double yc = a.ee[vb + i];
-        if (a.reset_ee) {
-            yc = 0.0;
-            a.ee[vb + i] = 0.0;
-        }
-        const double y = a.yypredict[vb + i] + yc;
-        const double yp = a.yppredict[vb + i] + cj * yc;
-        a.yy[vb + i] = y;
-        a.yp[vb + i] = yp;
+        double y, yp;
+        sys_point(a, (int)blockIdx.x, vb + i, i, cj, y, yp);
         syy[i] = y;
         syp[i] = yp;
     }
@@ -199,6 +240,12 @@ __global__ __launch_bounds__(256) void linear_sys_kernel(SysArgs a, const double
             }
         }
     }
+    if constexpr (ARGS::IC) {
+        if (a.lu) {  // delnew = J^-1 F and its norm, on the residual this workgroup has just left in a.delta
+            __syncthreads();
+            ic_solve_body<VEC>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out);
+        }
+    }
 }
 
 // J = B + cj*A (mul, then add), elementwise over the listed systems
@@ -231,7 +278,8 @@ __global__ __launch_bounds__(256) void linear_jac_kernel(double* __restrict__ ma
 }
 
 // ------------------------------------------------------------------------------------------------ heat 1-D
-__global__ __launch_bounds__(256) void heat_sys_kernel(SysArgs a, const double* __restrict__ params) {
+template <int VEC, class ARGS>
+__device__ __forceinline__ void heat_sys_body(ARGS a, const double* __restrict__ params) {
     extern __shared__ __align__(16) double sm[];
     const int n = a.n;
     double* syy = sm;
@@ -241,15 +289,8 @@ __global__ __launch_bounds__(256) void heat_sys_kernel(SysArgs a, const double* 
     const double cj = a.cj[blockIdx.x];
     const double coef = params[b];
     for (int i = threadIdx.x; i < n; i += 256) {
-        double yc = a.ee[vb + i];
-        if (a.reset_ee) {
-            yc = 0.0;
-            a.ee[vb + i] = 0.0;
-        }
-        const double y = a.yypredict[vb + i] + yc;
-        const double yp = a.yppredict[vb + i] + cj * yc;
-        a.yy[vb + i] = y;
-        a.yp[vb + i] = yp;
+        double y, yp;
+        sys_point(a, (int)blockIdx.x, vb + i, i, cj, y, yp);
         syy[i] = y;
     }
     __syncthreads();
@@ -260,7 +301,14 @@ __global__ __launch_bounds__(256) void heat_sys_kernel(SysArgs a, const double* 
         a.delta[vb + i] = r;
         a.savres[vb + i] = r;
     }
+    if constexpr (ARGS::IC) {
+        if (a.lu) {  // (dynamic LDS: 2 n doubles)
+            __syncthreads();
+            ic_solve_body<VEC>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out);
+        }
+    }
 }
+__global__ __launch_bounds__(256) void heat_sys_kernel(SysArgs a, const double* __restrict__ params) { heat_sys_body<1>(a, params); }
 
 __global__ __launch_bounds__(256) void heat_jac_kernel(double* __restrict__ mats, int n, const double* __restrict__ params,
                                                        const int* __restrict__ idx, const double* __restrict__ cjs, int chunks,
@@ -307,7 +355,8 @@ __global__ __launch_bounds__(256) void heat_jac_kernel(double* __restrict__ mats
 // ------------------------------------------------------------------------------------------------ host-callback problems
 // idaNlsResidual around a user residual that lives on the host (ida_nls.rs:118-153): `pre` forms yy, yp on the device and
 // packs them for the listed systems, the host evaluates F, `post` scatters the residuals into delta and savres.
-__global__ __launch_bounds__(256) void callback_pre_kernel(SysArgs a, double* __restrict__ stage) {
+template <class ARGS>
+__device__ __forceinline__ void callback_pre_body(ARGS a, double* __restrict__ stage) {
     const int n = a.n;
     if (a.skip && a.skip[blockIdx.x] != 0) return;
     const int b = a.idx[blockIdx.x];
@@ -315,19 +364,13 @@ __global__ __launch_bounds__(256) void callback_pre_kernel(SysArgs a, double* __
     const double cj = a.cj[blockIdx.x];
     double* __restrict__ sy = stage + (long)blockIdx.x * 3 * n;
     for (int i = threadIdx.x; i < n; i += 256) {
-        double yc = a.ee[vb + i];
-        if (a.reset_ee) {
-            yc = 0.0;
-            a.ee[vb + i] = 0.0;
-        }
-        const double y = a.yypredict[vb + i] + yc;
-        const double yp = a.yppredict[vb + i] + cj * yc;
-        a.yy[vb + i] = y;
-        a.yp[vb + i] = yp;
+        double y, yp;
+        sys_point(a, (int)blockIdx.x, vb + i, i, cj, y, yp);
         sy[i] = y;
         sy[n + i] = yp;
     }
 }
+__global__ __launch_bounds__(256) void callback_pre_kernel(SysArgs a, double* __restrict__ stage) { callback_pre_body(a, stage); }
 __global__ __launch_bounds__(256) void callback_post_kernel(SysArgs a, const double* __restrict__ stage) {
     const int n = a.n;
     if (a.skip && a.skip[blockIdx.x] != 0) return;

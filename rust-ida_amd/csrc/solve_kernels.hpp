@@ -412,6 +412,48 @@ __global__ void tiny_newton_iter_kernel(const double* LU, const long long* piv, 
     out[s] = acc;
 }
 
+// ------------------------------------------------------------------------------------------------ solve + norm (IDACalcIC)
+// What idaens_calc_ic solves with (ic_kernels.hpp): getrs with the ctx's factors and the WRMS sum, without the Newton body's
+// negation, scaling and accumulation into ee.
+// x <- LU^-1 x in place (rows gathered by the composed permutation), out = sum_i (x_i ewt_i)^2 left to right. One workgroup of 256
+// per system; dynamic LDS: 2 n doubles.
+template <int VEC>
+__device__ __forceinline__ void ic_solve_body(const double* __restrict__ LU, const int* __restrict__ perm, double* x,
+                                              const double* __restrict__ ewt, int n, int b, double* __restrict__ out) {
+    extern __shared__ __align__(16) double sm[];
+    double* bs = sm;
+    double* sq = sm + n;
+    const int t = threadIdx.x;
+    const long vb = (long)b * n;
+    for (int i = t; i < n; i += 256) bs[i] = x[vb + perm[vb + i]];
+    __syncthreads();
+    wg_getrs<VEC>(LU + (long)b * n * n, n, bs);
+    for (int i = t; i < n; i += 256) {
+        const double d = bs[i];
+        x[vb + i] = d;
+        const double p = d * ewt[vb + i];
+        sq[i] = p * p;
+    }
+    __syncthreads();
+    if (t == 0) out[blockIdx.x] = seq_sum_lds(sq, n);
+}
+
+__device__ __forceinline__ double ic_tiny_solve(const double* __restrict__ LU, const long long* __restrict__ piv, double* x,
+                                                const double* __restrict__ ewt, int n, int b) {
+    const long vb = (long)b * n;
+    double v[TINY_N];
+    for (int i = 0; i < n; ++i) v[i] = x[vb + i];
+    tiny_getrs(LU + (long)b * n * n, n, piv + vb, v);
+    double acc = 0.0;
+    for (int i = 0; i < n; ++i) {
+        x[vb + i] = v[i];
+        const double p = v[i] * ewt[vb + i];
+        acc = acc + p * p;
+    }
+    return acc;
+}
+
+
 // ------------------------------------------------------------------------------------------------ idaNlsConvTest on the device
 // The first two convergence tests of a Newton solve (src/ida_nls.rs:243-262) need no pow: m = 0 is two comparisons, m = 1 has
 // rate = (delnrm / oldnrm)^(1/1) = delnrm / oldnrm exactly. sum[q] is the kernel's sequential sum of (delta_i ewt_i)^2;

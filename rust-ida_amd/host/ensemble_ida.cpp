@@ -14,6 +14,7 @@
 //   get_dky               /root/reference/src/lib.rs:424-529        (coefficients; quirk Q9: C IDA's loop bound)
 //   stop_test1/2          /root/reference/src/impl_stop_test.rs:36-211 (no tstop: the reference has no setter)
 //   r_check1/2/3, root_finding  /root/reference/src/impl_r_check.rs:32-576 (scalar bracketing here, y(t) interpolated on the device)
+//   calc_ic               C IDA's IDACalcIC as DESIGN.md section 4f states it (the reference has none, src/lib.rs:328-335)
 // Vectors live on the device; this file talks to it only through include/ida_hip.h. The oracle is NOT used here.
 //
 // Lock-step execution: one "round" is one step attempt (set_coeffs -> predict -> Newton -> error test -> accept or
@@ -55,6 +56,7 @@ struct Sys : SysCore {
     // --- root finding (src/lib.rs:225-244, src/impl_r_check.rs); the vectors have nrtfn entries when roots are enabled
     std::vector<double> glo, ghi, grout, iroots;
     std::vector<uint8_t> gactive;
+    long nbacktr = 0;  // idaens_calc_ic: line-search backtracks (host-only: SysCore's size is part of the device steppers' ABI)
 };
 
 }  // namespace
@@ -75,6 +77,7 @@ struct idaens {
     double t0 = 0.0;                // every system starts at tn = t0 (Sys default)
     int64_t retired_iters = 0, passes = 0;  // idaens_stream: Newton iterations / integrations of systems already restarted
     bool have_ic = false, streaming = false;
+    bool started = false;  // a solve / solve_schedule / stream call has been made: idaens_calc_ic is refused from then on
     bool pow_mismatch = false; // glibc_pow.hpp != this host's std::pow (checked at create): the device steppers stay off
     bool device_ctl = true;    // small device problems: the whole of Ida::solve in one launch (idahip_tiny_solve), no lock-step rounds
     bool fused_newton = true;  // first two Newton iterations and their convergence tests in one device call (idahip_newton_iter2)
@@ -1047,6 +1050,7 @@ int solve_core_device(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, 
 }
 
 int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long max_rounds) {
+    e->started = true;
     if (const int mode = device_ctl_applies(e, C)) return solve_core_device(e, C, hTret, hStatus, max_rounds, mode);
     const double eps = std::numeric_limits<double>::epsilon();
     std::vector<Sys>& S = e->sys;
@@ -1298,6 +1302,271 @@ int idaens_solve_schedule(idaens* e, const double* touts, int ntout, double* hTr
     return solve_core(e, C, hTret, hStatus, max_rounds);
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------- consistent initial conditions (IDACalcIC)
+namespace {
+
+namespace ic {
+constexpr double EPS_NEWT = 0.01 * 0.33;
+constexpr int MAXNH = 5, MAXNJ = 4, MAXNIT = 10, MAXBACKS = 100;
+constexpr double ALPHALS = 1e-4, ICRATEMAX = 0.9;
+enum Ret { OK = 0, FAIL_RECOV, LINESRCH, CONV, SLOW };
+enum Stage { ST_RES = 0, ST_SETUP, ST_SOLVE, ST_TRIAL, ST_DONE };
+
+// the scalar state of one system's IDACalcIC: idaNlsIC / idaNewtonIC / idaLineSrch as a resumable machine
+struct State {
+    int stage = ST_DONE, status = 0;
+    double hic = 0.0, cj = 0.0;
+    int nwt = 1, nh = 1, nj = 1, mxnh = 1;
+    double fnorm = 0.0, fnorm0 = 0.0, oldfnrm = 0.0, rate = 0.0;
+    int m = 0;
+    double f1norm = 0.0, slpi = 0.0, minlam = 0.0, lambda = 1.0;
+    int nbacks = 0;
+};
+}  // namespace ic
+
+int calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus) {
+    using namespace ic;
+    std::vector<Sys>& S = e->sys;
+    const int batch = e->batch;
+    const double eps = std::numeric_limits<double>::epsilon();
+    const double steptol = std::pow(eps, 2.0 / 3.0);
+    const bool dq = idahip_jacobian_dq(e->ctx) > 0;
+    const long dq_evals = dq ? (idahip_band(e->ctx, nullptr, nullptr) > 0 ? dq_band_evals(e) : (long)e->n) : 0;
+    std::vector<State> T(batch);
+    std::vector<int32_t> L, acc, com, rst;
+    std::vector<double> tn, cj, hh, lam, nrm;
+    std::vector<int32_t> info;
+
+    // ---- setup (steps 1-8). The distance test is made first, on the host: a call that can do nothing launches nothing
+    for (int b = 0; b < batch; ++b) {
+        const double t0 = S[b].tn;
+        const double tdist = std::fabs(tout1 - t0);
+        // tdist == 0.0 is named on its own, as in the stepper's first call: with t0 == tout1 == 0 the bound is 0 too, and 0 < 0 is false
+        if (tdist == 0.0 || tdist < 2.0 * eps * (std::fabs(t0) + std::fabs(tout1))) T[b].status = IDAENS_ILL_INPUT;
+        else L.push_back(b);
+    }
+    if (!L.empty()) {
+        nrm.assign(L.size(), 0.0);
+        info.assign(L.size(), 0);
+        ENS_CALL(e, idahip_ic_begin(e->ctx, nrm.data(), info.data(), L.data(), (int)L.size()));
+        for (size_t q = 0; q < L.size(); ++q) {
+            const int b = L[q];
+            State& t = T[b];
+            if (info[q] != 0) {
+                t.status = IDAENS_BAD_EWT;
+                continue;
+            }
+            const double t0 = S[b].tn;
+            t.hic = 0.001 * std::fabs(tout1 - t0);
+            if (nrm[q] > 0.5 / t.hic) t.hic = 0.5 / nrm[q];
+            if (tout1 < t0) t.hic = -t.hic;
+            if (icopt == IDAENS_YA_YDP_INIT) {
+                t.cj = 1.0 / t.hic;
+                t.mxnh = MAXNH;
+            } else {
+                t.cj = 0.0;
+                t.mxnh = 1;
+            }
+            t.stage = ST_RES;
+        }
+    }
+
+    auto gather = [&](int stage) {
+        L.clear(); tn.clear(); cj.clear();
+        for (int b = 0; b < batch; ++b)
+            if (T[b].stage == stage) {
+                L.push_back(b);
+                tn.push_back(S[b].tn);
+                cj.push_back(T[b].cj);
+            }
+        return !L.empty();
+    };
+    // idaLineSrch's first lines, at the start of every Newton iteration
+    auto begin_linesearch = [&](int b) {
+        State& t = T[b];
+        S[b].niters += 1;
+        t.f1norm = t.fnorm * t.fnorm * 0.5;
+        t.slpi = -2.0 * t.f1norm;
+        t.minlam = steptol / t.fnorm;
+        t.lambda = 1.0;
+        t.nbacks = 0;
+        t.stage = ST_TRIAL;
+    };
+    // idaNlsIC returned `ret` for this step size: the outer loops of IDACalcIC
+    auto nls_returned = [&](int b, int ret) {
+        State& t = T[b];
+        if (ret == OK) {
+            com.push_back(b);  // ewt, phi; the pass counter moves on once the weights are known to be good
+            t.stage = ST_DONE;
+            return;
+        }
+        S[b].ncfn += 1;
+        if (t.nh == t.mxnh) {
+            t.status = ret == FAIL_RECOV ? IDAENS_NO_RECOVERY : ret == LINESRCH ? IDAENS_LINESEARCH_FAIL : IDAENS_CONV_FAIL;
+            t.stage = ST_DONE;
+            return;
+        }
+        if (ret != SLOW) rst.push_back(b);
+        t.hic *= 0.1;
+        t.cj = 1.0 / t.hic;
+        t.nh += 1;
+        t.stage = ST_RES;
+    };
+    // idaNewtonIC returned `ret`: idaNlsIC's loop over Jacobian evaluations
+    auto newton_returned = [&](int b, int ret) {
+        State& t = T[b];
+        if (ret == SLOW && t.nj < MAXNJ) {
+            t.nj += 1;
+            t.stage = ST_SETUP;  // (delta = savres: idahip_ic_setup)
+            return;
+        }
+        nls_returned(b, ret);
+    };
+    // the Newton loop was left with `ret` (a failed line search, or maxnit iterations)
+    auto newton_left = [&](int b, int ret) {
+        State& t = T[b];
+        if (t.rate <= ICRATEMAX) return newton_returned(b, ret);
+        if (t.fnorm < 0.1 * t.fnorm0) return newton_returned(b, SLOW);
+        return newton_returned(b, ret);
+    };
+
+    // ---- lock-step rounds: every system sits in one stage; a round issues one batched call per non-empty stage
+    for (;;) {
+        bool any = false;
+        for (int b = 0; b < batch; ++b) any = any || T[b].stage != ST_DONE;
+        if (!any) break;
+        acc.clear(); com.clear(); rst.clear();
+        if (gather(ST_RES)) {  // delta = savres = F(t0, yy0, yp0)
+            ENS_CALL(e, idahip_ic_res(e->ctx, tn.data(), cj.data(), L.data(), (int)L.size()));
+            for (int b : L) {
+                S[b].nre += 1;
+                T[b].nj = 1;
+                T[b].stage = ST_SETUP;
+            }
+        }
+        if (gather(ST_SETUP)) {  // J = dF/dy + cj dF/dy' at the iterate, factored
+            info.assign(L.size(), 0);
+            if (dq) {
+                hh.clear();
+                for (int b : L) hh.push_back(T[b].hic);
+                ENS_CALL(e, idahip_ic_setup_dq(e->ctx, tn.data(), cj.data(), hh.data(), info.data(), L.data(), (int)L.size()));
+            } else {
+                ENS_CALL(e, idahip_ic_setup(e->ctx, tn.data(), cj.data(), info.data(), L.data(), (int)L.size()));
+            }
+            for (size_t q = 0; q < L.size(); ++q) {
+                const int b = L[q];
+                S[b].nsetups += 1;
+                S[b].nje += 1;
+                S[b].nre_dq += dq_evals;
+                if (info[q] != 0) nls_returned(b, FAIL_RECOV);
+                else T[b].stage = ST_SOLVE;
+            }
+        }
+        if (gather(ST_SOLVE)) {  // delta = J^-1 delta; fnorm
+            nrm.assign(L.size(), 0.0);
+            ENS_CALL(e, idahip_ic_solve(e->ctx, nrm.data(), L.data(), (int)L.size()));
+            for (size_t q = 0; q < L.size(); ++q) {
+                const int b = L[q];
+                State& t = T[b];
+                t.fnorm = nrm[q];
+                if (t.fnorm <= EPS_NEWT) {
+                    newton_returned(b, OK);
+                    continue;
+                }
+                t.fnorm0 = t.oldfnrm = t.fnorm;
+                t.rate = 0.0;
+                t.m = 0;
+                begin_linesearch(b);
+            }
+        }
+        if (gather(ST_TRIAL)) {  // savres = F(trial point); delnew = J^-1 savres; fnormp
+            lam.clear();
+            for (int b : L) lam.push_back(T[b].lambda);
+            nrm.assign(L.size(), 0.0);
+            ENS_CALL(e, idahip_ic_trial(e->ctx, icopt, tn.data(), cj.data(), lam.data(), nrm.data(), L.data(), (int)L.size()));
+            for (size_t q = 0; q < L.size(); ++q) {
+                const int b = L[q];
+                State& t = T[b];
+                const double fnormp = nrm[q];
+                S[b].nre += 1;
+                if (fnormp * fnormp * 0.5 <= t.f1norm + ALPHALS * t.slpi * t.lambda) {
+                    acc.push_back(b);  // yy0 (yp0) = the trial point; delta = delnew
+                    t.fnorm = fnormp;
+                    t.rate = t.fnorm / t.oldfnrm;
+                    if (t.fnorm <= EPS_NEWT) {
+                        newton_returned(b, OK);
+                        continue;
+                    }
+                    t.m += 1;
+                    if (t.m >= MAXNIT) {
+                        newton_left(b, CONV);
+                        continue;
+                    }
+                    t.oldfnrm = t.fnorm;
+                    begin_linesearch(b);
+                    continue;
+                }
+                if (t.lambda < t.minlam) {
+                    newton_left(b, LINESRCH);
+                    continue;
+                }
+                t.lambda /= 2.0;
+                S[b].nbacktr += 1;
+                t.nbacks += 1;
+                if (t.nbacks == MAXBACKS) newton_left(b, LINESRCH);
+            }
+        }
+        if (!acc.empty()) ENS_CALL(e, idahip_ic_accept(e->ctx, icopt, acc.data(), (int)acc.size()));
+        if (!rst.empty()) ENS_CALL(e, idahip_ic_reset(e->ctx, rst.data(), (int)rst.size()));
+        if (!com.empty()) {  // a pass has converged: ewt = ewt_set(yy0); phi[0] = yy0; phi[1] = yp0; then the second pass
+            info.assign(com.size(), 0);
+            ENS_CALL(e, idahip_ic_commit(e->ctx, info.data(), com.data(), (int)com.size()));
+            for (size_t q = 0; q < com.size(); ++q) {
+                State& t = T[com[q]];
+                if (info[q] != 0) {
+                    t.status = IDAENS_BAD_EWT;
+                } else if (t.nwt < 2) {
+                    t.nwt += 1;
+                    t.nh = 1;
+                    t.stage = ST_RES;
+                }
+            }
+        }
+    }
+
+    // ---- a failed system keeps what it was created with; the restarts of idaens_stream begin from the corrected values
+    L.clear();
+    bool launched = false;
+    for (int b = 0; b < batch; ++b) {
+        hStatus[b] = T[b].status;
+        if (T[b].status != 0 && T[b].status != IDAENS_ILL_INPUT) L.push_back(b);
+        launched = launched || T[b].status != IDAENS_ILL_INPUT;
+    }
+    if (!L.empty()) ENS_CALL(e, idahip_restore_initial(e->ctx, L.data(), (int)L.size()));
+    if (launched) {
+        ENS_CALL(e, idahip_snapshot_initial(e->ctx));
+        const std::vector<double> zero((size_t)batch * e->n, 0.0);  // phi[2..4] held the iterate and delnew
+        for (int j = 2; j <= 4; ++j) ENS_CALL(e, idahip_upload(e->ctx, (idahip_field)(IDAHIP_F_PHI0 + j), 0, batch, zero.data()));
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int idaens_calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus) {
+    if (!e || !hStatus) return -1;
+    if (icopt != IDAENS_YA_YDP_INIT && icopt != IDAENS_Y_INIT) return efail(e, -2, "idaens_calc_ic: unknown icopt %d", icopt);
+    if (icopt == IDAENS_YA_YDP_INIT && idahip_id(e->ctx, nullptr) != 1)
+        return efail(e, -2, "idaens_calc_ic: IDAENS_YA_YDP_INIT needs the id vector (idahip_set_id)");
+    if (e->started) return efail(e, -2, "idaens_calc_ic: only before the first solve, solve_schedule or stream call");
+    if (!e->have_ic) return efail(e, -2, "no snapshot of the initial conditions (idaens_create failed to take it)");
+    return calc_ic(e, icopt, tout1, hStatus);
+}
+
+extern "C" {
+
 // ---- several ensembles side by side on one device (include/ida_ensemble.h): one host thread per ensemble, each on its own
 // context and HIP stream. The ensembles share nothing; what they gain is the device's own scheduling -- while one group's
 // round is in a part that leaves most of the chip idle (the serial chain of the panel kernels, the later Newton passes and
@@ -1424,6 +1693,7 @@ int idaens_get_counter(const idaens* e, int which, int64_t* out) {
             case IDAENS_C_NLI: v = s.nli; break;
             case IDAENS_C_NCFL: v = s.ncfl; break;
             case IDAENS_C_NRE_DQ: v = s.nre_dq; break;
+            case IDAENS_C_NBACKTR: v = s.nbacktr; break;
             default: return -2;
         }
         out[b] = v;

@@ -42,12 +42,14 @@ HIP_SYMBOLS = [
     "idahip_restore_initial", "idahip_ls_type", "idahip_ls_num_iters", "idahip_ls_res_norm", "idahip_timing_build", "idahip_concurrent_streams", "idahip_release_streams", "idahip_stream_pair_share", "idahip_set_lu_superpanel", "idahip_lu_superpanel", "idahip_set_lu_period", "idahip_lu_period",
     "idahip_create_band", "idahip_band", "idahip_set_host_band_problem", "idahip_download_lu_band", "idahip_ls_setup_band", "idahip_ls_solve_band",
     "idahip_set_jacobian_dq", "idahip_jacobian_dq", "idahip_set_host_residual", "idahip_jac_dq", "idahip_nls_lsetup_dq",
+    "idahip_set_id", "idahip_id", "idahip_ic_begin", "idahip_ic_reset", "idahip_ic_res", "idahip_ic_setup", "idahip_ic_setup_dq",
+    "idahip_ic_solve", "idahip_ic_trial", "idahip_ic_accept", "idahip_ic_commit",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
     "idaens_get_roots", "idaens_solve", "idaens_solve_schedule", "idaens_stream", "idaens_stream_group", "idaens_solve_schedule_group",
     "idaens_get_counter", "idaens_get_real", "idaens_get_yy", "idaens_get_yp", "idaens_get_dky", "idaens_total_newton_iters",
-    "idaens_total_rounds", "idaens_trace_system", "idaens_trace_len", "idaens_trace_get",
+    "idaens_total_rounds", "idaens_trace_system", "idaens_trace_len", "idaens_trace_get", "idaens_calc_ic",
 ]
 
 _libs = None
@@ -142,6 +144,17 @@ def load():
     H.idahip_set_host_residual.argtypes = [vp, RES_FN, vp]
     H.idahip_jac_dq.argtypes = [vp, dp, dp, dp, dp, i32p, ci]
     H.idahip_nls_lsetup_dq.argtypes = [vp, dp, dp, dp, i32p, i32p, ci]
+    H.idahip_set_id.argtypes = [vp, dp]
+    H.idahip_id.argtypes = [vp, dp]
+    H.idahip_ic_begin.argtypes = [vp, dp, i32p, i32p, ci]
+    H.idahip_ic_reset.argtypes = [vp, i32p, ci]
+    H.idahip_ic_res.argtypes = [vp, dp, dp, i32p, ci]
+    H.idahip_ic_setup.argtypes = [vp, dp, dp, i32p, i32p, ci]
+    H.idahip_ic_setup_dq.argtypes = [vp, dp, dp, dp, i32p, i32p, ci]
+    H.idahip_ic_solve.argtypes = [vp, dp, i32p, ci]
+    H.idahip_ic_trial.argtypes = [vp, ci, dp, dp, dp, dp, i32p, ci]
+    H.idahip_ic_accept.argtypes = [vp, ci, i32p, ci]
+    H.idahip_ic_commit.argtypes = [vp, i32p, i32p, ci]
     H.idahip_timing_enable.argtypes = [vp, ci]
     H.idahip_timing_get.argtypes = [vp, ci, dp, i64p, i64p]
     H.idahip_timing_reset.argtypes = [vp]
@@ -162,6 +175,7 @@ def load():
     E.idaens_solve.argtypes = [vp, cd, ci, dp, i32p, C.c_long]
     E.idaens_solve_schedule.argtypes = [vp, dp, ci, dp, i32p, i32p, dp, dp, C.c_long]
     E.idaens_stream.argtypes = [vp, dp, ci, C.c_long, C.c_long, i64p]
+    E.idaens_calc_ic.argtypes = [vp, ci, cd, i32p]
     E.idaens_get_counter.argtypes = [vp, ci, i64p]
     E.idaens_get_real.argtypes = [vp, ci, dp]
     E.idaens_get_yy.argtypes = [vp, dp]
@@ -254,6 +268,17 @@ class Ctx:
     def set_tolerances(self, rtol, atol):
         a = _f64(np.atleast_1d(atol))
         self._chk(self.H.idahip_set_tolerances(self.h, float(rtol), _p(a), a.size), "set_tolerances")
+
+    def set_id(self, id):
+        """C IDA's IDASetId: id[i] = 1.0 for a differential component, 0.0 for an algebraic one, shared by the ensemble
+        (Ensemble.calc_ic with YA_YDP_INIT). None clears it; any other value is refused."""
+        a = None if id is None else _f64(id).reshape(self.n)
+        self._chk(self.H.idahip_set_id(self.h, _p(a)), "set_id")
+
+    def id(self):
+        """The id vector [n], or None if none is set."""
+        out = np.zeros(self.n)
+        return out if self._chk(self.H.idahip_id(self.h, _p(out)), "id") == 1 else None
 
     def set_problem_params(self, params, first=0):
         p = _f64(params).reshape(-1, _f64(params).shape[-1] if np.ndim(params) > 1 else 1)
@@ -636,7 +661,8 @@ def band_expand_factors(ab, piv, n, ml, mu):
 
 COUNTERS = {"nst": 0, "nre": 1, "nje": 2, "nsetups": 3, "nni": 4, "netf": 5, "ncfn": 6, "n_attempts": 7, "nls_nconvfails": 8,
             "kused": 9, "kk": 10, "nge": 11, "nlufail": 12, "nconv_jcur": 13, "nfail_first": 14, "nli": 15, "ncfl": 16,
-            "nre_dq": 17}
+            "nre_dq": 17, "nbacktr": 18}
+YA_YDP_INIT, Y_INIT = 1, 2  # Ensemble.calc_ic's icopt (C IDA's IDA_YA_YDP_INIT, IDA_Y_INIT)
 REALS = {"tn": 0, "hused": 1, "hh": 2, "h0u": 3, "tolsf": 4}
 
 
@@ -719,6 +745,17 @@ class Ensemble:
     def set_max_ord(self, maxord):
         if self.E.idaens_set_max_ord(self.h, int(maxord)) != 0:
             raise IdaHipError("set_max_ord(%d) rejected" % maxord)
+
+    def calc_ic(self, icopt, tout1):
+        """C IDA's IDACalcIC for every system, before the first solve: YA_YDP_INIT corrects the algebraic components of y0 and
+        the differential components of y0' (Ctx.set_id says which is which), Y_INIT corrects y0 for the given y0'.
+        -> status [batch]: 0, or CONV_FAIL -4, LINESEARCH_FAIL -13, NO_RECOVERY -14, ILL_INPUT -22, BAD_EWT -24 per system; a
+        system that failed keeps the values it was created with. yy() / yp() return the corrected values."""
+        status = np.zeros(self.ctx.batch, dtype=np.int32)
+        rc = self.E.idaens_calc_ic(self.h, int(icopt), float(tout1), _p(status, i32p))
+        if rc < 0:
+            self.ctx.fail("idaens_calc_ic failed (%d): %s" % (rc, (self.E.idaens_last_error(self.h) or b"").decode()))
+        return status
 
     def solve(self, tout, itask=0, max_rounds=0):
         tret = np.zeros(self.ctx.batch)

@@ -43,7 +43,8 @@ def _linear_system(n, b):
     A[np.arange(nd), np.arange(nd)] += 1.0
     Bm = -((0.5 / np.sqrt(n)) * G)
     Bm[np.arange(n), np.arange(n)] -= (1.0 + s)
-    # consistent initial conditions (the reference has no IDACalcIC: src/lib.rs:328-335)
+    # consistent initial conditions in closed form, so that oracle and GPU path start from identical inputs (the reference has no
+    # IDACalcIC, src/lib.rs:328-335; a user without a closed form has Ensemble.calc_ic)
     y0 = np.zeros(n)
     yp0 = np.zeros(n)
     if nd < n:
