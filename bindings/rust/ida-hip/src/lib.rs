@@ -323,6 +323,17 @@ impl Ctx {
         let rc = unsafe { sys::idahip_set_id(self.raw, id.map_or(ptr::null(), |v| v.as_ptr())) };
         self.check(rc).map(|_| ())
     }
+
+    /// C IDA's `IDASetConstraints`: `c[i]` = 0.0 none, 1.0: y_i >= 0, -1.0: y_i <= 0, 2.0: y_i > 0,
+    /// -2.0: y_i < 0, shared by the ensemble and read by every solve call at its start; `None` clears them. A system that cannot
+    /// meet them ends with `IDAENS_CONSTR_FAIL`; one whose y0 violates them does not start (`IDAENS_ILL_INPUT`).
+    pub fn set_constraints(&mut self, c: Option<&[f64]>) -> Result<(), Error> {
+        if let Some(v) = c {
+            assert_eq!(v.len(), self.n);
+        }
+        let rc = unsafe { sys::idahip_set_constraints(self.raw, c.map_or(ptr::null(), |v| v.as_ptr())) };
+        self.check(rc).map(|_| ())
+    }
 }
 
 impl Drop for Ctx {

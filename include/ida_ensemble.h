@@ -37,6 +37,8 @@ enum {
     IDAENS_CONV_FAIL = -4,
     IDAENS_LSETUP_FAIL = -6,
     IDAENS_CLOSE_ROOTS = -10, /* IdaError::CloseRoots (impl_r_check.rs:199) */
+    IDAENS_CONSTR_FAIL = -11, /* the constraints (idahip_set_constraints) could not be met: maxncf failed attempts of one step, the
+                                 last of them a constraint failure (C IDA's IDA_CONSTR_FAIL; the reference has no constraints) */
     IDAENS_RTFUNC_FAIL = -12, /* a host root function returned non-zero (C IDA's IDA_RTFUNC_FAIL; the reference has the check
                                  commented out, impl_r_check.rs:83) */
     IDAENS_LINESEARCH_FAIL = -13, /* idaens_calc_ic: the line search failed (C IDA's IDA_LINESEARCH_FAIL) */
@@ -91,6 +93,23 @@ int idaens_get_roots(const idaens* e, int32_t* out /* [batch][nroots] */);
  * (impl_r_check.rs) is per-system scalar work on the host either way: roots are rare events of single systems. */
 typedef int (*idaens_root_fn)(void* user, int32_t sys, double t, const double* yy, const double* yp, int32_t nroots, double* gout);
 int idaens_set_root_fn(idaens* e, int nroots, idaens_root_fn fn, void* user);
+
+/* Inequality constraints on the solution: C IDA's IDASetConstraints (the reference has none), as DESIGN.md section 4g defines them.
+ * They belong to the ctx -- idahip_set_constraints(ctx, c) with c_i = 0 (none), 1 (y_i >= 0), -1 (y_i <= 0), 2 (y_i > 0), -2 (y_i < 0),
+ * shared by the ensemble -- and every idaens_solve / _solve_schedule / _stream call reads at its start whether the ctx has them, so
+ * they may be set, changed or cleared between calls. With constraints set:
+ *   - a system whose y0 violates them does not start: IDAENS_ILL_INPUT with tret = t0, exactly as for a tout too close to t0;
+ *   - after every successful Newton solve the new y is checked; a small violation (weighted norm of the correction <= eps_newt) is
+ *     taken out of the step's correction before the error test, a larger one fails the attempt like a convergence failure, with
+ *     the step size reduced by rr = max(0.9 min_i phi[0]_i / (phi[0]_i - y_i), 0.1) instead of 0.25. Such failures count in ncfn
+ *     and towards maxncf together with convergence and setup failures; when the last allowed one is a constraint failure the system
+ *     ends with IDAENS_CONSTR_FAIL, which is fatal and sticky like IDAENS_CONV_FAIL;
+ *   - every problem kind (host callbacks included), dense and band contexts, both tasks, root finding, schedules and streams work;
+ *     Roberts and Lorenz63 keep their one-thread-per-system device stepper; for n > 8 the host stepper runs
+ *     (idaens_device_controller_active reports 0): the device lock-step rounds have no constraint check.
+ * Refused (negative return with a text, nothing launched): any solve call on a ctx with constraints AND difference-quotient
+ * Jacobians (C IDA flips the increments' signs there), and idaens_calc_ic on a ctx with constraints (C IDA's line search has a
+ * constraint branch of its own). */
 
 /* Consistent initial conditions for every system: C IDA's IDACalcIC (the reference has none, src/lib.rs:328-335), as DESIGN.md
  * section 4f defines it -- no constraints, sysindex = 1, line search always on.

@@ -121,6 +121,16 @@ int idahip_set_tolerances(idahip_ctx* ctx, double rtol, const double* hAtol, int
 int idahip_set_id(idahip_ctx* ctx, const double* hId /* [n] or NULL */);
 /* 1 if an id is set (hId, when non-null, receives it), 0 if not, -1 for a null ctx */
 int idahip_id(const idahip_ctx* ctx, double* hId);
+/* C IDA's IDASetConstraints (the reference has none; DESIGN.md section 4g is the definition): hC[i] = 0.0 no constraint on component
+ * i, 1.0: y_i >= 0, -1.0: y_i <= 0, 2.0: y_i > 0, -2.0: y_i < 0; any other value: -2. Shared by the ensemble, as the tolerances are;
+ * NULL clears it; an all-zero vector counts as set (the check runs and always passes). Read by idahip_post_newton_constr,
+ * idahip_constr_check, the one-thread-per-system device stepper and libidaens' host stepper. Component i of a vector y is VIOLATED iff
+ * (|c_i| > 1.5 and y_i*c_i <= 0) or (|c_i| > 0.5 and y_i*c_i < 0); a NaN violates nothing. Not supported together with
+ * difference-quotient Jacobians (idahip_tiny_solve returns -2, libidaens refuses every solve call), by idahip_round_solve (-2) and by
+ * idaens_calc_ic (refused). */
+int idahip_set_constraints(idahip_ctx* ctx, const double* hC /* [n] or NULL = clear */);
+/* 1 if constraints are set (hC, when non-null, receives them), 0 if not, -1 for a null ctx */
+int idahip_constraints(const idahip_ctx* ctx, double* hC);
 /* per-system problem parameters, systems [first, first+count): LORENZ63 [count][3], HEAT1D [count][1] */
 int idahip_set_problem_params(idahip_ctx* ctx, int first, int count, const double* hParams, int nparam);
 /* LINEAR_DENSE data, systems [first, first+count): hA, hB [count][n*n] column-major, hC [count][n] */
@@ -189,7 +199,8 @@ int idahip_nls_lsetup(idahip_ctx* ctx, const double* hTn, const double* hCj, int
  *          J(i,j) = (1/inc_j)*(rtemp_i - rr_i) for max(0, j-mu) <= i <= min(n-1, j+ml); every other band entry +0.0.
  * A dense DQ Jacobian costs n residual evaluations, a band one min(width, n); libidaens counts them in IDAENS_C_NRE_DQ (C IDA's
  * nreDQ), not in nre. The heat kernel writes, on a dense ctx, only rows j-1..j+1 of column j, as its analytic kernel does:
- * entries that the definition gives as -0.0 there are +0.0. Constraints (which flip inc's sign in C IDA) do not exist here.
+ * entries that the definition gives as -0.0 there are +0.0. Constraints flip inc's sign in C IDA; here a ctx with both constraints
+ * (idahip_set_constraints) and DQ Jacobians is refused by the steppers instead.
  * A DQ ctx refuses idahip_nls_lsetup and idahip_nls_sys_setup (-2: they carry no step sizes); idahip_nls_lsetup_dq is
  * idahip_nls_lsetup with them, and returns -2 on a ctx without DQ. */
 int idahip_set_jacobian_dq(idahip_ctx* ctx, int on);
@@ -236,6 +247,22 @@ int idahip_scale_phi1(idahip_ctx* ctx, const double* hFac, const int32_t* hIdx, 
 int idahip_predict(idahip_ctx* ctx, const int32_t* hKkNs, const double* hBeta, const double* hGamma, const int32_t* hIdx, int nsys);
 int idahip_post_newton(idahip_ctx* ctx, const double* hCj, const int32_t* hKk, double* hNorms, const int32_t* hIdx, int nsys);
 int idahip_restore(idahip_ctx* ctx, const int32_t* hKkNs, const double* hCvals, const int32_t* hIdx, int nsys);
+/* idahip_post_newton with the constraint check of an attempt between the final yy / yp and the norms, in one
+ * launch; a ctx with constraints only (-2 otherwise). For a listed system s with hCheck[s] != 0 (its Newton solve succeeded):
+ *   - no component of yy violated: hFlag[s] = 0, everything as idahip_post_newton;
+ *   - otherwise v_i = yy_i - 0.1*((a_i*c_i)/ewt_i) for the violated i (a_i = 1 for |c_i| = 2, else 0), v_i = +0.0 elsewhere, and
+ *     vnorm = ||v||_wrms(ewt), summed left to right, sqrt and comparison on the device:
+ *       vnorm <= hEpsNewt[s]: hFlag[s] = 1; ee_i -= v_i for the violated i only; the four norms are those of the corrected ee;
+ *                             yy and yp keep their uncorrected values;
+ *       otherwise:            hFlag[s] = 2; hRr[s] = fmax(0.9*q, 0.1) with q the minimum of phi[0]_i / (phi[0]_i - yy_i) over the
+ *                             violated i with phi[0]_i != yy_i (DBL_MAX when there is none); ee is left alone, hNorms[s] = 0.
+ * hRr[s] = 0 unless hFlag[s] = 2. hCheck[s] == 0 skips the check: that system's results are idahip_post_newton's, bit for bit,
+ * with hFlag[s] = 0. A NaN in phi[0] or ewt is outside the definition. */
+int idahip_post_newton_constr(idahip_ctx* ctx, const double* hCj, const int32_t* hKk, const double* hEpsNewt, const int32_t* hCheck,
+                              double* hNorms, int32_t* hFlag, double* hRr, const int32_t* hIdx, int nsys);
+/* The constraint mask of one field: hViolated[s] = 1 if a component of `field` of listed system s is violated, else 0 (the start of
+ * an integration checks IDAHIP_F_PHI0). A ctx with constraints only (-2 otherwise). */
+int idahip_constr_check(idahip_ctx* ctx, idahip_field field, int32_t* hViolated, const int32_t* hIdx, int nsys);
 int idahip_complete_step(idahip_ctx* ctx, const int32_t* hKused, const double* hCk, int maxord, double* hPhi0Nrm,
                          int32_t* hEwtBad, const int32_t* hIdx, int nsys);
 int idahip_get_solution(idahip_ctx* ctx, const int32_t* hKord, const double* hCvals, const double* hDvals,

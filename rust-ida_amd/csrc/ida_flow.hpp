@@ -39,7 +39,9 @@ struct FlowArgs {
 // yy_from_phi01(f) (yy = phi[0] + f * phi[1]), yy_add_phi1(f) (yy += f * phi[1])
 // ROOTS = false compiles the root finding out (the steppers' kernels are instantiated both ways: the bracketing code costs
 // the no-roots kernels registers and scratch otherwise -- config 2: 57 -> 46 M iters/s with it compiled in).
-template <class V, bool ROOTS = false>
+// CONSTR = true compiles the inequality-constraint check in: V then also provides
+// post_newton_constr(s, checked, norms[4], &rr) -> 0 passed | 1 corrected | 2 recover, and constr_phi0_violated().
+template <class V, bool ROOTS = false, bool CONSTR = false>
 struct IdaFlow {
     const FlowArgs& a;
     idactl::SysCore& s;
@@ -330,6 +332,10 @@ struct IdaFlow {
             s.status = ist;
         }
     }
+    __device__ bool start_violates() const {
+        if constexpr (CONSTR) return v.constr_phi0_violated();
+        else return false;
+    }
     // (re)enter the schedule: the first-call block for a system that has not started (impl_solve.rs:84-173), then the entry
     // of its first Ida::solve call; true = the system steps
     __device__ bool start_system() const {
@@ -342,6 +348,9 @@ struct IdaFlow {
             const double troundoff = 2.0 * eps * (fabs(s.tn) + fabs(tout));
             if (tdist == 0.0 || tdist < troundoff) {
                 s.status = IDAENS_ILL_INPUT;  // "tout too close to t0 to start integration"
+                s.tret = s.tn;
+            } else if (start_violates()) {
+                s.status = IDAENS_ILL_INPUT;  // y0 does not satisfy the constraints
                 s.tret = s.tn;
             } else {
                 s.setup_done = true;
@@ -418,10 +427,19 @@ struct IdaFlow {
     // newton_solve_batched); true = the system steps on
     __device__ bool attempt_end() const {
         double norms[4];
-        v.post_newton(s, norms);
+        int cflag = 0;
+        if constexpr (CONSTR) {
+            double crr;
+            cflag = v.post_newton_constr(s, s.nls_ret == idactl::NLS_SUCCESS, norms, &crr);
+            if (cflag == 2) s.rr = crr;  // kept by handle_n_flag
+        } else {
+            v.post_newton(s, norms);
+        }
         int nflag = idactl::NFLAG_NONE;
         double err_k = 0.0, err_km1 = 0.0;
-        if (s.nls_ret == idactl::NLS_SUCCESS) {
+        if (CONSTR && cflag == 2) {
+            nflag = idactl::NFLAG_CONSTR_RECVR;
+        } else if (s.nls_ret == idactl::NLS_SUCCESS) {
             if (!idactl::test_error(s, s.ck, norms, &err_k, &err_km1)) nflag = idactl::NFLAG_TEST_FAIL;
         } else if (s.nls_ret == idactl::NLS_CONV_RECVR) {
             nflag = idactl::NFLAG_CONV_RECVR;

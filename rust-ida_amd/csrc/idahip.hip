@@ -237,7 +237,7 @@ int idahip_destroy(idahip_ctx* c) {
     if (!c) return 0;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
-                    c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->ic_y,
+                    c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->d_constr, c->ic_y,
                     c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d};
     for (void* p : ptrs)
@@ -429,6 +429,29 @@ int idahip_id(const idahip_ctx* c, double* hId) {
     if (!c) return -1;
     if (c->h_id.empty()) return 0;
     if (hId) std::memcpy(hId, c->h_id.data(), sizeof(double) * c->n);
+    return 1;
+}
+
+int idahip_set_constraints(idahip_ctx* c, const double* hC) {
+    DevGuard dev_guard__(c);
+    if (!c) return -1;
+    if (!hC) {
+        c->h_constr.clear();
+        return 0;
+    }
+    for (int i = 0; i < c->n; ++i)
+        if (!idactl::constr_value_ok(hC[i])) return fail(c, -2, "constraint[%d] = %g: 0 (none), 1 (>= 0), -1 (<= 0), 2 (> 0) or -2 (< 0)", i, hC[i]);
+    if (!c->d_constr) { int rc = dalloc(c, &c->d_constr, (size_t)c->n); if (rc) return rc; }
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    IDAHIP_HIP(c, hipMemcpy(c->d_constr, hC, sizeof(double) * c->n, hipMemcpyHostToDevice));
+    c->h_constr.assign(hC, hC + c->n);
+    return 0;
+}
+
+int idahip_constraints(const idahip_ctx* c, double* hC) {
+    if (!c) return -1;
+    if (c->h_constr.empty()) return 0;
+    if (hC) std::memcpy(hC, c->h_constr.data(), sizeof(double) * c->n);
     return 1;
 }
 
@@ -1348,6 +1371,72 @@ int idahip_post_newton(idahip_ctx* c, const double* hCj, const int32_t* hKk, dou
     return 0;
 }
 
+int idahip_post_newton_constr(idahip_ctx* c, const double* hCj, const int32_t* hKk, const double* hEpsNewt, const int32_t* hCheck,
+                              double* hNorms, int32_t* hFlag, double* hRr, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hCj || !hKk || !hEpsNewt || !hCheck || !hNorms || !hFlag || !hRr) return fail(c, -2, "null argument");
+    if (c->h_constr.empty()) return fail(c, -2, "idahip_post_newton_constr on a ctx without constraints (idahip_set_constraints)");
+    if (nsys == 0) return 0;
+    for (int s = 0; s < nsys; ++s)
+        if (hKk[s] < 1 || hKk[s] >= MXORDP1) return fail(c, -2, "bad kk at list position %d", s);
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    const double* d_cj = ap.in(hCj, nsys);
+    const int* d_kk = ap.in(hKk, nsys);
+    const double* d_eps = ap.in(hEpsNewt, nsys);
+    const int* d_chk = ap.in(hCheck, nsys);
+    double* d_out = ap.out<double>(4 * (size_t)nsys);
+    double* d_rr = ap.out<double>((size_t)nsys);
+    int* d_flag = ap.out<int>((size_t)nsys);
+    if ((rc = ap.ok())) return rc;
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+        hipLaunchKernelGGL(post_newton_constr_kernel, dim3(nsys), dim3(256), 4 * sizeof(double) * c->n, c->stream, vec_state(c),
+                           (const double*)c->d_constr, d_idx, d_cj, d_kk, d_eps, d_chk, d_out, d_flag, d_rr);
+        if ((rc = post_launch(c, "post_newton_constr"))) return rc;
+    }
+    if ((rc = ap.fetch())) return rc;
+    const double* h = ap.host_of(d_out);
+    const double* hr = ap.host_of((const double*)d_rr);
+    const int* hf = ap.host_of((const int*)d_flag);
+    for (size_t e = 0; e < 4 * (size_t)nsys; ++e) hNorms[e] = sqrt(h[e] / (double)c->n);
+    for (int s = 0; s < nsys; ++s) {
+        hFlag[s] = hf[s];
+        hRr[s] = hr[s];
+    }
+    return 0;
+}
+
+int idahip_constr_check(idahip_ctx* c, idahip_field field, int32_t* hViolated, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!hViolated) return fail(c, -2, "null argument");
+    if (c->h_constr.empty()) return fail(c, -2, "idahip_constr_check on a ctx without constraints (idahip_set_constraints)");
+    const double* x = field_ptr(c, field);
+    if (!x) return fail(c, -2, "unknown field %d", (int)field);
+    if (nsys == 0) return 0;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    int* d_v = ap.out<int>((size_t)nsys);
+    if ((rc = ap.ok())) return rc;
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+        hipLaunchKernelGGL(constr_check_kernel, dim3(nsys), dim3(256), 0, c->stream, x, (const double*)c->d_constr, c->n, d_idx, d_v);
+        if ((rc = post_launch(c, "constr_check"))) return rc;
+    }
+    if ((rc = ap.fetch())) return rc;
+    const int* hv = ap.host_of((const int*)d_v);
+    for (int s = 0; s < nsys; ++s) hViolated[s] = hv[s];
+    return 0;
+}
+
 int idahip_restore(idahip_ctx* c, const int32_t* hKkNs, const double* hCvals, const int32_t* hIdx, int nsys) {
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
@@ -1848,6 +1937,7 @@ int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_
     if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
     if (c->n != 3 || (c->kind != IDAHIP_ROBERTS && c->kind != IDAHIP_LORENZ63))
         return fail(c, -2, "the device-resident stepper takes the Roberts and Lorenz63 problems (n = 3)");
+    if (c->jac_dq && !c->h_constr.empty()) return fail(c, -2, "difference-quotient Jacobians and constraints do not combine (DESIGN.md section 4g)");
     if (call->recycle && (!c->ic_y || !c->ic_yp)) return fail(c, -2, "recycle needs idahip_snapshot_initial");
     if (call->recycle && call->max_rounds < 1) return fail(c, -2, "recycle needs a round limit");
     const int batch = c->batch, n = c->n;
@@ -1891,14 +1981,19 @@ int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_
         }
         // LDS: the controller records of a workgroup, and the systems' vectors too when the device grants that much
         const size_t lds_state = (size_t)spw * sizeof(idactl::SysCore), lds_all = lds_state + (size_t)spw * sizeof(double) * tiny_lds_doubles(n);
-        // four instantiations: problem x (root finding compiled in | out -- the bracketing code costs the plain stepper registers)
+        // instantiations: problem x (root finding compiled in | out -- the bracketing code costs the plain stepper registers)
         const bool roots = call->nroots > 0;
-        auto kern = c->kind == IDAHIP_ROBERTS ? (roots ? tiny_ida_kernel<IDAHIP_ROBERTS, true> : tiny_ida_kernel<IDAHIP_ROBERTS, false>)
-                                              : (roots ? tiny_ida_kernel<IDAHIP_LORENZ63, true> : tiny_ida_kernel<IDAHIP_LORENZ63, false>);
+        // and, for each, a twin with the constraint check compiled in (the plain kernels come out as they were without it)
+        const bool constr = !c->h_constr.empty();
+        auto kern = c->kind == IDAHIP_ROBERTS ? (roots ? tiny_ida_kernel<IDAHIP_ROBERTS, true, false> : tiny_ida_kernel<IDAHIP_ROBERTS, false, false>)
+                                              : (roots ? tiny_ida_kernel<IDAHIP_LORENZ63, true, false> : tiny_ida_kernel<IDAHIP_LORENZ63, false, false>);
+        if (constr)
+            kern = c->kind == IDAHIP_ROBERTS ? (roots ? tiny_ida_kernel<IDAHIP_ROBERTS, true, true> : tiny_ida_kernel<IDAHIP_ROBERTS, false, true>)
+                                             : (roots ? tiny_ida_kernel<IDAHIP_LORENZ63, true, true> : tiny_ida_kernel<IDAHIP_LORENZ63, false, true>);
         const int lds_vec = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * (sizeof(idactl::SysCore) + sizeof(double) * tiny_lds_doubles(n)))) == hipSuccess ? 1 : 0;
         if (!lds_vec) (void)hipGetLastError();
         const size_t shm = lds_vec ? lds_all : lds_state;
-        hipLaunchKernelGGL(kern, dim3((batch + spw - 1) / spw), dim3(spw), shm, c->stream, a, lds_vec);
+        hipLaunchKernelGGL(kern, dim3((batch + spw - 1) / spw), dim3(spw), shm, c->stream, a, lds_vec, constr ? (const double*)c->d_constr : (const double*)nullptr);
         if ((rc = post_launch(c, "tiny_ida"))) return rc;
     }
     IDAHIP_HIP(c, hipMemcpyAsync(hSys, c->tiny_sys, (size_t)batch * sizeof(idactl::SysCore), hipMemcpyDeviceToHost, c->stream));
@@ -1960,6 +2055,7 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     const bool heat = c->kind == IDAHIP_HEAT1D && c->n <= LU_BIG_MAX_N;
     if (c->n <= TINY_N || !(lin || heat) || c->lu_variant < 4)
         return fail(c, -2, "the device-resident lock-step stepper takes linear dense and heat problems with %d < n <= %d (LU variant 4)", TINY_N, LU_BIG_MAX_N);
+    if (!c->h_constr.empty()) return fail(c, -2, "the device lock-step stepper does not check constraints: the host stepper does (DESIGN.md section 4g)");
     if (call->recycle && (!c->ic_y || !c->ic_yp)) return fail(c, -2, "recycle needs idahip_snapshot_initial");
     if (call->recycle && call->max_rounds < 1) return fail(c, -2, "recycle needs a round limit");
     const int batch = c->batch, n = c->n;

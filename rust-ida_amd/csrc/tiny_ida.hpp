@@ -16,7 +16,8 @@
 //   Newton::solve         /root/reference/crates/nonlinear/src/newton.rs:51-167 (Q3: break on ConvergenceRecover with a current J)
 //   IdaNLProblem          /root/reference/src/ida_nls.rs:118-266
 //   complete_step         /root/reference/src/impl_complete_step.rs:22-177
-// Root finding for the family g_i = y[c_i] - thr_i runs here too (ida_flow.hpp). Not handled here (the host stepper keeps those
+// Root finding for the family g_i = y[c_i] - thr_i runs here too (ida_flow.hpp), and so does the inequality-constraint check of
+// DESIGN.md section 4g (TinyVecConstr, the CONSTR instantiations). Not handled here (the host stepper keeps those
 // cases): user root functions, IDA_ONE_STEP, host-callback problems, per-step traces.
 #pragma once
 #include "ida_flow.hpp"
@@ -191,6 +192,101 @@ struct TinyVec {
     }
 };
 
+// TinyVec with the constraint check (the CONSTR instantiations). The constraint vector travels in this backend and not in
+// TinyIdaArgs or TinyVec: the root-finding kernels keep both of those in scratch, and eight more bytes there change the resources of
+// kernels that never read them.
+struct TinyVecConstr : TinyVec {
+    const double* constr;  // [n] idahip_set_constraints
+
+    // post_newton_constr_kernel: post_newton with the constraint check between the final yy / yp and the
+    // norms. checked = the Newton solve succeeded. Returns 0 passed, 1 ee corrected, 2 recover with *rr (norms are 0 then).
+    __device__ int post_newton_constr(const idactl::SysCore& s, bool checked, double* norms, double* rr) const {
+        *rr = 0.0;
+        if (checked) {
+            bool any = false;
+            double sv = 0.0;
+            for (int i = 0; i < n; ++i) {
+                const double e = a.v.ee[vb + i];
+                const double y = a.v.yypredict[vb + i] + e;
+                a.v.yy[vb + i] = y;
+                a.v.yp[vb + i] = a.v.yppredict[vb + i] + s.cj * e;
+                const double c = constr[i], w = a.v.ewt[vb + i];
+                double v = 0.0;
+                if (idactl::constr_violated(c, y)) {
+                    v = idactl::constr_correction(c, y, w);
+                    any = true;
+                }
+                const double p = v * w;
+                sv = sv + p * p;
+            }
+            if (any) {
+                if (sqrt(sv / (double)n) <= s.eps_newt) {
+                    for (int i = 0; i < n; ++i) {
+                        const double c = constr[i], y = a.v.yy[vb + i];
+                        if (idactl::constr_violated(c, y)) a.v.ee[vb + i] = a.v.ee[vb + i] - idactl::constr_correction(c, y, a.v.ewt[vb + i]);
+                    }
+                } else {
+                    double q = idactl::CONSTR_QMAX;
+                    for (int i = 0; i < n; ++i) {
+                        const double y = a.v.yy[vb + i];
+                        if (!idactl::constr_violated(constr[i], y)) continue;
+                        const double p0 = phi(0, i);
+                        const double t = p0 - y;
+                        if (t != 0.0) {
+                            const double quot = p0 / t;
+                            if (quot < q) q = quot;
+                        }
+                    }
+                    *rr = idactl::constr_rr(q);
+                    norms[0] = norms[1] = norms[2] = norms[3] = 0.0;
+                    return 2;
+                }
+                error_norms(s, norms);  // of the corrected ee; yy and yp keep their uncorrected values
+                return 1;
+            }
+        }
+        post_newton(s, norms);
+        return 0;
+    }
+    // the four sums of post_newton without its writes to yy and yp
+    __device__ void error_norms(const idactl::SysCore& s, double* norms) const {
+        const int kk = s.kk;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double e = a.v.ee[vb + i];
+            const double w = a.v.ewt[vb + i];
+            double p = e * w;
+            s0 = s0 + p * p;
+            double d = 0.0;
+            if (kk > 1) {
+                d = phi(kk, i) + e;
+                p = d * w;
+                s1 = s1 + p * p;
+            }
+            if (kk > 2) {
+                d = d + phi(kk - 1, i);
+                p = d * w;
+                s2 = s2 + p * p;
+            }
+            if (kk + 1 < MXORDP1) {
+                const double tmp = e - phi(kk + 1, i);
+                p = tmp * w;
+                s3 = s3 + p * p;
+            }
+        }
+        norms[0] = sqrt(s0 / (double)n);
+        norms[1] = sqrt(s1 / (double)n);
+        norms[2] = sqrt(s2 / (double)n);
+        norms[3] = sqrt(s3 / (double)n);
+    }
+    // the start check: a component of phi[0] violates its constraint
+    __device__ bool constr_phi0_violated() const {
+        for (int i = 0; i < n; ++i)
+            if (idactl::constr_violated(constr[i], phi(0, i))) return true;
+        return false;
+    }
+};
+
 // Newton::solve for one attempt of one small system, in the owning thread (newton.rs:51-167 as ensemble_ida.cpp's
 // newton_solve_batched runs it for one system; tiny_sys_kernel / tiny_jac_kernel / tiny_getrf / tiny_newton_iter_kernel)
 template <int KIND>
@@ -312,8 +408,8 @@ __host__ __device__ constexpr int tiny_lds_doubles(int n) { return 14 * n + n * 
 // the latency of its own state (scratch and global memory: ~500 cycles a touch; LDS: ~60). The vector code is the same either way: the
 // per-thread copy of the arguments points each field at this thread's block and the offsets vb / lub are zero. Config 2 (Lorenz63, 1024 systems): 26.0 -> 31.0 M iterations/s with the controller
 // record alone.
-template <int KIND, bool ROOTS>
-__global__ __launch_bounds__(64) void tiny_ida_kernel(TinyIdaArgs ga, int lds_vec) {
+template <int KIND, bool ROOTS, bool CONSTR>
+__global__ __launch_bounds__(64) void tiny_ida_kernel(TinyIdaArgs ga, int lds_vec, const double* constr) {
     extern __shared__ __align__(16) unsigned char tiny_sm[];
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= ga.f.batch) return;
@@ -347,10 +443,14 @@ __global__ __launch_bounds__(64) void tiny_ida_kernel(TinyIdaArgs ga, int lds_ve
         a.piv = pv;
     }
     const long vb = lds_vec ? 0 : gvb, lub = lds_vec ? 0 : (long)b * n * n;
-    TinyVec v{a, b, n, vb, gvb};
+    using Vec = std::conditional_t<CONSTR, TinyVecConstr, TinyVec>;
+    Vec v = [&] {
+        if constexpr (CONSTR) return TinyVecConstr{{a, b, n, vb, gvb}, constr};
+        else return TinyVec{a, b, n, vb, gvb};
+    }();
     idahip_root_state rs;
     if (ROOTS) rs = ga.roots[b];
-    const IdaFlow<TinyVec, ROOTS> F{a.f, s, v, ROOTS ? &rs : nullptr};
+    const IdaFlow<Vec, ROOTS, CONSTR> F{a.f, s, v, ROOTS ? &rs : nullptr};
     const TinyNewton<KIND> N{a, s, b, n, vb, lub};
     long long ground = a.round_base;  // global round counter (idaens_stream: every system takes part in every round)
     long long done = 0;

@@ -12,6 +12,7 @@
 #pragma once
 #include "common.hpp"
 #include "solve_kernels.hpp"
+#include "../host/ida_controller.hpp"
 
 namespace idahip {
 
@@ -126,6 +127,136 @@ __global__ __launch_bounds__(256) void post_newton_kernel(VecState s, const int*
     }
     __syncthreads();
     if (threadIdx.x < 4) out[4 * blockIdx.x + threadIdx.x] = seq_sum_lds(sm + threadIdx.x * n, n);
+}
+
+// post_newton_kernel followed by the inequality-constraint check of DESIGN.md section 4g (C IDA's IDASetConstraints; the reference
+// has none), in one launch. cvec[n]: 0 none, 1: y >= 0, -1: y <= 0, 2: y > 0, -2: y < 0 (idactl::constr_violated).
+//   phase 1: yy, yp; v_i = the correction of a violated component (+0.0 elsewhere); sm[i] = (v_i ewt_i)^2
+//   decision (one lane, then uniform): no violation -> 0; sqrt(sum / n) <= eps_newt -> 1 (correct); otherwise 2 (recover)
+//   phase 2: 0 / 1: ee_i -= v_i for the violated i (flag 1), then post_newton_kernel's four sums of the ee now in memory;
+//            2: rr from the minimum of phi[0]_i / (phi[0]_i - yy_i) over the violated i whose denominator is not zero, sums = 0
+// The sums of phase 2 reuse the LDS of phase 1's (4 n doubles in all, as post_newton_kernel). check[s] == 0 (the Newton solve
+// failed): no check, the system gets post_newton_kernel's results. out [nsys][4] sums, flag [nsys], rr [nsys] (0 unless flag 2).
+__global__ __launch_bounds__(256) void post_newton_constr_kernel(VecState s, const double* __restrict__ cvec, const int* __restrict__ idx,
+                                                                 const double* __restrict__ cjs, const int* __restrict__ kks,
+                                                                 const double* __restrict__ eps_newt, const int* __restrict__ check,
+                                                                 double* __restrict__ out, int* __restrict__ flag, double* __restrict__ rr) {
+    extern __shared__ __align__(16) double sm[];
+    __shared__ double s_q[256];
+    __shared__ int s_any, s_flag;
+    const int n = s.n;
+    const int b = idx[blockIdx.x];
+    const long vb = (long)b * n;
+    const double cj = cjs[blockIdx.x];
+    const int kk = kks[blockIdx.x];
+    const bool chk = check[blockIdx.x] != 0;
+    if (threadIdx.x == 0) {
+        s_any = 0;
+        s_flag = 0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const double e = s.ee[vb + i];
+        const double y = s.yypredict[vb + i] + e;
+        s.yy[vb + i] = y;
+        s.yp[vb + i] = s.yppredict[vb + i] + cj * e;
+        if (chk) {
+            const double c = cvec[i], w = s.ewt[vb + i];
+            double v = 0.0;
+            if (idactl::constr_violated(c, y)) {
+                v = idactl::constr_correction(c, y, w);
+                s_any = 1;
+            }
+            const double p = v * w;
+            sm[i] = p * p;
+        }
+    }
+    __syncthreads();
+    if (chk && threadIdx.x == 0 && s_any) {
+        const double vnorm = sqrt(seq_sum_lds(sm, n) / (double)n);
+        s_flag = (vnorm <= eps_newt[blockIdx.x]) ? 1 : 2;
+    }
+    __syncthreads();
+    const int fl = s_flag;
+    if (fl == 2) {
+        double q = idactl::CONSTR_QMAX;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const double y = s.yy[vb + i];
+            if (!idactl::constr_violated(cvec[i], y)) continue;
+            const double p0 = s.phi[vb + i];
+            const double t = p0 - y;
+            if (t != 0.0) {
+                const double quot = p0 / t;
+                if (quot < q) q = quot;
+            }
+        }
+        s_q[threadIdx.x] = q;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (threadIdx.x < w && s_q[threadIdx.x + w] < s_q[threadIdx.x]) s_q[threadIdx.x] = s_q[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            flag[blockIdx.x] = 2;
+            rr[blockIdx.x] = idactl::constr_rr(s_q[0]);
+        }
+        if (threadIdx.x < 4) out[4 * blockIdx.x + threadIdx.x] = 0.0;
+        return;
+    }
+    for (int i = threadIdx.x; i < n; i += 256) {
+        double e = s.ee[vb + i];
+        const double w = s.ewt[vb + i];
+        if (fl == 1) {
+            const double c = cvec[i], y = s.yy[vb + i];
+            if (idactl::constr_violated(c, y)) {
+                e = e - idactl::constr_correction(c, y, w);
+                s.ee[vb + i] = e;
+            }
+        }
+        double p = e * w;
+        sm[i] = p * p;
+        double d = 0.0;
+        if (kk > 1) {
+            d = s.phi[kk * s.phistride + vb + i] + e;
+            p = d * w;
+            sm[n + i] = p * p;
+        } else {
+            sm[n + i] = 0.0;
+        }
+        if (kk > 2) {
+            d = d + s.phi[(kk - 1) * s.phistride + vb + i];
+            p = d * w;
+            sm[2 * n + i] = p * p;
+        } else {
+            sm[2 * n + i] = 0.0;
+        }
+        if (kk + 1 < MXORDP1) {
+            const double tmp = e - s.phi[(kk + 1) * s.phistride + vb + i];
+            p = tmp * w;
+            sm[3 * n + i] = p * p;
+        } else {
+            sm[3 * n + i] = 0.0;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) out[4 * blockIdx.x + threadIdx.x] = seq_sum_lds(sm + threadIdx.x * n, n);
+    if (threadIdx.x == 0) {
+        flag[blockIdx.x] = fl;
+        rr[blockIdx.x] = 0.0;
+    }
+}
+
+// the constraint mask of one field (x: [batch][n]): violated[s] = 1 when a component of listed system s violates cvec
+__global__ __launch_bounds__(256) void constr_check_kernel(const double* __restrict__ x, const double* __restrict__ cvec, int n,
+                                                           const int* __restrict__ idx, int* __restrict__ violated) {
+    __shared__ int s_any;
+    const long vb = (long)idx[blockIdx.x] * n;
+    if (threadIdx.x == 0) s_any = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256)
+        if (idactl::constr_violated(cvec[i], x[vb + i])) s_any = 1;
+    __syncthreads();
+    if (threadIdx.x == 0) violated[blockIdx.x] = s_any;
 }
 
 // phi[j] *= cvals[j-ns], j = ns..kk

@@ -78,6 +78,7 @@ struct idaens {
     int64_t retired_iters = 0, passes = 0;  // idaens_stream: Newton iterations / integrations of systems already restarted
     bool have_ic = false, streaming = false;
     bool started = false;  // a solve / solve_schedule / stream call has been made: idaens_calc_ic is refused from then on
+    bool constr = false;   // the ctx has constraints (idahip_set_constraints): read at the start of every solve / solve_schedule / stream call
     bool pow_mismatch = false; // glibc_pow.hpp != this host's std::pow (checked at create): the device steppers stay off
     bool device_ctl = true;    // small device problems: the whole of Ida::solve in one launch (idahip_tiny_solve), no lock-step rounds
     bool fused_newton = true;  // first two Newton iterations and their convergence tests in one device call (idahip_newton_iter2)
@@ -650,7 +651,24 @@ int attempt_round(idaens* e, std::vector<int32_t>& act, SolveCall& C) {
         cj[q] = S[act[q]].cj;
         kk[q] = S[act[q]].kk;
     }
-    ENS_CALL(e, idahip_post_newton(e->ctx, cj.data(), kk.data(), norms.data(), act.data(), na));
+    // with constraints: the same launch also checks the new yy of the systems whose Newton solve succeeded
+    // and either corrects ee before the norms are formed (flag 1) or asks for a shorter step (flag 2, with rr)
+    std::vector<int32_t> cflag;
+    std::vector<double> crr;
+    if (e->constr) {
+        std::vector<double> epsn(na);
+        std::vector<int32_t> check(na);
+        cflag.resize(na);
+        crr.resize(na);
+        for (int q = 0; q < na; ++q) {
+            epsn[q] = S[act[q]].eps_newt;
+            check[q] = S[act[q]].nls_ret == NLS_SUCCESS ? 1 : 0;
+        }
+        ENS_CALL(e, idahip_post_newton_constr(e->ctx, cj.data(), kk.data(), epsn.data(), check.data(), norms.data(), cflag.data(), crr.data(),
+                                              act.data(), na));
+    } else {
+        ENS_CALL(e, idahip_post_newton(e->ctx, cj.data(), kk.data(), norms.data(), act.data(), na));
+    }
 
     // --- decisions
     std::vector<int32_t> rest_idx, rest_kkns, done_idx, done_kused, reset_idx;
@@ -661,7 +679,10 @@ int attempt_round(idaens* e, std::vector<int32_t>& act, SolveCall& C) {
         Sys& s = S[b];
         int nflag = NFLAG_NONE;
         double err_k = 0.0, err_km1 = 0.0;
-        if (s.nls_ret == NLS_SUCCESS) {
+        if (e->constr && cflag[q] == 2) {
+            nflag = NFLAG_CONSTR_RECVR;
+            s.rr = crr[q];  // kept by handle_n_flag
+        } else if (s.nls_ret == NLS_SUCCESS) {
             if (!test_error(s, s.ck, &norms[4 * q], &err_k, &err_km1)) nflag = NFLAG_TEST_FAIL;
         } else if (s.nls_ret == NLS_CONV_RECVR) {
             nflag = NFLAG_CONV_RECVR;
@@ -957,6 +978,7 @@ int device_ctl_applies(const idaens* e, const SolveCall& C) {
     // root finding on the device: the function family of idaens_set_roots (not a user callback), not in idaens_stream
     if (e->nrtfn != 0 && (e->rt_fn != nullptr || e->nrtfn > IDAHIP_MAX_ROOTS || C.recycle)) return 0;
     if (e->n <= 8 && (k == IDAHIP_ROBERTS || k == IDAHIP_LORENZ63)) return 1;
+    if (idahip_constraints(e->ctx, nullptr) == 1) return 0;  // the lock-step device rounds have no constraint check
     if (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D) && idahip_lu_variant(e->ctx) >= 4) return 2;
     return 0;
 }
@@ -1049,7 +1071,17 @@ int solve_core_device(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, 
     return 0;
 }
 
+// Whether the ctx has constraints, read anew by every solve / solve_schedule / stream call (C IDA lets a user change them between
+// calls). With difference-quotient Jacobians they are refused: C IDA flips the increments' signs there.
+int read_constraints(idaens* e) {
+    e->constr = idahip_constraints(e->ctx, nullptr) == 1;
+    if (e->constr && idahip_jacobian_dq(e->ctx) > 0)
+        return efail(e, -2, "constraints on a ctx with difference-quotient Jacobians are not supported");
+    return 0;
+}
+
 int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long max_rounds) {
+    if (const int rcc = read_constraints(e)) return rcc;
     e->started = true;
     if (const int mode = device_ctl_applies(e, C)) return solve_core_device(e, C, hTret, hStatus, max_rounds, mode);
     const double eps = std::numeric_limits<double>::epsilon();
@@ -1072,6 +1104,11 @@ int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long ma
                 // and ||phi[0]|| for the first tolsf test (impl_solve.rs:289-295)
                 std::vector<double> ypnorm(fresh.size()), p0nrm(fresh.size());
                 ENS_CALL(e, idahip_init_first(e->ctx, ypnorm.data(), p0nrm.data(), fresh.data(), (int)fresh.size()));
+                std::vector<int32_t> viol;
+                if (e->constr) {  // y0 must satisfy the constraints
+                    viol.resize(fresh.size());
+                    ENS_CALL(e, idahip_constr_check(e->ctx, IDAHIP_F_PHI0, viol.data(), fresh.data(), (int)fresh.size()));
+                }
                 std::vector<int32_t> ok;
                 std::vector<double> fac;
                 for (size_t q = 0; q < fresh.size(); ++q) {
@@ -1080,6 +1117,11 @@ int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long ma
                     const double troundoff = 2.0 * eps * (std::fabs(s.tn) + std::fabs(tout));
                     if (tdist == 0.0 || tdist < troundoff) {
                         s.status = IDAENS_ILL_INPUT;  // "tout too close to t0 to start integration"
+                        s.tret = s.tn;
+                        continue;
+                    }
+                    if (e->constr && viol[q]) {
+                        s.status = IDAENS_ILL_INPUT;  // "y0 fails to satisfy constraints"
                         s.tret = s.tn;
                         continue;
                     }
@@ -1267,6 +1309,7 @@ int idaens_solve(idaens* e, double tout, int itask, double* hTret, int32_t* hSta
 
 int idaens_stream(idaens* e, const double* touts, int ntout, long max_rounds, long stagger_rounds, int64_t* passes_done) {
     if (!e || !touts || ntout < 1 || max_rounds < 1 || stagger_rounds < 0) return -1;
+    if (const int rcc = read_constraints(e)) return rcc;
     if (!e->streaming && stagger_rounds > 0) {  // first call: system b enters at round b * stagger / batch
         e->start_round.resize(e->batch);
         for (int b = 0; b < e->batch; ++b) e->start_round[b] = e->total_rounds + (int64_t)b * stagger_rounds / e->batch;
@@ -1561,6 +1604,7 @@ extern "C" int idaens_calc_ic(idaens* e, int icopt, double tout1, int32_t* hStat
     if (icopt == IDAENS_YA_YDP_INIT && idahip_id(e->ctx, nullptr) != 1)
         return efail(e, -2, "idaens_calc_ic: IDAENS_YA_YDP_INIT needs the id vector (idahip_set_id)");
     if (e->started) return efail(e, -2, "idaens_calc_ic: only before the first solve, solve_schedule or stream call");
+    if (idahip_constraints(e->ctx, nullptr) == 1) return efail(e, -2, "idaens_calc_ic: a ctx with constraints is not supported (idahip_set_constraints)");
     if (!e->have_ic) return efail(e, -2, "no snapshot of the initial conditions (idaens_create failed to take it)");
     return calc_ic(e, icopt, tout1, hStatus);
 }

@@ -48,11 +48,12 @@ constexpr int MAXNLSIT = 4;
 constexpr double RATEMAX = 0.9;
 
 enum NlsCode { NLS_SUCCESS = 0, NLS_CONV_RECVR = 1, NLS_LSETUP_RECVR = 2 };
-enum NFlag { NFLAG_NONE = 0, NFLAG_TEST_FAIL = 1, NFLAG_CONV_RECVR = 2, NFLAG_LSETUP_RECVR = 3 };
+enum NFlag { NFLAG_NONE = 0, NFLAG_TEST_FAIL = 1, NFLAG_CONV_RECVR = 2, NFLAG_LSETUP_RECVR = 3,
+             NFLAG_CONSTR_RECVR = 4 /* the inequality constraints asked for a shorter step: s.rr holds the factor */ };
 enum Phase { PH_IDLE = 0 /* between solve calls */, PH_LOOP_TOP = 1 /* needs the loop-top checks, then a new step */,
              PH_RETRY = 2 /* inside step()'s attempt loop */ };
 // status codes of include/ida_ensemble.h that the controller itself produces
-constexpr int ST_ERR_FAIL = -3, ST_CONV_FAIL = -4, ST_BAD_T = -26;
+constexpr int ST_ERR_FAIL = -3, ST_CONV_FAIL = -4, ST_CONSTR_FAIL = -11, ST_BAD_T = -26;
 
 struct SysCore {
     // --- Ida scalars (src/lib.rs:89-244)
@@ -246,6 +247,26 @@ IDA_HD inline bool test_error(SysCore& s, double ck, const double* nrm /* enorm_
     return (ck * enorm_k) <= 1.0;
 }
 
+// ---------------------------------------------------------------- inequality constraints (C IDA's
+// IDASetConstraints -- the reference has none). c = 0 none, 1: y >= 0, -1: y <= 0, 2: y > 0, -2: y < 0.
+IDA_HD inline bool constr_value_ok(double c) { return c == 0.0 || c == 1.0 || c == -1.0 || c == 2.0 || c == -2.0; }
+// whether component y violates its constraint c (a NaN violates nothing)
+IDA_HD inline bool constr_violated(double c, double y) {
+    const double ac = IDA_FABS(c), yc = y * c;
+    return (ac > 1.5 && yc <= 0.0) || (ac > 0.5 && yc < 0.0);
+}
+// the correction of a violated component: v = y - 0.1 * ((a * c) / ewt), a = 1 for a strict constraint, else 0
+IDA_HD inline double constr_correction(double c, double y, double ewt) {
+    const double a = IDA_FABS(c) >= 1.5 ? 1.0 : 0.0;
+    return y - 0.1 * ((a * c) / ewt);
+}
+// rr of a constraint failure from the min-quotient q (DBL_MAX when no violated component had phi[0] != yy)
+IDA_HD inline double constr_rr(double q) {
+    const double rr = 0.9 * q;
+    return IDA_FMAX(rr, 0.1);
+}
+constexpr double CONSTR_QMAX = 1.7976931348623157e308;  // DBL_MAX
+
 // ---------------------------------------------------------------- restore scalars (lib.rs:1044-1083)
 IDA_HD inline void restore_scalars(SysCore& s) {
     s.tn = s.saved_t;
@@ -290,10 +311,10 @@ IDA_HD inline int handle_n_flag(SysCore& s, int nflag, double err_k, double err_
     }
     s.ncf += 1;
     s.ncfn += 1;
-    s.rr = 0.25;
+    if (nflag != NFLAG_CONSTR_RECVR) s.rr = 0.25;  // a constraint failure keeps the rr of its min-quotient (C IDA's IDAHandleNFlag)
     s.hh *= s.rr;
     if (s.ncf < maxncf) return 0;
-    return ST_CONV_FAIL;
+    return nflag == NFLAG_CONSTR_RECVR ? ST_CONSTR_FAIL : ST_CONV_FAIL;
 }
 
 // ---------------------------------------------------------------- complete_step scalars (impl_complete_step.rs:22-147)

@@ -44,6 +44,7 @@ HIP_SYMBOLS = [
     "idahip_set_jacobian_dq", "idahip_jacobian_dq", "idahip_set_host_residual", "idahip_jac_dq", "idahip_nls_lsetup_dq",
     "idahip_set_id", "idahip_id", "idahip_ic_begin", "idahip_ic_reset", "idahip_ic_res", "idahip_ic_setup", "idahip_ic_setup_dq",
     "idahip_ic_solve", "idahip_ic_trial", "idahip_ic_accept", "idahip_ic_commit",
+    "idahip_set_constraints", "idahip_constraints", "idahip_post_newton_constr", "idahip_constr_check",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
@@ -146,6 +147,10 @@ def load():
     H.idahip_nls_lsetup_dq.argtypes = [vp, dp, dp, dp, i32p, i32p, ci]
     H.idahip_set_id.argtypes = [vp, dp]
     H.idahip_id.argtypes = [vp, dp]
+    H.idahip_set_constraints.argtypes = [vp, dp]
+    H.idahip_constraints.argtypes = [vp, dp]
+    H.idahip_post_newton_constr.argtypes = [vp, dp, i32p, dp, i32p, dp, i32p, dp, i32p, ci]
+    H.idahip_constr_check.argtypes = [vp, ci, i32p, i32p, ci]
     H.idahip_ic_begin.argtypes = [vp, dp, i32p, i32p, ci]
     H.idahip_ic_reset.argtypes = [vp, i32p, ci]
     H.idahip_ic_res.argtypes = [vp, dp, dp, i32p, ci]
@@ -279,6 +284,17 @@ class Ctx:
         """The id vector [n], or None if none is set."""
         out = np.zeros(self.n)
         return out if self._chk(self.H.idahip_id(self.h, _p(out)), "id") == 1 else None
+
+    def set_constraints(self, c):
+        """C IDA's IDASetConstraints: c[i] = 0.0 none, 1.0: y_i >= 0, -1.0: y_i <= 0, 2.0: y_i > 0,
+        -2.0: y_i < 0, shared by the ensemble. None clears them; any other value is refused (-2)."""
+        a = None if c is None else _f64(c).reshape(self.n)
+        self._chk(self.H.idahip_set_constraints(self.h, _p(a)), "set_constraints")
+
+    def constraints(self):
+        """The constraint vector [n], or None if none is set."""
+        out = np.zeros(self.n)
+        return out if self._chk(self.H.idahip_constraints(self.h, _p(out)), "constraints") == 1 else None
 
     def set_problem_params(self, params, first=0):
         p = _f64(params).reshape(-1, _f64(params).shape[-1] if np.ndim(params) > 1 else 1)
@@ -531,6 +547,28 @@ class Ctx:
         kk = _i32(np.broadcast_to(kk, idx.shape))
         out = np.zeros((idx.size, 4))
         self._chk(self.H.idahip_post_newton(self.h, _p(cj), _p(kk, i32p), _p(out), _p(idx, i32p), idx.size), "post_newton")
+        return out
+
+    def post_newton_constr(self, cj, kk, eps_newt, check=1, idx=None):
+        """post_newton with the constraint check of an attempt in the same launch -> (norms [nsys][4], flag [nsys], rr [nsys]);
+        flag 0 passed (or check == 0: not checked), 1 ee corrected, 2 recover with rr."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        cj = _f64(np.broadcast_to(cj, idx.shape))
+        kk = _i32(np.broadcast_to(kk, idx.shape))
+        eps_newt = _f64(np.broadcast_to(eps_newt, idx.shape))
+        check = _i32(np.broadcast_to(check, idx.shape))
+        out = np.zeros((idx.size, 4))
+        flag = np.zeros(idx.size, dtype=np.int32)
+        rr = np.zeros(idx.size)
+        self._chk(self.H.idahip_post_newton_constr(self.h, _p(cj), _p(kk, i32p), _p(eps_newt), _p(check, i32p), _p(out), _p(flag, i32p),
+                                                   _p(rr), _p(idx, i32p), idx.size), "post_newton_constr")
+        return out, flag, rr
+
+    def constr_check(self, field=F_PHI0, idx=None):
+        """The constraint mask of one field -> violated [nsys] (1: some component of the system violates its constraint)."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        out = np.zeros(idx.size, dtype=np.int32)
+        self._chk(self.H.idahip_constr_check(self.h, int(field), _p(out, i32p), _p(idx, i32p), idx.size), "constr_check")
         return out
 
     def restore(self, kk, ns, cvals, idx=None):
