@@ -384,18 +384,53 @@ __device__ __forceinline__ double upd(double a, double u, double l) { return a -
 
 // Raw buffer loads / stores: a per-lane 32-bit byte offset plus a scalar byte offset, no 64-bit vector address arithmetic; a
 // per-lane offset at or beyond the descriptor's size reads +0.0 without touching memory (range check on the vector offset).
+// NT: the access carries the non-temporal bit (aux bit 1, `nt` in the ISA): the line is marked for early eviction from L2 / MALL -- for
+// data that this launch touches once (exp_switches.hpp, NT_*). A cache policy changes no value.
+template <bool NT = false>
 __device__ __forceinline__ double buf_load_f64(__amdgpu_buffer_rsrc_t rsrc, unsigned voffset, int soffset) {
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
-    const v2u r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voffset, soffset, 0);
+    const v2u r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voffset, soffset, NT ? 2 : 0);
     return __hiloint2double((int)r.y, (int)r.x);
 }
 
+template <bool NT = false>
 __device__ __forceinline__ void buf_store_f64(__amdgpu_buffer_rsrc_t rsrc, unsigned voffset, int soffset, double v) {
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
     v2u d;
     d.x = (unsigned)__double2loint(v);
     d.y = (unsigned)__double2hiint(v);
-    __builtin_amdgcn_raw_buffer_store_b64(d, rsrc, (int)voffset, soffset, 0);
+    __builtin_amdgcn_raw_buffer_store_b64(d, rsrc, (int)voffset, soffset, NT ? 2 : 0);
+}
+
+// Plain global loads / stores of one double or of two adjacent ones (16-byte aligned), with the same choice of policy.
+typedef double v2d_t __attribute__((ext_vector_type(2)));
+template <bool NT>
+__device__ __forceinline__ double ld_f64(const double* p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+template <bool NT>
+__device__ __forceinline__ void st_f64(double* p, double v) {
+    if constexpr (NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+template <bool NT>
+__device__ __forceinline__ double2 ld_f64x2(const double* p) {
+    v2d_t q;
+    if constexpr (NT) q = __builtin_nontemporal_load(reinterpret_cast<const v2d_t*>(p));
+    else q = *reinterpret_cast<const v2d_t*>(p);
+    double2 r;
+    r.x = q.x;
+    r.y = q.y;
+    return r;
+}
+template <bool NT>
+__device__ __forceinline__ void st_f64x2(double* p, double2 v) {
+    v2d_t q;
+    q.x = v.x;
+    q.y = v.y;
+    if constexpr (NT) __builtin_nontemporal_store(q, reinterpret_cast<v2d_t*>(p));
+    else *reinterpret_cast<v2d_t*>(p) = q;
 }
 
 __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {

@@ -11,8 +11,9 @@
 #if !defined(IDAHIP_TIMING_BUILD) &&                                                                                   \
     (defined(IDAHIP_EXP_NOPRO) || defined(IDAHIP_EXP_NOUPD) || defined(IDAHIP_EXP_NOGATHER) || defined(IDAHIP_EXP_NODIAG) || \
      defined(IDAHIP_EXP_NOSWEEP) || defined(IDAHIP_STAMPS) || defined(IDAHIP_TRAIL_PIPE) || defined(IDAHIP_TRAIL_QUAD) ||   \
-     defined(IDAHIP_WP_RING) || defined(IDAHIP_US_PAD) || defined(IDAHIP_SYS_UNR) || defined(IDAHIP_TRAIL_AHEAD))
-#error "IDAHIP_EXP_* / IDAHIP_STAMPS / IDAHIP_TRAIL_* (IDAHIP_TRAIL_AHEAD: 0..3) / IDAHIP_WP_RING / IDAHIP_US_PAD / IDAHIP_SYS_UNR are timing-build switches: add -DIDAHIP_TIMING_BUILD (the library then reports itself as one and is not a product)"
+     defined(IDAHIP_WP_RING) || defined(IDAHIP_US_PAD) || defined(IDAHIP_SYS_UNR) || defined(IDAHIP_TRAIL_AHEAD) ||         \
+     defined(IDAHIP_NT_SYS) || defined(IDAHIP_NT_SOLVE) || defined(IDAHIP_NT_FINALIZE) || defined(IDAHIP_NT_TRAIL))
+#error "IDAHIP_EXP_* / IDAHIP_STAMPS / IDAHIP_TRAIL_* (IDAHIP_TRAIL_AHEAD: 0..3) / IDAHIP_WP_RING / IDAHIP_US_PAD / IDAHIP_SYS_UNR / IDAHIP_NT_* are timing-build switches: add -DIDAHIP_TIMING_BUILD (the library then reports itself as one and is not a product)"
 #endif
 
 namespace idahip {
@@ -91,6 +92,37 @@ constexpr bool WP_DEEP_RING = false;
 constexpr int SYS_UNR = IDAHIP_SYS_UNR;
 #else
 constexpr int SYS_UNR = 16;
+#endif
+
+// Cache policy of the streams a launch touches once (the non-temporal bit on loads and stores that exist anyway; results are bit
+// for bit the same either way). The product values are the ones that won their A/B in the stream of four groups, alternating
+// processes on one box (profiles/r07_cache_policy_ab.txt); -DIDAHIP_TIMING_BUILD -DIDAHIP_NT_...=0|1 builds
+// the other side.
+//   NT_SYS      (on):  linear_sys_kernel: A and B, and the J store of the fused variant (y, y', c keep the default policy)
+//   NT_SOLVE    (on):  wg_getrs (newton_iter_kernel, ls_solve_kernel, the IC trial): the factors
+//   NT_FINALIZE (on):  lu_finalize_kernel: the work matrix it reads, the factors it writes
+//   NT_TRAIL    (off): lu_trail64w_kernel, n <= 1024: the A22 strips read and written, the U12 store to the factors (L21, L11, the
+//                      pivot rows and the live list, which the column blocks of a matrix share, keep the default policy either
+//                      way). Same registers, LDS and instruction counts, and 3 % slower in the stream: off.
+#ifdef IDAHIP_NT_SYS
+constexpr bool NT_SYS = IDAHIP_NT_SYS != 0;
+#else
+constexpr bool NT_SYS = true;
+#endif
+#ifdef IDAHIP_NT_SOLVE
+constexpr bool NT_SOLVE = IDAHIP_NT_SOLVE != 0;
+#else
+constexpr bool NT_SOLVE = true;
+#endif
+#ifdef IDAHIP_NT_FINALIZE
+constexpr bool NT_FINALIZE = IDAHIP_NT_FINALIZE != 0;
+#else
+constexpr bool NT_FINALIZE = true;
+#endif
+#ifdef IDAHIP_NT_TRAIL
+constexpr bool NT_TRAIL = IDAHIP_NT_TRAIL != 0;
+#else
+constexpr bool NT_TRAIL = false;
 #endif
 
 }  // namespace tb

@@ -1072,7 +1072,7 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) creg[i][j] = buf_load_f64(rsC[j], cvo[i], 0);
+                for (int i = 0; i < 4; ++i) creg[i][j] = buf_load_f64<tb::NT_TRAIL>(rsC[j], cvo[i], 0);  // (A22: this workgroup alone, once per launch)
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1359,7 +1359,7 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
 #pragma unroll 4
         for (int i = 0; i < 16; ++i) {
             const int cc = wave * 16 + i;  // column of the block; its LDS slot is 4 * (cc & 15) + (cc >> 4)
-            if (cc < ncols) O[(long)(cb0 + cc) * n + k0 + lane] = Us[lane][4 * (cc & 15) + (cc >> 4)];
+            if (cc < ncols) st_f64<BUF && tb::NT_TRAIL>(O + (long)(cb0 + cc) * n + k0 + lane, Us[lane][4 * (cc & 15) + (cc >> 4)]);
         }
     }
     if constexpr (tb::NOUPD) return;  // timing build: prologue only
@@ -1490,7 +1490,7 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) buf_store_f64(rsC[j], svo[i], 0, c[i][j]);  // no such row or column: out of range, dropped
+                for (int i = 0; i < 4; ++i) buf_store_f64<tb::NT_TRAIL>(rsC[j], svo[i], 0, c[i][j]);  // no such row or column: out of range, dropped
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -1507,6 +1507,7 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
 // out(pos[r], j) = work(r, j); perm[pos[r]] = r. One workgroup per (matrix, column group).
 // sp = panel width of the pipeline (wp_rows: see below): its trailing kernels already wrote the U rows right of their panel into `out`; those
 // entries are skipped here -- the work matrix no longer holds them (sp_lead: see below).
+// Both sides of the copy pass through once: tb::NT_FINALIZE (exp_switches.hpp) marks them non-temporal.
 __global__ __launch_bounds__(256) void lu_finalize_kernel(LuWs w, double* __restrict__ out, long ostride, int* __restrict__ perm,
                                                           int cols_per_block, int sp, int sp_lead, int wp_rows) {
     if (w.cnt && (int)blockIdx.x >= *w.cnt) return;
@@ -1549,13 +1550,13 @@ __global__ __launch_bounds__(256) void lu_finalize_kernel(LuWs w, double* __rest
             for (int j0 = jbeg; j0 < je; j0 += 8) {  // eight columns' loads in flight per thread (the trip count differs from row to row: the compiler does not unroll it)
                 double v[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = (j0 + u < je) ? A[(long)(j0 + u) * n + r] : 0.0;
+                for (int u = 0; u < 8; ++u) v[u] = (j0 + u < je) ? ld_f64<tb::NT_FINALIZE>(A + (long)(j0 + u) * n + r) : 0.0;
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const bool bits = __double_as_longlong(v[u]) != 0ll;  // (a column beyond je: +0.0, no bits, no store when the block is clean; and never stored: see the test on j)
                     anybits = anybits || bits;
                     anynz = anynz || (v[u] != 0.0);
-                    if (j0 + u < je && (bits || was_dirty)) O[(long)(j0 + u) * n + p] = v[u];
+                    if (j0 + u < je && (bits || was_dirty)) st_f64<tb::NT_FINALIZE>(O + (long)(j0 + u) * n + p, v[u]);
                     if (bits && j0 + u < je) cmask |= 1u << (j0 + u - jbeg);
                 }
             }
@@ -1572,12 +1573,12 @@ __global__ __launch_bounds__(256) void lu_finalize_kernel(LuWs w, double* __rest
         } else if (w.zmap) {  // the same copy, noting which 64 x 64 blocks of the factors receive a non-zero (or a NaN)
             unsigned char* __restrict__ zm = w.zmap + (long)b * 4096;
             for (int j = jbeg; j < je; ++j) {
-                const double v = A[(long)j * n + r];
-                O[(long)j * n + p] = v;
+                const double v = ld_f64<tb::NT_FINALIZE>(A + (long)j * n + r);
+                st_f64<tb::NT_FINALIZE>(O + (long)j * n + p, v);
                 if (v != 0.0) zm[(j >> 6) * 64 + (p >> 6)] = 1;
             }
         } else {
-            for (int j = jbeg; j < je; ++j) O[(long)j * n + p] = A[(long)j * n + r];
+            for (int j = jbeg; j < je; ++j) st_f64<tb::NT_FINALIZE>(O + (long)j * n + p, ld_f64<tb::NT_FINALIZE>(A + (long)j * n + r));
         }
     }
 }

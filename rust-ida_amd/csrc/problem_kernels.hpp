@@ -149,6 +149,7 @@ __global__ void tiny_jac_kernel(double* mats, const double* __restrict__ yy, con
 // WITH_JAC: the sweep also writes the Newton matrix J = B + cj*A (mul, then add -- as linear_jac_kernel) to Jout, column-
 // major: when the reference's Newton::solve calls setup right after sys (call_lsetup), A and B are read once for both.
 // ARGS = SysArgsIC (ic_kernels.hpp): the IC front end, and with a.lu set the solve of the trial in the same launch.
+// A, B and J pass through once per launch: tb::NT_SYS (exp_switches.hpp) marks them non-temporal.
 template <int VEC, bool WITH_JAC, class ARGS = SysArgs>
 __global__ __launch_bounds__(256) void linear_sys_kernel(ARGS a, const double* __restrict__ A, const double* __restrict__ Bm,
                                                          const double* __restrict__ C, double* __restrict__ Jout) {
@@ -187,13 +188,13 @@ __global__ __launch_bounds__(256) void linear_sys_kernel(ARGS a, const double* _
                 const double* pa = Ab + (long)(j + u) * n + i;
                 const double* pb = Bb + (long)(j + u) * n + i;
                 if constexpr (VEC == 2) {
-                    const double2 qa = *reinterpret_cast<const double2*>(pa);
-                    const double2 qb = *reinterpret_cast<const double2*>(pb);
+                    const double2 qa = ld_f64x2<tb::NT_SYS>(pa);
+                    const double2 qb = ld_f64x2<tb::NT_SYS>(pb);
                     av[u][0] = qa.x; av[u][1] = qa.y;
                     bv[u][0] = qb.x; bv[u][1] = qb.y;
                 } else {
-                    av[u][0] = *pa;
-                    bv[u][0] = *pb;
+                    av[u][0] = ld_f64<tb::NT_SYS>(pa);
+                    bv[u][0] = ld_f64<tb::NT_SYS>(pb);
                 }
             }
             if constexpr (WITH_JAC) {
@@ -204,9 +205,9 @@ __global__ __launch_bounds__(256) void linear_sys_kernel(ARGS a, const double* _
                         double2 o;
                         o.x = bv[u][0] + cj * av[u][0];
                         o.y = bv[u][1] + cj * av[u][1];
-                        *reinterpret_cast<double2*>(pj) = o;
+                        st_f64x2<tb::NT_SYS>(pj, o);
                     } else {
-                        *pj = bv[u][0] + cj * av[u][0];
+                        st_f64<tb::NT_SYS>(pj, bv[u][0] + cj * av[u][0]);
                     }
                 }
             }
@@ -224,8 +225,8 @@ __global__ __launch_bounds__(256) void linear_sys_kernel(ARGS a, const double* _
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
                 if (i + v < n) {
-                    const double ae = Ab[(long)j * n + i + v], be = Bb[(long)j * n + i + v];
-                    if constexpr (WITH_JAC) Jb[(long)j * n + i + v] = be + cj * ae;
+                    const double ae = ld_f64<tb::NT_SYS>(Ab + (long)j * n + i + v), be = ld_f64<tb::NT_SYS>(Bb + (long)j * n + i + v);
+                    if constexpr (WITH_JAC) st_f64<tb::NT_SYS>(Jb + (long)j * n + i + v, be + cj * ae);
                     ra[v] = ra[v] + ae * syp[j];
                     rb[v] = rb[v] + be * syy[j];
                 }

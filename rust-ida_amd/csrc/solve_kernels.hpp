@@ -37,6 +37,9 @@ __device__ __forceinline__ double seq_sum_lds(const double* sq, int n) {
 // is not exactly true: a b_k of the column block is not finite (0 * inf is NaN), or the row's b_i is -0.0 (which -0.0 - (-0.0)
 // would turn into +0.0). The factors of a banded matrix (the heat equation's Jacobian) are zero almost everywhere, and the
 // reference's solve multiplies through all of it; so did this kernel, 134 MB per system and iteration at n = 4096.
+// A solve reads every entry of the factors once: tb::NT_SOLVE (exp_switches.hpp) marks the loads of the sweeps and, with 256
+// threads, of the diagonal blocks non-temporal. The staging loads of the diagonal blocks (T > 256, n >= 2048: 1/64 of a block
+// column) keep the default policy: no run has compared the two there.
 // dg (T > 256 only): 64 x 64 doubles of LDS for the diagonal block. With few, large systems per call a workgroup's life is
 // its 2 n / 64 diagonal solves, and each of those was eight dependent round trips to memory (eight columns loaded, eight
 // steps, ...): 17 us per block at n = 4096. The block a solve needs is instead fetched by all threads while the sweep before
@@ -95,7 +98,7 @@ __device__ __forceinline__ void wg_getrs(const double* __restrict__ LU, int n, d
                 for (int u = 0; u < UNR; ++u) {
                     const int k = k0 + u;
                     if (STAGE) l[u] = (k + 1 < kw && lane > k && lane < kw) ? dg[k * 64 + lane] : 0.0;
-                    else l[u] = buf_load_f64(rsrc, (k + 1 < kw && lane > k && lane < kw) ? (unsigned)i * 8u : OOB, __builtin_amdgcn_readfirstlane((kb + (k < kw ? k : kw - 1)) * n * 8));  // (groups past the block's end: every lane out of range anyway; the scalar offset stays inside the matrix)
+                    else l[u] = buf_load_f64<tb::NT_SOLVE>(rsrc, (k + 1 < kw && lane > k && lane < kw) ? (unsigned)i * 8u : OOB, __builtin_amdgcn_readfirstlane((kb + (k < kw ? k : kw - 1)) * n * 8));  // (groups past the block's end: every lane out of range anyway; the scalar offset stays inside the matrix)
                 }
             };
             auto fwd = [&](const int k0, const double (&l)[UNR]) {
@@ -147,11 +150,11 @@ __device__ __forceinline__ void wg_getrs(const double* __restrict__ LU, int n, d
                     for (int u = 0; u < UNR; ++u) {
                         const double* p = LU + (long)(kb + k + u) * n + i;
                         if constexpr (VEC == 2) {
-                            const double2 q = *reinterpret_cast<const double2*>(p);
+                            const double2 q = ld_f64x2<tb::NT_SOLVE>(p);
                             lv[u][0] = q.x;
                             lv[u][1] = q.y;
                         } else {
-                            lv[u][0] = *p;
+                            lv[u][0] = ld_f64<tb::NT_SOLVE>(p);
                         }
                     }
 #pragma unroll
@@ -184,7 +187,7 @@ __device__ __forceinline__ void wg_getrs(const double* __restrict__ LU, int n, d
                 for (int u = 0; u < UNR; ++u) {
                     const int k = k0 - u;
                     if (STAGE) uu[u] = (k >= 0 && lane <= k) ? dg[k * 64 + lane] : 1.0;
-                    else uu[u] = buf_load_f64(rsrc, (k >= 0 && lane <= k) ? (unsigned)i * 8u : OOB, __builtin_amdgcn_readfirstlane((kb + (k >= 0 ? k : 0)) * n * 8));  // (0.0 where 1.0 stood: never used)
+                    else uu[u] = buf_load_f64<tb::NT_SOLVE>(rsrc, (k >= 0 && lane <= k) ? (unsigned)i * 8u : OOB, __builtin_amdgcn_readfirstlane((kb + (k >= 0 ? k : 0)) * n * 8));  // (0.0 where 1.0 stood: never used)
                 }
             };
             auto bwd = [&](const int k0, const double (&uu)[UNR]) {
@@ -237,11 +240,11 @@ __device__ __forceinline__ void wg_getrs(const double* __restrict__ LU, int n, d
                         const int k = (k0 - u) >= 0 ? (k0 - u) : 0;
                         const double* p = LU + (long)(kb + k) * n + i;
                         if constexpr (VEC == 2) {
-                            const double2 q = *reinterpret_cast<const double2*>(p);
+                            const double2 q = ld_f64x2<tb::NT_SOLVE>(p);
                             uv[u][0] = q.x;
                             uv[u][1] = q.y;
                         } else {
-                            uv[u][0] = *p;
+                            uv[u][0] = ld_f64<tb::NT_SOLVE>(p);
                         }
                     }
 #pragma unroll
