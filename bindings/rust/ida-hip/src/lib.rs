@@ -211,6 +211,41 @@ impl Ctx {
         Ok(Ctx { raw, n, batch, callbacks: None, residual: None })
     }
 
+    /// A Krylov context (`idahip_create_krylov`): the matrix-free SPGMR solver of DESIGN.md section 4h, no matrix, no factors.
+    /// `Problem::Heat1D`, `Problem::LinearDense` or a host-callback problem (its residual alone), 8 < n <= 4096; `maxl` = 0 means 5,
+    /// at most 16 and at most n.
+    pub fn new_krylov(device: i32, n: usize, batch: usize, problem: Problem, maxl: usize) -> Result<Self, Error> {
+        let mut raw: *mut sys::idahip_ctx = ptr::null_mut();
+        let rc = unsafe { sys::idahip_create_krylov(&mut raw, device, n as c_int, batch as c_int, problem.code(), ptr::null_mut(), maxl as c_int) };
+        if rc != 0 || raw.is_null() {
+            return Err(Error::Library { code: rc, message: "idahip_create_krylov failed (kind, size or maxl refused, or no GPU)".to_string() });
+        }
+        Ok(Ctx { raw, n, batch, callbacks: None, residual: None })
+    }
+
+    /// `Some(maxl)` for a Krylov context.
+    pub fn krylov(&self) -> Option<usize> {
+        let mut maxl: c_int = 0;
+        if unsafe { sys::idahip_krylov(self.raw, &mut maxl) } == 1 {
+            Some(maxl as usize)
+        } else {
+            None
+        }
+    }
+
+    /// Krylov context, built-in problems: the whole solve in one launch (default) or one launch per step.
+    pub fn set_krylov_fused(&mut self, on: bool) -> Result<(), Error> {
+        let rc = unsafe { sys::idahip_set_krylov_fused(self.raw, on as c_int) };
+        if rc != 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(())
+    }
+
+    pub fn krylov_fused(&self) -> bool {
+        unsafe { sys::idahip_krylov_fused(self.raw) == 1 }
+    }
+
     pub fn n(&self) -> usize {
         self.n
     }
@@ -462,6 +497,114 @@ impl<D: DimName> Drop for HipDense<D> {
             sys::idahip_dev_free(raw, self.d_x as *mut c_void);
             sys::idahip_dev_free(raw, self.d_b as *mut c_void);
         }
+    }
+}
+
+/// `linear::LSolver` of type Iterative on the device: the matrix-free SPGMR solver of a Krylov context. It
+/// solves J x = b for J = dF/dy + cj dF/dy' at the context-resident yy, yp, savres and ewt of system 0 without ever forming J: the
+/// matrix handed to `setup` / `solve` is not read. `tn` and `cj` are the point the residual is perturbed at; `tol` is the solver's
+/// tolerance, as `idaLsSolve` passes it (src/ida_ls.rs:316-329).
+pub struct HipKrylov<D: DimName> {
+    ctx: Ctx,
+    pub tn: f64,
+    pub cj: f64,
+    flag: std::cell::Cell<i32>,
+    _dim: PhantomData<D>,
+}
+
+impl<D: DimName> HipKrylov<D> {
+    /// Around a Krylov context whose problem and state the caller has set up (batch = 1).
+    pub fn with_ctx(ctx: Ctx, tn: f64, cj: f64) -> Self {
+        assert!(ctx.krylov().is_some(), "HipKrylov needs a context made by Ctx::new_krylov");
+        HipKrylov { ctx, tn, cj, flag: std::cell::Cell::new(0), _dim: PhantomData }
+    }
+    pub fn ctx(&mut self) -> &mut Ctx {
+        &mut self.ctx
+    }
+    /// The flag of the last `solve`: 0 SUCCESS, 1 RES_REDUCED (a solution was formed, the tolerance was not reached), 2 CONV_FAIL,
+    /// 3 QRSOL_FAIL (for the last two no solution was formed and `x` is `b`). The trait's error type has no variant for a failed
+    /// iterative solve, so `solve` returns `Ok(())` for every flag and the caller reads it here, as `idaLsSolve` reads the
+    /// solver's return value (src/ida_ls.rs:413-415: any of 1, 2, 3 is a recoverable failure of the Newton iteration).
+    pub fn last_flag(&self) -> i32 {
+        self.flag.get()
+    }
+}
+
+impl<D> LSolver<f64, D> for HipKrylov<D>
+where
+    D: DimName,
+    DefaultAllocator: Allocator<f64, D> + Allocator<usize, D>,
+{
+    /// A host-callback Krylov context of one system with the default maxl. It has no residual yet: register one through
+    /// `ctx().set_host_residual(..)` and upload yy, yp, savres and ewt before the first `solve`, which otherwise panics with the
+    /// library's refusal text ("idahip_set_host_residual has not been called"), as every device failure of these solvers does.
+    fn new() -> Self {
+        let ctx = Ctx::new_krylov(0, D::dim(), 1, Problem::HostCallback, 0).expect("no MI355X visible, or n outside 8 < n <= 4096");
+        Self::with_ctx(ctx, 0.0, 0.0)
+    }
+
+    fn get_type(&self) -> LSolverType {
+        match unsafe { sys::idahip_ls_type(self.ctx.raw) } {
+            1 => LSolverType::Iterative,
+            2 => LSolverType::MatrixIterative,
+            _ => LSolverType::Direct,
+        }
+    }
+
+    /// The linear setup of a matrix-free solver forms and factors nothing and cannot fail.
+    fn setup<S>(&mut self, _mat_a: &mut Matrix<f64, D, D, S>) -> Result<(), linear::Error>
+    where
+        S: StorageMut<f64, D, D>,
+    {
+        Ok(())
+    }
+
+    fn solve<SA, SB, SC>(
+        &self,
+        _mat_a: &Matrix<f64, D, D, SA>,
+        x: &mut Matrix<f64, D, U1, SB>,
+        b: &Matrix<f64, D, U1, SC>,
+        tol: f64,
+    ) -> Result<(), linear::Error>
+    where
+        SA: StorageMut<f64, D, D>,
+        SB: StorageMut<f64, D>,
+        SC: StorageMut<f64, D>,
+    {
+        let n = D::dim();
+        let rhs: Vec<f64> = b.iter().copied().collect();
+        let mut out = vec![0.0f64; n];
+        let (idx, tn, cj, tl) = ([0i32], [self.tn], [self.cj], [tol]);
+        let (mut nli, mut flag, mut rn) = ([0i32], [0i32], [0.0f64]);
+        let rc = unsafe {
+            sys::idahip_krylov_solve(
+                self.ctx.raw,
+                tn.as_ptr(),
+                cj.as_ptr(),
+                tl.as_ptr(),
+                rhs.as_ptr(),
+                out.as_mut_ptr(),
+                nli.as_mut_ptr(),
+                flag.as_mut_ptr(),
+                rn.as_mut_ptr(),
+                idx.as_ptr(),
+                1,
+            )
+        };
+        assert!(rc >= 0, "{}", self.ctx.last_error());
+        self.flag.set(flag[0]);
+        for (dst, src) in x.iter_mut().zip(out.iter()) {
+            *dst = *src;
+        }
+        Ok(()) // whatever the flag: last_flag() tells a failed solve from a converged one
+    }
+
+    fn num_iters(&self) -> usize {
+        unsafe { sys::idahip_ls_num_iters(self.ctx.raw) as usize }
+    }
+
+    fn res_norm(&self) -> f64 {
+        unsafe { sys::idahip_ls_res_norm(self.ctx.raw) }
     }
 }
 

@@ -111,6 +111,18 @@ int idaens_set_root_fn(idaens* e, int nroots, idaens_root_fn fn, void* user);
  * Jacobians (C IDA flips the increments' signs there), and idaens_calc_ic on a ctx with constraints (C IDA's line search has a
  * constraint branch of its own). */
 
+/* A Krylov ctx (idahip_create_krylov: matrix-free SPGMR) under the stepper. The iterative branch of idaLsSolve
+ * (src/ida_ls.rs:316-418) runs:
+ *   - a system whose Newton solve asks for a linear setup gets its residual (idahip_nls_sys) and the setup's bookkeeping only --
+ *     nsetups += 1, cjold = cj, cjratio = 1, ss = 20, jcur = true; nothing is formed or factored, nothing can fail, nje stays 0;
+ *   - the Newton iteration is idahip_newton_iter_krylov, with the solver's tolerance (sqrt(N) * 0.05) * eps_newt; the correction is not
+ *     scaled by 2 / (1 + cjratio); IDAENS_C_NLI grows by the solve's iterations and IDAENS_C_NRE_DQ by as many residual evaluations;
+ *     any flag other than SUCCESS adds 1 to IDAENS_C_NCFL and is recoverable: the attempt takes Newton's ConvergenceRecover exit
+ *     (a retry with a setup when the setup's data were stale, else a convergence failure of the step, counted in ncfn);
+ *   - the fused first two Newton iterations are off (idaens_set_fused_newton changes nothing), idaens_device_controller_active reports 0:
+ *     the host stepper runs; idaens_calc_ic is refused (negative return with a text);
+ *   - solve, schedules, streams, groups, both tasks and root finding never touch the linear solver and work unchanged. */
+
 /* Consistent initial conditions for every system: C IDA's IDACalcIC (the reference has none, src/lib.rs:328-335), as DESIGN.md
  * section 4f defines it -- no constraints, sysindex = 1, line search always on.
  *   IDAENS_YA_YDP_INIT: given the differential components of y0 (idahip_set_id: id_i = 1), compute the algebraic components of y0

@@ -96,6 +96,61 @@ int idahip_download_lu_band(idahip_ctx* ctx, int sys, double* hAB, int64_t* hPiv
 int idahip_ls_setup_band(idahip_ctx* ctx, int ml, int mu, double* dAB, int64_t* dPiv, int32_t* hInfo, const int32_t* hIdx, int nsys);
 int idahip_ls_solve_band(idahip_ctx* ctx, int ml, int mu, const double* dAB, const int64_t* dPiv, double* dX, const double* dB, double tol,
                          const int32_t* hIdx, int nsys);
+/* ---- A KRYLOV ctx: matrix-free SPGMR behind the iterative branch of idaLsSolve (the reference has no iterative solver; this text and
+ * DESIGN.md section 4h are the definition). C IDA's default iterative setup: SPGMR, no preconditioner, scaling by ewt on both sides,
+ * modified Gram-Schmidt, maxl = 5, no restarts, J v by a difference quotient of the residual (idaLsDQJtimes). The ctx holds no work
+ * matrix, no factors and no pivots: memory per system is O(maxl n) instead of O(n^2). Kinds IDAHIP_HEAT1D, IDAHIP_LINEAR_DENSE (the
+ * problem's own A and B remain) and IDAHIP_HOST_CALLBACK (idahip_set_host_residual: there is no Jacobian to ask for); 8 < n <= 4096;
+ * maxl = 0 means 5; maxl > 16 or maxl > n is refused (-2).
+ *
+ * Inner product kdot(x, y): p_i = x_i*y_i; partial q (q = 0..63) is the left-to-right sum of p_q, p_{q+64}, p_{q+128}, ... from +0.0;
+ * the result is the left-to-right sum of the 64 partials from +0.0 (partials without an element are +0.0).
+ *
+ * The solve of one system. In: b, w = ewt, the current yy, yp, rr = savres (the residual there, as idahip_nls_sys leaves it), tn, cj,
+ * tol = (sqrt(n) * 0.05) * eps_newt (C IDA's eplin). No FMA; 1/x is a true division; |.| is fabs.
+ *   1. V0_i = w_i*b_i; beta = sqrt(kdot(V0, V0)). beta <= tol: nli = 0, flag SUCCESS, res_norm = beta, x = b unchanged.
+ *   2. V0_i = V0_i*(1/beta); rot = 1.0; H (17 x 16) all zero.
+ *   3. l = 0 .. maxl-1, nli += 1 at the top:
+ *        z_i = V_l,i / w_i;  sig = sqrt(n)*1.0;  y'_i = sig*z_i + yy_i;  yp'_i = (cj*sig)*z_i + yp_i;
+ *        F' = F(tn, y', yp'), a full residual evaluation in the residual kernel's own operation order;
+ *        Jv_i = (1/sig)*(F'_i - rr_i);  V_{l+1},i = w_i*Jv_i;
+ *        modified Gram-Schmidt: i = 0..l: H[i][l] = kdot(V_i, V_{l+1}), then V_{l+1} = V_{l+1} - H[i][l]*V_i;
+ *        hn = H[l+1][l] = sqrt(kdot(V_{l+1}, V_{l+1}))   (SUNDIALS' rare re-orthogonalisation pass is left out);
+ *        earlier rotations, k = 0..l-1, c = q[2k], s = q[2k+1], t1 = H[k][l], t2 = H[k+1][l]:
+ *          H[k][l] = c*t1 - s*t2;  H[k+1][l] = s*t1 + c*t2;
+ *        new rotation from t1 = H[l][l], t2 = H[l+1][l]:  t2 == 0: c = 1, s = 0;
+ *          |t2| >= |t1|: t3 = t1/t2, s = -1/sqrt(1 + t3*t3), c = -s*t3;  otherwise: t3 = t2/t1, c = 1/sqrt(1 + t3*t3), s = -c*t3;
+ *        q[2l] = c; q[2l+1] = s; H[l][l] = c*t1 - s*t2 (H[l+1][l] keeps hn);
+ *        rot = rot*s; rho = |rot*beta|; res_norm = rho; rho <= tol: converged, krydim = l+1, leave the loop;
+ *        otherwise V_{l+1},i = V_{l+1},i*(1/hn).
+ *   4. no convergence: krydim = maxl; !(rho < beta): flag CONV_FAIL, no solution is formed; otherwise RES_REDUCED.
+ *   5. SUCCESS and RES_REDUCED: g = [beta, 0, ...]; the rotations k = 0..krydim-1 applied to g (same two-line form); back-substitution
+ *      k = krydim-1 .. 0: H[k][k] == 0: flag QRSOL_FAIL, stop; g[k] = g[k]/H[k][k]; i < k: g[i] = g[i] - g[k]*H[i][k];
+ *      xc = g[0]*V0, then xc = xc + g[k]*V_k for ascending k; x_i = xc_i/w_i.
+ * Flags: 0 SUCCESS, 1 RES_REDUCED, 2 CONV_FAIL, 3 QRSOL_FAIL. The loop is bounded by maxl whatever the data.
+ *
+ * Built-in kinds run the whole solve of a listed system in ONE launch (one workgroup per system; the basis [batch][maxl+1][n] stays in
+ * L2); idahip_set_krylov_fused(ctx, 0) runs the same device functions one launch per step with the host looping over l -- how a
+ * host-callback residual runs (always; the switch is 0 there and cannot be set), and the cross-check of the fused kernel.
+ * On a Krylov ctx idahip_ls_type is IDAHIP_LS_ITERATIVE, idahip_ls_num_iters the sum and idahip_ls_res_norm the maximum over the
+ * listed systems of the last solve call. Refused with -2: idahip_ls_setup (no dense work matrices), idahip_nls_lsetup*, idahip_nls_sys_setup, idahip_newton_iter,
+ * idahip_newton_iter2, idahip_download_lu*, idahip_set_jacobian_dq(1), idahip_set_constraints, idahip_set_host_problem,
+ * idahip_ic_*, idahip_round_solve. */
+int idahip_create_krylov(idahip_ctx** ctx, int device, int n, int batch, idahip_problem kind, void* hip_stream, int maxl);
+/* 1 for a Krylov ctx (*maxl set when non-null), 0 otherwise, -1 for a null ctx */
+int idahip_krylov(const idahip_ctx* ctx, int* maxl);
+int idahip_set_krylov_fused(idahip_ctx* ctx, int on);
+int idahip_krylov_fused(const idahip_ctx* ctx); /* 1 fused (the default for built-in kinds), 0 split */
+/* The solve of the definition for the listed systems at the ctx-resident yy, yp, savres, ewt: hB, hX host arrays [nsys][n] by list
+ * position; hTol, hNli, hFlag, hResNorm [nsys]. The stand-alone LSolver::solve. Returns 1 if some flag is not SUCCESS. */
+int idahip_krylov_solve(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hTol, const double* hB, double* hX,
+                        int32_t* hNli, int32_t* hFlag, double* hResNorm, const int32_t* hIdx, int nsys);
+/* The Newton loop body on a Krylov ctx: delta = -delta; the solve with b = delta and tol = (sqrt(n)*0.05)*hEpsNewt[s]; flag SUCCESS:
+ * delta = x, ee += delta, hDelnrm[s] = ||delta||_wrms(ewt) summed left to right as everywhere else; any other flag: ee is untouched,
+ * delta keeps the negated residual, hDelnrm[s] = 0. The correction is not scaled by 2/(1+cjratio) (src/ida_ls.rs:405-410).
+ * Returns 1 if some flag is not SUCCESS (recoverable: Newton's ConvergenceRecover exit). */
+int idahip_newton_iter_krylov(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hEpsNewt, double* hDelnrm,
+                              int32_t* hNli, int32_t* hFlag, const int32_t* hIdx, int nsys);
 /* `count` HIP streams on `device` for contexts that are to work SIDE BY SIDE (idaens_stream_group, ida_ensemble.h). The HIP
  * runtime maps its streams onto a few hardware queues as it sees fit, and two streams on one queue take turns; this call
  * creates streams and keeps those a probe kernel shows to run concurrently with every stream kept before. streams_out[count]

@@ -77,6 +77,16 @@ struct idahip_ctx {
     // (band_kernels.hpp), factored in place; piv is shared with the dense mode. lu, jw and the dense LU's workspace are not allocated.
     int band = 0, ml = 0, mu = 0, ldab = 0;
     double* bab = nullptr;
+    // Krylov mode (idahip_create_krylov, krylov_kernels.hpp): matrix-free SPGMR; no work matrix, no factors, no pivots are allocated
+    int krylov = 0, kry_maxl = 0;
+    int kry_fused = 1;          // the whole solve in one launch (built-in kinds); 0: one launch per step, the host loops
+    double* kry_V = nullptr;    // [batch][kry_maxl + 1][n] Krylov basis
+    void* kry_st = nullptr;     // [batch] idakry::Sys (split path)
+    double* kry_stage = nullptr;  // [batch][3][n] perturbed point and its residual (split path)
+    double *kry_b = nullptr, *kry_x = nullptr;  // [batch][n] right-hand sides and solutions of idahip_krylov_solve, by list position
+    std::vector<double> kry_host;               // host mirror of kry_stage (host-callback residuals)
+    int kry_last_nli = 0;            // sum of the iterations / maximum of the residual norms over the last solve call's list
+    double kry_last_resnorm = 0.0;
     double *ic_y = nullptr, *ic_yp = nullptr;  // [batch][n] initial conditions kept for idahip_restore_initial (lazy)
     double* dky = nullptr;                     // [batch][n] result buffer of idahip_get_dky (lazy)
     int lu_variant = 4;  // 4: one wave per matrix factors each 64-column super-panel (lu_wavepanel.hpp, default)

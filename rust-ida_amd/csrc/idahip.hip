@@ -8,6 +8,7 @@
 #include "dq_kernels.hpp"
 #include "vector_kernels.hpp"
 #include "ic_kernels.hpp"
+#include "krylov_kernels.hpp"
 #include "tiny_ida.hpp"
 #include "round_ida.hpp"
 
@@ -104,7 +105,7 @@ int band_factor(idahip_ctx* c, double* dAB, long sstride, int64_t* dPiv, long ps
     return post_launch(c, "band_getrf");
 }
 
-int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, bool band, int ml, int mu) {
+int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, bool band, int ml, int mu, int krylov_maxl = 0) {
     if (!out) return -1;
     *out = nullptr;
     if (n < 1 || batch < 1) return -2;
@@ -115,6 +116,11 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     if (band) {
         c->band = 1; c->ml = ml; c->mu = mu; c->ldab = 2 * ml + mu + 1;
     }
+    if (krylov_maxl > 0) {
+        c->krylov = 1; c->kry_maxl = krylov_maxl;
+        c->kry_fused = kind == IDAHIP_HOST_CALLBACK ? 0 : 1;
+    }
+    const bool nomat = band || krylov_maxl > 0;  // no n x n storage
     c->npad16 = (n + 15) & ~15;
     c->list_seen.assign(((size_t)batch + 63) / 64, 0);
     c->lu_superpanel = kind == IDAHIP_HEAT1D ? 1 : 0;
@@ -142,20 +148,27 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     rc |= dalloc(c, &c->yy, bn); rc |= dalloc(c, &c->yp, bn); rc |= dalloc(c, &c->yypredict, bn); rc |= dalloc(c, &c->yppredict, bn);
     rc |= dalloc(c, &c->ewt, bn); rc |= dalloc(c, &c->ee, bn); rc |= dalloc(c, &c->delta, bn); rc |= dalloc(c, &c->savres, bn);
     rc |= dalloc(c, &c->phi, (size_t)MXORDP1 * bn);
-    rc |= dalloc(c, &c->piv, bn); rc |= dalloc(c, &c->perm, bn);
-    rc |= dalloc(c, &c->lu_info, (size_t)batch);
-    rc |= dalloc(c, &c->lu_redo, (size_t)batch);
-    rc |= dalloc(c, &c->lu_nzb, (size_t)batch);
+    if (!krylov_maxl) { rc |= dalloc(c, &c->piv, bn); rc |= dalloc(c, &c->perm, bn); }  // a Krylov ctx has no pivots
+    rc |= dalloc(c, &c->lu_info, (size_t)batch);  // (also the band calls on caller-owned buffers report through it, on any ctx)
+    if (!krylov_maxl) { rc |= dalloc(c, &c->lu_redo, (size_t)batch); rc |= dalloc(c, &c->lu_nzb, (size_t)batch); }
     if (band) rc |= dalloc(c, &c->bab, bn * c->ldab);  // instead of every n x n buffer below
-    if (!band) rc |= dalloc(c, &c->lu, bnn);
-    if (!band && n > LU_MAX_N) rc |= dalloc(c, &c->lu_bz, (size_t)batch * 64);
-    if (!band && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_zmap, (size_t)batch * 4096);
-    if (!band && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_dirty, (size_t)batch * 4096);
-    if (!band && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_jwzero, (size_t)batch);
-    if (!band && n > TINY_N) {
+    if (!nomat) rc |= dalloc(c, &c->lu, bnn);
+    if (!nomat && n > LU_MAX_N) rc |= dalloc(c, &c->lu_bz, (size_t)batch * 64);
+    if (!nomat && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_zmap, (size_t)batch * 4096);
+    if (!nomat && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_dirty, (size_t)batch * 4096);
+    if (!nomat && n >= LU_ZMAP_MIN_N) rc |= dalloc(c, &c->lu_jwzero, (size_t)batch);
+    if (!nomat && n > TINY_N) {
         rc |= dalloc(c, &c->jw, bnn);
         rc |= dalloc(c, &c->lu_pos, bn); rc |= dalloc(c, &c->lu_live, bn); rc |= dalloc(c, &c->lu_prow, bn);
         rc |= dalloc(c, &c->lu_l11, (size_t)batch * L11_STRIDE);
+    }
+    if (krylov_maxl > 0) {
+        idakry::Sys* st = nullptr;
+        rc |= dalloc(c, &c->kry_V, bn * (size_t)(krylov_maxl + 1));
+        rc |= dalloc(c, &st, (size_t)batch);
+        c->kry_st = st;
+        rc |= dalloc(c, &c->kry_stage, 3 * bn);
+        rc |= dalloc(c, &c->kry_b, bn); rc |= dalloc(c, &c->kry_x, bn);
     }
     if (kind == IDAHIP_LINEAR_DENSE) {
         rc |= dalloc(c, &c->A, bnn); rc |= dalloc(c, &c->B, bnn); rc |= dalloc(c, &c->C, bn);
@@ -183,9 +196,9 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     (void)hipMemsetAsync(c->phi, 0, (size_t)MXORDP1 * bn * sizeof(double), c->stream);
     (void)hipMemsetAsync(c->lu_info, 0, (size_t)batch * sizeof(int), c->stream);
     // pivots and row permutation in range before the first setup: a Newton iteration or solve ahead of it gathers rows by them
-    (void)hipMemsetAsync(c->piv, 0, bn * sizeof(int64_t), c->stream);
-    (void)hipMemsetAsync(c->perm, 0, bn * sizeof(int32_t), c->stream);
-    (void)hipMemsetAsync(c->lu_redo, 0, (size_t)batch * sizeof(int), c->stream);
+    if (c->piv) (void)hipMemsetAsync(c->piv, 0, bn * sizeof(int64_t), c->stream);
+    if (c->perm) (void)hipMemsetAsync(c->perm, 0, bn * sizeof(int32_t), c->stream);
+    if (c->lu_redo) (void)hipMemsetAsync(c->lu_redo, 0, (size_t)batch * sizeof(int), c->stream);
     if (c->bab) (void)hipMemsetAsync(c->bab, 0, bn * c->ldab * sizeof(double), c->stream);
     if (c->lu_dirty) {  // the factors start as zeros, and so does the map of their blocks that have ever held anything else
         (void)hipMemsetAsync(c->lu, 0, bnn * sizeof(double), c->stream);
@@ -236,7 +249,7 @@ int idahip_destroy(idahip_ctx* c) {
     DevGuard dev_guard__(c);
     if (!c) return 0;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* ptrs[] = {c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
+    void* ptrs[] = {c->kry_V, c->kry_st, c->kry_stage, c->kry_b, c->kry_x, c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
                     c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->d_constr, c->ic_y,
                     c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d};
@@ -433,6 +446,7 @@ int idahip_id(const idahip_ctx* c, double* hId) {
 }
 
 int idahip_set_constraints(idahip_ctx* c, const double* hC) {
+    if (c && c->krylov) return fail(c, -2, "idahip_set_constraints on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (!hC) {
@@ -478,6 +492,7 @@ int idahip_set_linear_dense(idahip_ctx* c, int first, int count, const double* h
 }
 
 int idahip_set_host_problem(idahip_ctx* c, idahip_res_fn res, idahip_jac_fn jac, void* user) {
+    if (c && c->krylov) return fail(c, -2, "idahip_set_host_problem on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     if (!c || !res || !jac) return -1;
     if (c->kind != IDAHIP_HOST_CALLBACK) return fail(c, -2, "not an IDAHIP_HOST_CALLBACK ctx");
     if (c->band) return fail(c, -2, "a band ctx takes a band Jacobian: idahip_set_host_band_problem");
@@ -496,12 +511,14 @@ int idahip_set_host_residual(idahip_ctx* c, idahip_res_fn res, void* user) {
     c->cb_jac = nullptr;
     c->cb_bjac = nullptr;
     c->cb_user = user;
+    if (c->krylov) return 0;  // no Jacobian to ask for: the residual is all a Krylov ctx takes
     c->jac_dq = 1;
     c->dq_locked = 1;
     return 0;
 }
 
 int idahip_set_host_band_problem(idahip_ctx* c, idahip_res_fn res, idahip_band_jac_fn bjac, void* user) {
+    if (c && c->krylov) return fail(c, -2, "idahip_set_host_band_problem on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     if (!c || !res || !bjac) return -1;
     if (c->kind != IDAHIP_HOST_CALLBACK) return fail(c, -2, "not an IDAHIP_HOST_CALLBACK ctx");
     if (!c->band) return fail(c, -2, "a dense ctx takes a dense Jacobian: idahip_set_host_problem");
@@ -536,6 +553,7 @@ int idahip_download(idahip_ctx* c, idahip_field f, int first, int count, double*
 }
 
 int idahip_download_lu(idahip_ctx* c, int sys, double* hLU, int64_t* hPiv) {
+    if (c && c->krylov) return fail(c, -2, "idahip_download_lu on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
@@ -548,6 +566,7 @@ int idahip_download_lu(idahip_ctx* c, int sys, double* hLU, int64_t* hPiv) {
 }
 
 int idahip_download_lu_band(idahip_ctx* c, int sys, double* hAB, int64_t* hPiv) {
+    if (c && c->krylov) return fail(c, -2, "idahip_download_lu_band on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
@@ -594,6 +613,7 @@ int idahip_ls_setup(idahip_ctx* c, double* dA, int64_t* dPiv, int32_t* hInfo, co
     if (rc) return rc;
     if (!dA || !dPiv || !hInfo) return fail(c, -2, "null argument");
     if (c->band) return fail(c, -2, "idahip_ls_setup on a band ctx (no dense work matrices): idahip_ls_setup_band");
+    if (c->krylov) return fail(c, -2, "idahip_ls_setup on a Krylov ctx (idahip_create_krylov): it holds no dense work matrices");
     if (nsys == 0) return 0;
     const int n = c->n;
     const long nn = (long)n * n;
@@ -748,7 +768,7 @@ namespace {
 // (ic: the same round trip with the IC front end, idahip_ic_res / idahip_ic_trial)
 int callback_sys(idahip_ctx* c, const SysArgs& a, const double* hTn, const int32_t* hIdx, int nsys, const SysArgsIC* ic = nullptr) {
     const int n = c->n;
-    if (!c->cb_res || !(c->cb_jac || c->cb_bjac || c->dq_locked))
+    if (!c->cb_res || !(c->cb_jac || c->cb_bjac || c->dq_locked || c->krylov))
         return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_problem has not been called");
     const size_t cnt = (size_t)nsys * 3 * n;
     if (ic) hipLaunchKernelGGL(ic_callback_pre_kernel, dim3(nsys), dim3(256), 0, c->stream, *ic, c->cb_stage);
@@ -1058,6 +1078,7 @@ int idahip_nls_sys(idahip_ctx* c, const double* hTn, const double* hCj, int rese
 }
 
 int idahip_nls_lsetup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_nls_lsetup on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1080,6 +1101,7 @@ int idahip_nls_lsetup(idahip_ctx* c, const double* hTn, const double* hCj, int32
 
 int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, int reset_ee, int32_t* hInfo, const int32_t* hIdx,
                          int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_nls_sys_setup on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1111,6 +1133,7 @@ int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, in
 
 int idahip_nls_lsetup_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx,
                          int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_nls_lsetup_dq on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1162,6 +1185,7 @@ int idahip_jac_dq(idahip_ctx* c, const double* hTn, const double* hCj, const dou
 int idahip_set_jacobian_dq(idahip_ctx* c, int on) {
     if (!c) return -1;
     if (!on && c->dq_locked) return fail(c, -2, "the ctx has a residual and no Jacobian (idahip_set_host_residual): DQ stays on");
+    if (on && c->krylov) return fail(c, -2, "idahip_set_jacobian_dq on a Krylov ctx (idahip_create_krylov): it forms no Jacobian");
     c->jac_dq = on ? 1 : 0;
     return 0;
 }
@@ -1197,6 +1221,7 @@ static int launch_newton_iter(idahip_ctx* c, const int* d_idx, const double* d_s
 }
 
 int idahip_newton_iter(idahip_ctx* c, const double* hScale, double* hDelnrm, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_newton_iter on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1222,6 +1247,7 @@ int idahip_newton_iter(idahip_ctx* c, const double* hScale, double* hDelnrm, con
 
 int idahip_newton_iter2(idahip_ctx* c, const double* hScale, const double* hTn, const double* hCj, const double* hToldel, const double* hSs,
                         const double* hEpsNewt, double* hDelnrm, int32_t* hConv, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_newton_iter2 on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1274,6 +1300,181 @@ int idahip_newton_iter2(idahip_ctx* c, const double* hScale, const double* hTn, 
 }
 
 int idahip_kind(const idahip_ctx* c) { return c ? (int)c->kind : -1; }
+
+// ------------------------------------------------------------------------------------------------ Krylov ctx (krylov_kernels.hpp)
+int idahip_create_krylov(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, int maxl) {
+    if (!out) return -1;
+    *out = nullptr;
+    if (kind != IDAHIP_HEAT1D && kind != IDAHIP_LINEAR_DENSE && kind != IDAHIP_HOST_CALLBACK) {
+        std::fprintf(stderr, "idahip_create_krylov: problem kind %d (IDAHIP_HEAT1D, IDAHIP_LINEAR_DENSE or IDAHIP_HOST_CALLBACK)\n", (int)kind);
+        return -2;
+    }
+    if (n <= TINY_N || n > LU_BIG_MAX_N) {
+        std::fprintf(stderr, "idahip_create_krylov: n = %d outside %d < n <= %d\n", n, TINY_N, LU_BIG_MAX_N);
+        return -2;
+    }
+    if (maxl == 0) maxl = idakry::MAXL_DEFAULT;
+    if (maxl < 1 || maxl > idakry::MAXL_MAX || maxl > n) {
+        std::fprintf(stderr, "idahip_create_krylov: maxl = %d outside 1 <= maxl <= min(%d, n)\n", maxl, idakry::MAXL_MAX);
+        return -2;
+    }
+    return create_ctx(out, device, n, batch, kind, hip_stream, false, 0, 0, maxl);
+}
+
+int idahip_krylov(const idahip_ctx* c, int* maxl) {
+    if (!c) return -1;
+    if (c->krylov && maxl) *maxl = c->kry_maxl;
+    return c->krylov;
+}
+
+int idahip_set_krylov_fused(idahip_ctx* c, int on) {
+    if (!c) return -1;
+    if (!c->krylov) return fail(c, -2, "idahip_set_krylov_fused: not a Krylov ctx (idahip_create_krylov)");
+    if (on && c->kind == IDAHIP_HOST_CALLBACK) return fail(c, -2, "a host-callback residual runs on the host: the split path only");
+    c->kry_fused = on ? 1 : 0;
+    return 0;
+}
+
+int idahip_krylov_fused(const idahip_ctx* c) { return c ? (c->krylov ? c->kry_fused : 0) : -1; }
+
+namespace {
+
+// the solve of the listed systems, fused or split; a.idx / cj / tol / results point into `ap`'s slot, already uploaded
+int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* hIdx, int nsys) {
+    const int n = c->n;
+    a.yy = c->yy; a.yp = c->yp; a.ewt = c->ewt; a.rr = c->savres;
+    a.V = c->kry_V; a.st = (idakry::Sys*)c->kry_st; a.stage = c->kry_stage;
+    a.delta = c->delta; a.ee = c->ee;
+    a.n = n; a.maxl = c->kry_maxl;
+    a.params = c->params; a.A = c->A; a.Bm = c->B; a.C = c->C;
+    a.skip = nullptr;
+    const dim3 grid(nsys), blk(KRY_T);
+    if (c->kry_fused) {
+        const size_t shm = kry_lds_bytes(n, 3);
+        if (c->kind == IDAHIP_HEAT1D) hipLaunchKernelGGL(krylov_fused_kernel<IDAHIP_HEAT1D>, grid, blk, shm, c->stream, a);
+        else if (c->kind == IDAHIP_LINEAR_DENSE) hipLaunchKernelGGL(krylov_fused_kernel<IDAHIP_LINEAR_DENSE>, grid, blk, shm, c->stream, a);
+        else return fail(c, -2, "no fused Krylov kernel for problem kind %d", (int)c->kind);
+        return post_launch(c, "krylov_fused");
+    }
+    if (c->kind == IDAHIP_HOST_CALLBACK && !c->cb_res) return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_residual has not been called");
+    const size_t shm1 = kry_lds_bytes(n, 1);
+    std::vector<int> done((size_t)nsys, 0);
+    auto fetch_done = [&]() -> int {
+        IDAHIP_HIP(c, hipMemcpyAsync(done.data(), a.done, sizeof(int) * nsys, hipMemcpyDeviceToHost, c->stream));
+        IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+        return 0;
+    };
+    int rc;
+    hipLaunchKernelGGL(krylov_begin_kernel, grid, blk, shm1, c->stream, a);
+    if ((rc = post_launch(c, "krylov_begin"))) return rc;
+    if ((rc = fetch_done())) return rc;
+    a.skip = a.done;  // a system whose loop has ended is left alone by the launches that follow
+    for (int l = 0; l < c->kry_maxl; ++l) {
+        bool any = false;
+        for (int s = 0; s < nsys; ++s) any = any || done[s] == 0;
+        if (!any) break;
+        hipLaunchKernelGGL(krylov_point_kernel, grid, blk, 0, c->stream, a, l);
+        if (c->kind == IDAHIP_HOST_CALLBACK) {  // the user's residual, exactly as idahip_nls_sys calls it
+            const size_t cnt = (size_t)nsys * 3 * n;
+            if (c->kry_host.size() < cnt) c->kry_host.resize(cnt);
+            double* h = c->kry_host.data();
+            IDAHIP_HIP(c, hipMemcpyAsync(h, c->kry_stage, sizeof(double) * cnt, hipMemcpyDeviceToHost, c->stream));
+            IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+            for (int s = 0; s < nsys; ++s) {
+                if (done[s]) continue;
+                double* hs = h + (size_t)s * 3 * n;
+                if (c->cb_res(hIdx[s], hTn[s], hs, hs + n, hs + 2 * n, c->cb_user) != 0)
+                    return fail(c, -7, "the user's residual function failed for system %d", hIdx[s]);
+            }
+            IDAHIP_HIP(c, hipMemcpyAsync(c->kry_stage, h, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
+        } else if (c->kind == IDAHIP_HEAT1D) {
+            hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_HEAT1D>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
+        } else {
+            hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_LINEAR_DENSE>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
+        }
+        hipLaunchKernelGGL(krylov_step_kernel, grid, blk, shm1, c->stream, a, l);
+        if ((rc = post_launch(c, "krylov_step"))) return rc;
+        if ((rc = fetch_done())) return rc;
+    }
+    hipLaunchKernelGGL(krylov_finish_kernel, grid, blk, shm1, c->stream, a);
+    return post_launch(c, "krylov_finish");
+}
+
+int krylov_call(idahip_ctx* c, bool newton, const double* hTn, const double* hCj, const double* hTol, const double* hB, double* hX,
+                double* hDelnrm, int32_t* hNli, int32_t* hFlag, double* hResNorm, const int32_t* hIdx, int nsys) {
+    const int n = c->n;
+    ArgPack ap;
+    int rc;
+    if ((rc = ap.begin(c))) return rc;
+    KryArgs a{};
+    a.idx = ap.in(hIdx, nsys);
+    a.cj = ap.in(hCj, nsys);
+    a.tol = ap.in(hTol, nsys);
+    a.nli = ap.out<int>(nsys);
+    a.flag = ap.out<int>(nsys);
+    a.resnorm = ap.out<double>(nsys);
+    a.nrm = ap.out<double>(nsys);
+    a.done = ap.out<int>(nsys);
+    if ((rc = ap.ok())) return rc;
+    if ((rc = ap.upload())) return rc;
+    a.newton = newton ? 1 : 0;
+    a.b = c->kry_b;
+    a.x = c->kry_x;
+    if (!newton) IDAHIP_HIP(c, hipMemcpyAsync(c->kry_b, hB, sizeof(double) * nsys * n, hipMemcpyHostToDevice, c->stream));
+    {
+        KTimer kt(c, newton ? IDAHIP_K_NEWTON_ITER : IDAHIP_K_SOLVE, nsys);
+        if ((rc = krylov_launch(c, a, hTn, hIdx, nsys))) return rc;
+    }
+    if ((rc = ap.fetch())) return rc;
+    if (!newton) {
+        IDAHIP_HIP(c, hipMemcpyAsync(hX, c->kry_x, sizeof(double) * nsys * n, hipMemcpyDeviceToHost, c->stream));
+        IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    const int* hn = ap.host_of((const int*)a.nli);
+    const int* hf = ap.host_of((const int*)a.flag);
+    const double* hr = ap.host_of((const double*)a.resnorm);
+    const double* hs = ap.host_of((const double*)a.nrm);
+    int any = 0, sum = 0;
+    double worst = 0.0;
+    for (int s = 0; s < nsys; ++s) {
+        hNli[s] = hn[s];
+        hFlag[s] = hf[s];
+        if (hResNorm) hResNorm[s] = hr[s];
+        if (newton) hDelnrm[s] = hf[s] == 0 ? sqrt(hs[s] / (double)n) : 0.0;
+        if (hf[s] != 0) any = 1;
+        sum += hn[s];
+        if (hr[s] > worst) worst = hr[s];
+    }
+    c->kry_last_nli = sum;
+    c->kry_last_resnorm = worst;
+    return any;
+}
+
+}  // namespace
+
+int idahip_krylov_solve(idahip_ctx* c, const double* hTn, const double* hCj, const double* hTol, const double* hB, double* hX, int32_t* hNli,
+                        int32_t* hFlag, double* hResNorm, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!c->krylov) return fail(c, -2, "idahip_krylov_solve: not a Krylov ctx (idahip_create_krylov)");
+    if (!hTn || !hCj || !hTol || !hB || !hX || !hNli || !hFlag || !hResNorm) return fail(c, -2, "null argument");
+    if (nsys == 0) return 0;
+    return krylov_call(c, false, hTn, hCj, hTol, hB, hX, nullptr, hNli, hFlag, hResNorm, hIdx, nsys);
+}
+
+int idahip_newton_iter_krylov(idahip_ctx* c, const double* hTn, const double* hCj, const double* hEpsNewt, double* hDelnrm, int32_t* hNli,
+                              int32_t* hFlag, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!c->krylov) return fail(c, -2, "idahip_newton_iter_krylov: not a Krylov ctx (idahip_create_krylov)");
+    if (!hTn || !hCj || !hEpsNewt || !hDelnrm || !hNli || !hFlag) return fail(c, -2, "null argument");
+    if (nsys == 0) return 0;
+    std::vector<double> tol((size_t)nsys);
+    for (int s = 0; s < nsys; ++s) tol[s] = idakry::tolerance(c->n, hEpsNewt[s]);
+    return krylov_call(c, true, hTn, hCj, tol.data(), nullptr, nullptr, hDelnrm, hNli, hFlag, nullptr, hIdx, nsys);
+}
 
 // ------------------------------------------------------------------------------------------------ stepper vector ops
 int idahip_init_first(idahip_ctx* c, double* hYpnorm, double* hPhi0Nrm, const int32_t* hIdx, int nsys) {
@@ -1692,6 +1893,7 @@ int ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, const double* 
 }  // namespace
 
 int idahip_ic_begin(idahip_ctx* c, double* hYpnorm, int32_t* hEwtBad, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_begin on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1720,6 +1922,7 @@ int idahip_ic_begin(idahip_ctx* c, double* hYpnorm, int32_t* hEwtBad, const int3
 }
 
 int idahip_ic_reset(idahip_ctx* c, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_reset on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1737,6 +1940,7 @@ int idahip_ic_reset(idahip_ctx* c, const int32_t* hIdx, int nsys) {
 }
 
 int idahip_ic_res(idahip_ctx* c, const double* hTn, const double* hCj, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_res on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1758,6 +1962,7 @@ int idahip_ic_res(idahip_ctx* c, const double* hTn, const double* hCj, const int
 }
 
 int idahip_ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_setup on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1768,6 +1973,7 @@ int idahip_ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t
 }
 
 int idahip_ic_setup_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_setup_dq on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1778,6 +1984,7 @@ int idahip_ic_setup_dq(idahip_ctx* c, const double* hTn, const double* hCj, cons
 }
 
 int idahip_ic_solve(idahip_ctx* c, double* hFnorm, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_solve on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1801,6 +2008,7 @@ int idahip_ic_solve(idahip_ctx* c, double* hFnorm, const int32_t* hIdx, int nsys
 
 int idahip_ic_trial(idahip_ctx* c, int icopt, const double* hTn, const double* hCj, const double* hLambda, double* hFnormp,
                     const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_trial on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1837,6 +2045,7 @@ int idahip_ic_trial(idahip_ctx* c, int icopt, const double* hTn, const double* h
 }
 
 int idahip_ic_accept(idahip_ctx* c, int icopt, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_accept on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -1855,6 +2064,7 @@ int idahip_ic_accept(idahip_ctx* c, int icopt, const int32_t* hIdx, int nsys) {
 }
 
 int idahip_ic_commit(idahip_ctx* c, int32_t* hEwtBad, const int32_t* hIdx, int nsys) {
+    if (c && c->krylov) return fail(c, -2, "idahip_ic_commit on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
@@ -2047,6 +2257,7 @@ static int stepper_buffers(idahip_ctx* c, const idahip_tiny_call* call, bool out
 
 int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc,
                        double* hYout, double* hYPout, int64_t* rounds_run) {
+    if (c && c->krylov) return fail(c, -2, "idahip_round_solve on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (!hSys || !call || !hRoundsDone || !hAcc || !rounds_run || !call->touts || call->ntout < 1) return fail(c, -2, "null argument");
@@ -2218,9 +2429,9 @@ int idahip_set_lu_period(idahip_ctx* c, int rounds) {
 int idahip_lu_period(const idahip_ctx* c) { return c ? c->lu_period : -1; }
 
 // LSolver::get_type / num_iters / res_norm of the dense direct solver (crates/linear/src/dense.rs:30-36, traits.rs:82-90)
-int idahip_ls_type(const idahip_ctx* c) { return c ? IDAHIP_LS_DIRECT : -1; }
-int idahip_ls_num_iters(const idahip_ctx* c) { return c ? 0 : -1; }
-double idahip_ls_res_norm(const idahip_ctx* c) { (void)c; return 0.0; }
+int idahip_ls_type(const idahip_ctx* c) { return c ? (c->krylov ? IDAHIP_LS_ITERATIVE : IDAHIP_LS_DIRECT) : -1; }
+int idahip_ls_num_iters(const idahip_ctx* c) { return c ? (c->krylov ? c->kry_last_nli : 0) : -1; }
+double idahip_ls_res_norm(const idahip_ctx* c) { return c && c->krylov ? c->kry_last_resnorm : 0.0; }
 
 #ifdef IDAHIP_STAMPS /* (only accepted together with -DIDAHIP_TIMING_BUILD: exp_switches.hpp) */
 /* timing builds: a device buffer for in-kernel time stamps (8 per workgroup of the instrumented launch) */

@@ -438,13 +438,18 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
             L.clear(); P.clear();
             // a DQ ctx (idahip_set_jacobian_dq): sys for all of them, then the setups with their step sizes
             const bool dq = idahip_jacobian_dq(e->ctx) > 0;
-            for (int b : R) (S[b].call_lsetup && !dq ? L : P).push_back(b);
+            // a Krylov ctx (idahip_create_krylov): sys for all of them; its linear setup forms and factors nothing and cannot fail
+            const bool kry = idahip_krylov(e->ctx, nullptr) == 1;
+            for (int b : R) (S[b].call_lsetup && !dq && !kry ? L : P).push_back(b);
             if (!P.empty()) {
                 tn.clear(); cj.clear();
                 for (int b : P) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); }
                 ENS_CALL(e, idahip_nls_sys(e->ctx, tn.data(), cj.data(), 1, P.data(), (int)P.size()));
             }
             for (int b : R) S[b].nre += 1;
+            if (kry)
+                for (int b : R)
+                    if (S[b].call_lsetup) after_lsetup_nojac(S[b]);  // idaNlsLSetup's bookkeeping; no Jacobian: nje stays
             if (dq)
                 for (int b : R)
                     if (S[b].call_lsetup) L.push_back(b);
@@ -482,16 +487,18 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
         }
         if (I.empty()) break;
         sc.clear();
-        {   // idaLsSolve's bookkeeping around LSolver::solve (ida_ls.rs:316-418): the solver's type decides the tolerance it is
+        const int lst = idahip_ls_type(e->ctx);
+        if (lst == IDAHIP_LS_DIRECT) {   // idaLsSolve's bookkeeping around LSolver::solve (ida_ls.rs:316-418): the solver's type decides the tolerance it is
             // given (0 for a direct solver: idahip_ls_solve ignores it), the nli / ncfl counters and whether the correction is
-            // scaled by 2 / (1 + cjratio) (:405-410). The library's solver is Direct with no iterations and no failures.
-            const int lst = idahip_ls_type(e->ctx);
+            // scaled by 2 / (1 + cjratio) (:405-410). The dense and band solvers are Direct with no iterations and no failures.
             const long nli_inc = idahip_ls_num_iters(e->ctx);
             // tol = sqrt(N) * eplifac for an iterative solver, 0 for a direct one (:323-329; eplifac = 0.05, :211). The fused
             // iteration kernel is LSolver::solve of the DIRECT solver and takes no tolerance: anything else has no kernel here.
             const double tol = lsolve_tol(lst, std::sqrt((double)e->n), EPLIFAC);
-            if (lst != IDAHIP_LS_DIRECT || tol != 0.0) return efail(e, -3, "LSolverType %d (tol %g): only the dense direct solver is implemented", lst, tol);
+            if (tol != 0.0) return efail(e, -3, "LSolverType %d (tol %g): a direct solver takes no tolerance", lst, tol);
             for (int b : I) sc.push_back(after_lsolve(S[b], lst, nli_inc, false) ? 2.0 / (1.0 + S[b].cjratio) : 1.0);
+        } else if (lst != IDAHIP_LS_ITERATIVE) {
+            return efail(e, -3, "LSolverType %d: only the direct solvers and the matrix-free SPGMR of a Krylov ctx are implemented", lst);
         }
         C.clear();
         // what follows a convergence test (newton.rs:109-153): converged / iterate again / ConvergenceRecover
@@ -521,9 +528,34 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
                 s.nls_ret = NLS_CONV_RECVR;
             }
         };
-        bool all_fresh = e->fused_newton;
+        bool all_fresh = e->fused_newton && lst == IDAHIP_LS_DIRECT;
         for (int b : I) all_fresh = all_fresh && S[b].curiter == 0;
-        if (all_fresh) {
+        if (lst == IDAHIP_LS_ITERATIVE) {
+            // the Newton body of a Krylov ctx: the solver's tolerance is (sqrt(N) * eplifac) * eps_newt, formed by the
+            // library from eps_newt; the correction is not scaled (ida_ls.rs:405-410); nli / ncfl through after_lsolve; the residual
+            // evaluations of the difference quotients (one per linear iteration) go to nre_dq; every flag other than SUCCESS is
+            // recoverable and takes Newton's ConvergenceRecover exit (newton.rs:146-153), ee left alone
+            tn.clear(); cj.clear();
+            std::vector<double> epsv;
+            for (int b : I) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); epsv.push_back(S[b].eps_newt); }
+            nrm.assign(I.size(), 0.0);
+            std::vector<int32_t> nli(I.size(), 0), lflag(I.size(), 0);
+            ENS_CALL(e, idahip_newton_iter_krylov(e->ctx, tn.data(), cj.data(), epsv.data(), nrm.data(), nli.data(), lflag.data(), I.data(), (int)I.size()));
+            for (size_t q = 0; q < I.size(); ++q) {
+                const int b = I[q];
+                Sys& s = S[b];
+                s.niters += 1;
+                (void)after_lsolve(s, lst, nli[q], lflag[q] != 0);
+                s.nre_dq += nli[q];
+                if (lflag[q] != 0) {
+                    after_ctest(b, NLS_CONV_RECVR, false);
+                    continue;
+                }
+                bool converged = false;
+                const int ret = conv_test(s, nrm[q], &converged);
+                after_ctest(b, ret, converged);
+            }
+        } else if (all_fresh) {
             // the first two iterations in one device call: both convergence tests are decided there (no powf needed for
             // m <= 1, ida_nls.rs:243-262); the scalar state is brought up to date here from the two norms it returns
             tn.clear(); cj.clear();
@@ -788,7 +820,8 @@ int idaens_create(idaens** out, idahip_ctx* ctx, const double* hYY0, const doubl
     e->ctx = ctx;
     e->n = idahip_n(ctx);
     e->batch = idahip_batch(ctx);
-    e->fused_newton = idahip_kind(ctx) != IDAHIP_HOST_CALLBACK;  // a host residual cannot run between two device iterations
+    // a host residual cannot run between two device iterations; a Krylov ctx has its own Newton body
+    e->fused_newton = idahip_kind(ctx) != IDAHIP_HOST_CALLBACK && idahip_krylov(ctx, nullptr) != 1;
     e->sys.resize(e->batch);
     // Ida::new (lib.rs:291-293): phi[0] = yy0, phi[1] = yp0; yy/yp start as yy0/yp0 (ida_nls.rs:83-84)
     int rc = idahip_upload(ctx, IDAHIP_F_PHI0, 0, e->batch, hYY0);
@@ -874,7 +907,7 @@ int idaens_set_device_controller(idaens* e, int on) {
 }
 int idaens_set_fused_newton(idaens* e, int on) {
     if (!e) return -1;
-    e->fused_newton = on != 0 && idahip_kind(e->ctx) != IDAHIP_HOST_CALLBACK;
+    e->fused_newton = on != 0 && idahip_kind(e->ctx) != IDAHIP_HOST_CALLBACK && idahip_krylov(e->ctx, nullptr) != 1;
     return 0;
 }
 
@@ -975,6 +1008,7 @@ int continue_schedule(idaens* e, SolveCall& C, int b) {
 int device_ctl_applies(const idaens* e, const SolveCall& C) {
     const int k = idahip_kind(e->ctx);
     if (!e->device_ctl || C.itask != IDAENS_NORMAL || e->trace_sys >= 0) return 0;
+    if (idahip_krylov(e->ctx, nullptr) == 1) return 0;  // the device steppers solve with factors: a Krylov ctx steps on the host
     // root finding on the device: the function family of idaens_set_roots (not a user callback), not in idaens_stream
     if (e->nrtfn != 0 && (e->rt_fn != nullptr || e->nrtfn > IDAHIP_MAX_ROOTS || C.recycle)) return 0;
     if (e->n <= 8 && (k == IDAHIP_ROBERTS || k == IDAHIP_LORENZ63)) return 1;
@@ -1605,6 +1639,7 @@ extern "C" int idaens_calc_ic(idaens* e, int icopt, double tout1, int32_t* hStat
         return efail(e, -2, "idaens_calc_ic: IDAENS_YA_YDP_INIT needs the id vector (idahip_set_id)");
     if (e->started) return efail(e, -2, "idaens_calc_ic: only before the first solve, solve_schedule or stream call");
     if (idahip_constraints(e->ctx, nullptr) == 1) return efail(e, -2, "idaens_calc_ic: a ctx with constraints is not supported (idahip_set_constraints)");
+    if (idahip_krylov(e->ctx, nullptr) == 1) return efail(e, -2, "idaens_calc_ic: a Krylov ctx is not supported (idahip_create_krylov)");
     if (!e->have_ic) return efail(e, -2, "no snapshot of the initial conditions (idaens_create failed to take it)");
     return calc_ic(e, icopt, tout1, hStatus);
 }

@@ -185,6 +185,16 @@ IDA_HD inline void after_lsetup(SysCore& s, int info) {
     s.ss = 20.0;
     s.nls_ret = info ? NLS_LSETUP_RECVR : NLS_SUCCESS;
 }
+// the same bookkeeping for a linear setup that forms no Jacobian -- the matrix-free solver of a Krylov ctx:
+// nothing is formed or factored, nothing can fail, nje stays
+IDA_HD inline void after_lsetup_nojac(SysCore& s) {
+    s.nsetups += 1;
+    s.jcur = true;
+    s.cjold = s.cj;
+    s.cjratio = 1.0;
+    s.ss = 20.0;
+    s.nls_ret = NLS_SUCCESS;
+}
 
 // ---------------------------------------------------------------- idaLsSolve's bookkeeping around LSolver::solve (ida_ls.rs:316-418)
 // ls_type: LSolverType (0 Direct, 1 Iterative, 2 MatrixIterative; include/ida_hip.h). Returns the tolerance the solver is to be

@@ -45,6 +45,8 @@ HIP_SYMBOLS = [
     "idahip_set_id", "idahip_id", "idahip_ic_begin", "idahip_ic_reset", "idahip_ic_res", "idahip_ic_setup", "idahip_ic_setup_dq",
     "idahip_ic_solve", "idahip_ic_trial", "idahip_ic_accept", "idahip_ic_commit",
     "idahip_set_constraints", "idahip_constraints", "idahip_post_newton_constr", "idahip_constr_check",
+    "idahip_create_krylov", "idahip_krylov", "idahip_set_krylov_fused", "idahip_krylov_fused", "idahip_krylov_solve",
+    "idahip_newton_iter_krylov",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
@@ -160,6 +162,12 @@ def load():
     H.idahip_ic_trial.argtypes = [vp, ci, dp, dp, dp, dp, i32p, ci]
     H.idahip_ic_accept.argtypes = [vp, ci, i32p, ci]
     H.idahip_ic_commit.argtypes = [vp, i32p, i32p, ci]
+    H.idahip_create_krylov.argtypes = [C.POINTER(vp), ci, ci, ci, ci, vp, ci]
+    H.idahip_krylov.argtypes = [vp, C.POINTER(ci)]
+    H.idahip_set_krylov_fused.argtypes = [vp, ci]
+    H.idahip_krylov_fused.argtypes = [vp]
+    H.idahip_krylov_solve.argtypes = [vp, dp, dp, dp, dp, dp, i32p, i32p, dp, i32p, ci]
+    H.idahip_newton_iter_krylov.argtypes = [vp, dp, dp, dp, dp, i32p, i32p, i32p, ci]
     H.idahip_timing_enable.argtypes = [vp, ci]
     H.idahip_timing_get.argtypes = [vp, ci, dp, i64p, i64p]
     H.idahip_timing_reset.argtypes = [vp]
@@ -204,14 +212,22 @@ class IdaHipError(RuntimeError):
 
 class Ctx:
     """One ensemble context on one device (idahip_ctx). band=(ml, mu): a band ctx (idahip_create_band) whose Jacobians are stored,
-    factored and solved in LAPACK band storage."""
+    factored and solved in LAPACK band storage. krylov=maxl: a Krylov ctx (idahip_create_krylov) with the matrix-free SPGMR solver
+    of DESIGN.md section 4h and no matrix at all (maxl = 0: C IDA's default, 5)."""
 
-    def __init__(self, kind, n, batch, device=0, stream=None, band=None):
+    def __init__(self, kind, n, batch, device=0, stream=None, band=None, krylov=None):
         self.H, self.E = load()
         self.n, self.batch = int(n), int(batch)
         self.kind = KIND[kind] if isinstance(kind, str) else int(kind)
         h = C.c_void_p()
-        if band is None:
+        if krylov is not None:
+            if band is not None:
+                raise IdaHipError("a ctx is a band ctx or a Krylov ctx, not both")
+            self.band = None
+            rc = self.H.idahip_create_krylov(C.byref(h), int(device), self.n, self.batch, self.kind, stream, int(krylov))
+            if rc != 0 or not h.value:
+                raise IdaHipError("idahip_create_krylov failed (%d) -- kind, 8 < n <= 4096, maxl <= min(16, n), and a GPU visible?" % rc)
+        elif band is None:
             self.band = None
             rc = self.H.idahip_create(C.byref(h), int(device), self.n, self.batch, self.kind, stream)
             if rc != 0 or not h.value:
@@ -232,6 +248,53 @@ class Ctx:
         ml, mu = C.c_int(-1), C.c_int(-1)
         rc = self.H.idahip_band(self.h, C.byref(ml), C.byref(mu))
         return (ml.value, mu.value) if rc == 1 else None
+
+    @property
+    def krylov(self):
+        """idahip_krylov -> maxl for a Krylov ctx, None otherwise."""
+        m = C.c_int(-1)
+        return m.value if self.H.idahip_krylov(self.h, C.byref(m)) == 1 else None
+
+    def set_krylov_fused(self, on=True):
+        """Krylov ctx: the whole solve in one launch (default for the built-in kinds) or one launch per step (always for host callbacks)."""
+        self._chk(self.H.idahip_set_krylov_fused(self.h, int(bool(on))), "set_krylov_fused")
+
+    def krylov_fused(self):
+        return bool(self._chk(self.H.idahip_krylov_fused(self.h), "krylov_fused"))
+
+    def krylov_solve(self, tn, cj, tol, b, idx=None):
+        """The SPGMR solve of the listed systems at the ctx-resident yy, yp, savres, ewt; b [nsys][n] by list position
+        -> (x [nsys][n], nli [nsys], flag [nsys], res_norm [nsys]); flags 0 SUCCESS, 1 RES_REDUCED, 2 CONV_FAIL, 3 QRSOL_FAIL."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        tn, cj, tol = (_f64(np.broadcast_to(v, idx.shape)) for v in (tn, cj, tol))
+        b = _f64(b).reshape(idx.size, self.n)
+        x = np.zeros((idx.size, self.n))
+        nli = np.zeros(idx.size, dtype=np.int32)
+        flag = np.zeros(idx.size, dtype=np.int32)
+        rn = np.zeros(idx.size)
+        self._chk(self.H.idahip_krylov_solve(self.h, _p(tn), _p(cj), _p(tol), _p(b), _p(x), _p(nli, i32p), _p(flag, i32p), _p(rn),
+                                             _p(idx, i32p), idx.size), "krylov_solve")
+        return x, nli, flag, rn
+
+    def newton_iter_krylov(self, tn, cj, eps_newt, idx=None):
+        """The Newton loop body on a Krylov ctx -> (delnrm [nsys], nli [nsys], flag [nsys]); ee is untouched where flag != 0."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        tn, cj, eps_newt = (_f64(np.broadcast_to(v, idx.shape)) for v in (tn, cj, eps_newt))
+        out = np.zeros(idx.size)
+        nli = np.zeros(idx.size, dtype=np.int32)
+        flag = np.zeros(idx.size, dtype=np.int32)
+        self._chk(self.H.idahip_newton_iter_krylov(self.h, _p(tn), _p(cj), _p(eps_newt), _p(out), _p(nli, i32p), _p(flag, i32p),
+                                                   _p(idx, i32p), idx.size), "newton_iter_krylov")
+        return out, nli, flag
+
+    def ls_type(self):
+        return int(self.H.idahip_ls_type(self.h))
+
+    def ls_num_iters(self):
+        return int(self.H.idahip_ls_num_iters(self.h))
+
+    def ls_res_norm(self):
+        return float(self.H.idahip_ls_res_norm(self.h))
 
     def close(self):
         """idahip_destroy. Refused while an Ensemble created on this ctx is still open: libidaens keeps the raw ctx pointer."""

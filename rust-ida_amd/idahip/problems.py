@@ -276,17 +276,20 @@ def heat1d(n=4096, batch=256):
             "atol": np.array([1.0e-8]), "touts": 0.01 * np.arange(1, 11)}
 
 
-def make_ctx(prob, device=0, stream=None, band=False):
+def make_ctx(prob, device=0, stream=None, band=False, krylov=None):
     """Create a device context for a generated problem and load its data (import kept local: this module is also
     used by CPU-only tests). band=True: a band ctx -- (1, 1) for heat1d, prob["band"] for a host-callback problem with a band
-    Jacobian prob["bjac"]; a (ml, mu) pair is taken as given."""
+    Jacobian prob["bjac"]; a (ml, mu) pair is taken as given. krylov=maxl: a Krylov ctx (matrix-free SPGMR; 0 = the default maxl);
+    a host-callback problem then registers its residual alone."""
     from . import Ctx
     batch = prob["yy0"].shape[0]
     if band is True:
         band = (1, 1) if prob["kind"] == "heat1d" else tuple(prob["band"])
-    ctx = Ctx(prob["kind"], prob["n"], batch, device=device, stream=stream, band=band or None)
+    ctx = Ctx(prob["kind"], prob["n"], batch, device=device, stream=stream, band=band or None, krylov=krylov)
     ctx.set_tolerances(prob["rtol"], prob["atol"])
-    if prob["kind"] == "host_callback" and band:
+    if prob["kind"] == "host_callback" and krylov is not None:
+        ctx.set_host_residual(prob["res"])
+    elif prob["kind"] == "host_callback" and band:
         ctx.set_host_band_problem(prob["res"], prob["bjac"])
     elif prob["kind"] == "linear_dense":
         step = max(1, (1 << 28) // (8 * prob["n"] * prob["n"]))  # <= 256 MiB per matrix upload
