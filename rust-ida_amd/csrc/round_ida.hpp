@@ -431,9 +431,10 @@ __global__ __launch_bounds__(WG_NT) void round_end_kernel(RoundArgs a) {
     WgVec v{a, b, a.v.n, (long)b * a.v.n, sm};
     const IdaFlow<WgVec, ROOTS> F{a.f, s, v, ROOTS ? &s_rt : nullptr};
     bool stepping = a.stepping[b] != 0;
-    if (stepping && a.in_newton[b] && !s.newton_retry) stepping = F.attempt_end();
+    // (both calls inlined by force: a call out of line keeps the pointers in vector registers and spills around it)
+    if (stepping && a.in_newton[b] && !s.newton_retry) [[clang::always_inline]] stepping = F.attempt_end();
     const long long ground = a.round_base + a.round + 1;
-    if (a.f.recycle) stepping = F.after_round_stream(stepping, ground, b, threadIdx.x == 0);
+    if (a.f.recycle) [[clang::always_inline]] stepping = F.after_round_stream(stepping, ground, b, threadIdx.x == 0);
     __syncthreads();
     wg_copy_words(a.sys + b, s_raw);
     if (ROOTS) wg_copy_root(a.roots + b, &s_rt);

@@ -165,7 +165,7 @@ struct TinyVec {
             a.v.yp[vb + i] = yp;
         }
     }
-    // root functions (ida_flow.hpp): one thread owns the system, nothing to synchronise
+    // root functions (ida_flow.hpp's backend of the shared root finding): one thread owns the system, nothing to synchronise
     __device__ void sync() const {}
     __device__ double yy_at(int i) const { return a.v.yy[vb + i]; }
     __device__ double phi_at(int j, int i) const { return phi(j, i); }

@@ -12,8 +12,8 @@
 //   complete_step         /root/reference/src/impl_complete_step.rs:22-177
 //   get_solution          /root/reference/src/lib.rs:1274-1343      (coefficients; the sums run on the device)
 //   get_dky               /root/reference/src/lib.rs:424-529        (coefficients; quirk Q9: C IDA's loop bound)
-//   stop_test1/2          /root/reference/src/impl_stop_test.rs:36-211 (no tstop: the reference has no setter)
-//   r_check1/2/3, root_finding  /root/reference/src/impl_r_check.rs:32-576 (scalar bracketing here, y(t) interpolated on the device)
+//   stop_test1/2, r_check1/2/3, root_finding and the per-system pieces of Ida::solve: ida_solve_flow.hpp, shared with the device
+//                         steppers like the controller (here: the backend HostFlow, y(t) interpolated on the device)
 //   calc_ic               C IDA's IDACalcIC as DESIGN.md section 4f states it (the reference has none, src/lib.rs:328-335)
 // Vectors live on the device; this file talks to it only through include/ida_hip.h. The oracle is NOT used here.
 //
@@ -36,7 +36,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
-#include <limits>
 #include <chrono>
 #include <functional>
 #include <mutex>
@@ -46,16 +45,27 @@
 
 #include "../../include/ida_ensemble.h"
 
-#include "ida_controller.hpp"
+#include "ida_solve_flow.hpp"
 
 namespace {
 
-using namespace idactl;  // constants, SysCore and the scalar controller shared with the device-resident stepper
+using namespace idactl;  // constants, SysCore, the scalar controller and Ida::solve's per-system flow, shared with the device steppers
+
+// root finding (src/lib.rs:225-244, src/impl_r_check.rs): the root state of ida_solve_flow.hpp; nrtfn entries when roots are enabled
+struct RootVecs {
+    std::vector<double> glo, ghi, grout, iroots;
+    std::vector<int32_t> gactive;
+};
+template <class D, class S>
+void copy_roots(D& d, const S& s, int nr) {  // between RootVecs and the device steppers' idahip_root_state
+    for (int i = 0; i < nr; ++i) {
+        d.glo[i] = s.glo[i]; d.ghi[i] = s.ghi[i]; d.grout[i] = s.grout[i];
+        d.iroots[i] = s.iroots[i]; d.gactive[i] = s.gactive[i];
+    }
+}
 
 struct Sys : SysCore {
-    // --- root finding (src/lib.rs:225-244, src/impl_r_check.rs); the vectors have nrtfn entries when roots are enabled
-    std::vector<double> glo, ghi, grout, iroots;
-    std::vector<uint8_t> gactive;
+    RootVecs rt;
     long nbacktr = 0;  // idaens_calc_ic: line-search backtracks (host-only: SysCore's size is part of the device steppers' ABI)
 };
 
@@ -145,47 +155,6 @@ int queue_solution(Sys& s, int b, double t, SolList& sl) {
     return 0;
 }
 
-// ---------------------------------------------------------------- stop tests (impl_stop_test.rs), tstop == None
-int stop_test1(Sys& s, int b, double tout, int itask, SolList& sl) {
-    if (itask == IDAENS_NORMAL) {
-        if (tout == s.tretlast) {
-            s.tretlast = tout;
-            s.tret = tout;
-            return IDAENS_SUCCESS;
-        }
-        if ((s.tn - tout) * s.hh >= 0.0) {
-            const int ier = queue_solution(s, b, tout, sl);
-            if (ier) return ier;
-            s.tretlast = tout;
-            s.tret = tout;
-            return IDAENS_SUCCESS;
-        }
-        return IDAENS_UNFINISHED;  // ContinueSteps
-    }
-    if ((s.tn - s.tretlast) * s.hh > 0.0) {
-        queue_solution(s, b, s.tn, sl);
-        s.tretlast = s.tn;
-        s.tret = s.tn;
-        return IDAENS_SUCCESS;
-    }
-    return IDAENS_UNFINISHED;
-}
-
-int stop_test2(Sys& s, int b, double tout, int itask, SolList& sl) {
-    if (itask == IDAENS_NORMAL) {
-        if ((s.tn - tout) * s.hh >= 0.0) {
-            s.tret = tout;
-            s.tretlast = tout;
-            queue_solution(s, b, tout, sl);
-            return IDAENS_SUCCESS;
-        }
-        return IDAENS_UNFINISHED;
-    }
-    s.tret = s.tn;  // OneStep: yy/yp already hold y(tn)
-    s.tretlast = s.tn;
-    return IDAENS_SUCCESS;
-}
-
 int flush_solutions(idaens* e, SolList& sl) {
     if (sl.idx.empty()) return 0;
     ENS_CALL(e, idahip_get_solution(e->ctx, sl.kord.data(), sl.cvals.data(), sl.dvals.data(), sl.idx.data(), (int)sl.idx.size()));
@@ -193,228 +162,49 @@ int flush_solutions(idaens* e, SolList& sl) {
     return 0;
 }
 
-// ---------------------------------------------------------------- root finding (src/impl_r_check.rs:32-576)
-// Roots are rare events of single systems: the bracketing runs system by system on the host, with the device
-// interpolating y(t), y'(t) (idahip_get_solution) and the two vectors coming back for the root functions.
-int root_fn(const idaens* e, int b, double t, const double* y, const double* yp, double* g) {
-    if (e->rt_fn) return e->rt_fn(e->rt_user, b, t, y, yp, e->nrtfn, g) == 0 ? 0 : IDAENS_RTFUNC_FAIL;
-    for (int i = 0; i < e->nrtfn; ++i) g[i] = y[e->rt_comp[i]] - e->rt_thr[i];
-    return 0;
-}
-
-// get_solution(t) of system b on the device (yy, yp of that system become y(t), y'(t), lib.rs:1274), copy to e->hy, e->hyp
-int interp_now(idaens* e, int b, double t) {
-    Sys& s = e->sys[b];
-    int kord = 1;
-    const int rc = get_solution_coeffs(s, t, &kord);
-    if (rc) return rc;
-    const int32_t ib = b, ko = kord;
-    ENS_CALL(e, idahip_get_solution(e->ctx, &ko, s.cvals, s.dvals, &ib, 1));
-    ENS_CALL(e, idahip_download(e->ctx, IDAHIP_F_YY, b, 1, e->hy.data()));
-    ENS_CALL(e, idahip_download(e->ctx, IDAHIP_F_YP, b, 1, e->hyp.data()));
-    return 0;
-}
-
-// impl_r_check.rs:32-115 -- at the first call, before phi[1] is scaled by hh
-int r_check1(idaens* e, int b) {
-    const double eps = std::numeric_limits<double>::epsilon();
-    Sys& s = e->sys[b];
-    const int n = e->n, nr = e->nrtfn;
-    std::fill(s.iroots.begin(), s.iroots.end(), 0.0);
-    s.tlo = s.tn;
-    s.ttol = (std::fabs(s.tn) + std::fabs(s.hh)) * eps * 100.0;
-    ENS_CALL(e, idahip_download(e->ctx, IDAHIP_F_PHI0, b, 1, e->hy.data()));
-    ENS_CALL(e, idahip_download(e->ctx, (idahip_field)(IDAHIP_F_PHI0 + 1), b, 1, e->hyp.data()));
-    if (int rf = root_fn(e, b, s.tlo, e->hy.data(), e->hyp.data(), s.glo.data())) return rf;
-    s.nge = 1;
-    bool zroot = false;
-    for (int i = 0; i < nr; ++i)
-        if (std::fabs(s.glo[i]) == 0.0) {
-            s.gactive[i] = 0;
-            zroot = true;
-        }
-    if (zroot) {
-        const double hratio = std::fmax(s.ttol / std::fabs(s.hh), 0.1);
-        const double smallh = hratio * s.hh;
-        for (int i = 0; i < n; ++i) e->hy[i] = e->hy[i] + smallh * e->hyp[i];  // yy = phi[0] + smallh * phi[1]
+// ---------------------------------------------------------------- the backend of ida_solve_flow.hpp for system b
+// Roots are rare events of single systems: the bracketing (ida_solve_flow.hpp) runs system by system on the host, with the device
+// interpolating y(t), y'(t) (idahip_get_solution) and the two vectors coming back to e->hy, e->hyp for the root functions.
+struct HostFlow {
+    idaens* e;
+    int b;
+    SolList& sl;
+    int solution_at(double t) { return queue_solution(e->sys[b], b, t, sl); }
+    // get_solution(t) of system b on the device now (yy, yp of that system become y(t), y'(t), lib.rs:1274)
+    int interp(double t) {
+        Sys& s = e->sys[b];
+        int kord = 1;
+        const int rc = get_solution_coeffs(s, t, &kord);
+        if (rc) return rc;
+        const int32_t ib = b, ko = kord;
+        ENS_CALL(e, idahip_get_solution(e->ctx, &ko, s.cvals, s.dvals, &ib, 1));
+        ENS_CALL(e, idahip_download(e->ctx, IDAHIP_F_YY, b, 1, e->hy.data()));
+        ENS_CALL(e, idahip_download(e->ctx, IDAHIP_F_YP, b, 1, e->hyp.data()));
+        return 0;
+    }
+    int eval(double t, double* g) {
+        if (e->rt_fn) return e->rt_fn(e->rt_user, b, t, e->hy.data(), e->hyp.data(), e->nrtfn, g) == 0 ? 0 : IDAENS_RTFUNC_FAIL;
+        for (int i = 0; i < e->nrtfn; ++i) g[i] = e->hy[e->rt_comp[i]] - e->rt_thr[i];
+        return 0;
+    }
+    int eval_start(double* g) {
+        ENS_CALL(e, idahip_download(e->ctx, IDAHIP_F_PHI0, b, 1, e->hy.data()));
+        ENS_CALL(e, idahip_download(e->ctx, (idahip_field)(IDAHIP_F_PHI0 + 1), b, 1, e->hyp.data()));
+        return eval(e->sys[b].tn, g);
+    }
+    int yy_from_phi01(double f) {  // r_check1 only, after eval_start: hy, hyp hold phi[0], phi[1] (the callback keeps seeing phi[1] as y')
+        for (int i = 0; i < e->n; ++i) e->hy[i] = e->hy[i] + f * e->hyp[i];
         ENS_CALL(e, idahip_upload(e->ctx, IDAHIP_F_YY, b, 1, e->hy.data()));
-        if (int rf = root_fn(e, b, s.tlo + smallh, e->hy.data(), e->hyp.data(), s.ghi.data())) return rf;
-        s.nge += 1;
-        for (int i = 0; i < nr; ++i)
-            if (!s.gactive[i] && std::fabs(s.ghi[i]) != 0.0) {
-                s.gactive[i] = 1;
-                s.glo[i] = s.ghi[i];
-            }
+        return 0;
     }
-    return 0;
-}
-
-// impl_r_check.rs:117-219 -- on re-entry after a root return. Returns IDAENS_UNFINISHED (continue), ROOT_RETURN or < 0.
-int r_check2(idaens* e, int b) {
-    const double eps = std::numeric_limits<double>::epsilon();
-    Sys& s = e->sys[b];
-    const int n = e->n, nr = e->nrtfn;
-    if (!s.irfnd) return IDAENS_UNFINISHED;
-    int rc = interp_now(e, b, s.tlo);
-    if (rc) return rc;
-    if (int rf = root_fn(e, b, s.tlo, e->hy.data(), e->hyp.data(), s.glo.data())) return rf;
-    s.nge += 1;
-    std::fill(s.iroots.begin(), s.iroots.end(), 0.0);
-    bool zroot = false;
-    for (int i = 0; i < nr; ++i)
-        if (s.gactive[i] && std::fabs(s.glo[i]) == 0.0) {
-            zroot = true;
-            s.iroots[i] = 1.0;
-        }
-    if (zroot) {
-        s.ttol = (std::fabs(s.tn) + std::fabs(s.hh)) * eps * 100.0;
-        const double smallh = s.ttol * signum(s.hh);
-        const double tplus = s.tlo + smallh;
-        if ((tplus - s.tn) * s.hh >= 0.0) {
-            const double hratio = smallh / s.hh;
-            std::vector<double> p1(n);
-            ENS_CALL(e, idahip_download(e->ctx, (idahip_field)(IDAHIP_F_PHI0 + 1), b, 1, p1.data()));
-            for (int i = 0; i < n; ++i) e->hy[i] = e->hy[i] + hratio * p1[i];  // yy += hratio * phi[1]
-            ENS_CALL(e, idahip_upload(e->ctx, IDAHIP_F_YY, b, 1, e->hy.data()));
-        } else {
-            rc = interp_now(e, b, tplus);
-            if (rc) return rc;
-        }
-        if (int rf = root_fn(e, b, tplus, e->hy.data(), e->hyp.data(), s.ghi.data())) return rf;
-        s.nge += 1;
-        bool zroot2 = false;
-        for (int i = 0; i < nr; ++i) {
-            if (!s.gactive[i]) continue;
-            if (std::fabs(s.ghi[i]) == 0.0) {
-                if (s.iroots[i] > 0.0) return IDAENS_CLOSE_ROOTS;
-                zroot2 = true;
-                s.iroots[i] = 1.0;
-            } else if (s.iroots[i] > 0.0) {
-                s.glo[i] = s.ghi[i];
-            }
-        }
-        if (zroot2) return IDAENS_ROOT_RETURN;
+    int yy_add_phi1(double f) {  // after interp: hy holds yy
+        std::vector<double> p1(e->n);
+        ENS_CALL(e, idahip_download(e->ctx, (idahip_field)(IDAHIP_F_PHI0 + 1), b, 1, p1.data()));
+        for (int i = 0; i < e->n; ++i) e->hy[i] = e->hy[i] + f * p1[i];
+        ENS_CALL(e, idahip_upload(e->ctx, IDAHIP_F_YY, b, 1, e->hy.data()));
+        return 0;
     }
-    return IDAENS_UNFINISHED;
-}
-
-void scan_roots(const idaens* e, const Sys& s, const std::vector<double>& gval, bool first, bool* zroot, bool* sgnchg, int* imax) {
-    double maxfrac = 0.0;
-    *zroot = false;
-    *sgnchg = false;
-    for (int i = 0; i < e->nrtfn; ++i) {
-        if (!s.gactive[i]) continue;
-        const bool rootdir_glo_neg = 0.0 * s.glo[i] <= 0.0;  // rootdir is 0 (no setter in the reference, lib.rs:372)
-        if (first) {  // impl_r_check.rs:361-383
-            if (std::fabs(gval[i]) == 0.0) {
-                if (rootdir_glo_neg) *zroot = true;
-                continue;
-            }
-        } else if (std::fabs(gval[i]) == 0.0 && rootdir_glo_neg) {  // impl_r_check.rs:486-504
-            *zroot = true;
-            continue;
-        }
-        if (s.glo[i] * gval[i] < 0.0 && rootdir_glo_neg) {
-            const double gfrac = std::fabs(gval[i] / (gval[i] - s.glo[i]));
-            if (gfrac > maxfrac) {
-                *sgnchg = true;
-                maxfrac = gfrac;
-                *imax = i;
-            }
-        }
-    }
-}
-
-// impl_r_check.rs:343-576 (modified secant / Illinois). Returns IDAENS_UNFINISHED (no root), ROOT_RETURN or < 0.
-int root_find(idaens* e, int b) {
-    Sys& s = e->sys[b];
-    const int nr = e->nrtfn;
-    int imax = 0;
-    bool zroot, sgnchg;
-    scan_roots(e, s, s.ghi, true, &zroot, &sgnchg, &imax);
-    if (!sgnchg) {
-        s.trout = s.thi;
-        s.grout = s.ghi;
-        if (!zroot) return IDAENS_UNFINISHED;
-        for (int i = 0; i < nr; ++i) {
-            s.iroots[i] = 0.0;
-            if (s.gactive[i] && std::fabs(s.ghi[i]) == 0.0 && 0.0 * s.glo[i] <= 0.0) s.iroots[i] = signum(s.glo[i]);
-        }
-        return IDAENS_ROOT_RETURN;
-    }
-    double alph = 1.0;
-    int side = 0, sideprev = -1;
-    for (;;) {
-        if (std::fabs(s.thi - s.tlo) <= s.ttol) break;
-        if (sideprev == side) alph = (side == 2) ? alph * 2.0 : alph * 0.5;
-        else alph = 1.0;
-        double tmid = s.thi - (s.thi - s.tlo) * s.ghi[imax] / (s.ghi[imax] - alph * s.glo[imax]);
-        if (std::fabs(tmid - s.tlo) < 0.5 * s.ttol) {
-            const double fracint = std::fabs(s.thi - s.tlo) / s.ttol;
-            const double fracsub = (fracint > 5.0) ? 0.1 : 0.5 / fracint;
-            tmid = s.tlo + fracsub * (s.thi - s.tlo);
-        }
-        if (std::fabs(s.thi - tmid) < 0.5 * s.ttol) {
-            const double fracint = std::fabs(s.thi - s.tlo) / s.ttol;
-            const double fracsub = (fracint > 5.0) ? 0.1 : 0.5 / fracint;
-            tmid = s.thi - fracsub * (s.thi - s.tlo);
-        }
-        const int rc = interp_now(e, b, tmid);
-        if (rc) return rc;
-        if (int rf = root_fn(e, b, tmid, e->hy.data(), e->hyp.data(), s.grout.data())) return rf;
-        s.nge += 1;
-        sideprev = side;
-        scan_roots(e, s, s.grout, false, &zroot, &sgnchg, &imax);
-        if (sgnchg) {
-            s.thi = tmid;
-            s.ghi = s.grout;
-            side = 1;
-            if (std::fabs(s.thi - s.tlo) <= s.ttol) break;
-            continue;
-        }
-        if (zroot) {
-            s.thi = tmid;
-            s.ghi = s.grout;
-            break;
-        }
-        s.tlo = tmid;
-        s.glo = s.grout;
-        side = 2;
-        if (std::fabs(s.thi - s.tlo) <= s.ttol) break;
-    }
-    s.trout = s.thi;
-    s.grout = s.ghi;
-    for (int i = 0; i < nr; ++i) {
-        s.iroots[i] = 0.0;
-        if (s.gactive[i] && 0.0 * s.glo[i] <= 0.0 && (std::fabs(s.ghi[i]) == 0.0 || s.glo[i] * s.ghi[i] < 0.0))
-            s.iroots[i] = signum(s.glo[i]);
-    }
-    return IDAENS_ROOT_RETURN;
-}
-
-// impl_r_check.rs:221-280 -- after a successful step. Returns IDAENS_UNFINISHED (no root), ROOT_RETURN or < 0.
-int r_check3(idaens* e, int b) {
-    const double eps = std::numeric_limits<double>::epsilon();
-    Sys& s = e->sys[b];
-    if (s.taskc == IDAENS_ONE_STEP) s.thi = s.tn;
-    else s.thi = ((s.toutc - s.tn) * s.hh >= 0.0) ? s.tn : s.toutc;
-    int rc = interp_now(e, b, s.thi);
-    if (rc) return rc;
-    if (int rf = root_fn(e, b, s.thi, e->hy.data(), e->hyp.data(), s.ghi.data())) return rf;
-    s.nge += 1;
-    s.ttol = (std::fabs(s.tn) + std::fabs(s.hh)) * eps * 100.0;
-    const int ier = root_find(e, b);
-    if (ier < 0) return ier;
-    for (int i = 0; i < e->nrtfn; ++i)
-        if (!s.gactive[i] && s.grout[i] != 0.0) s.gactive[i] = 1;
-    s.tlo = s.trout;
-    s.glo = s.grout;
-    if (ier == IDAENS_ROOT_RETURN) {
-        rc = interp_now(e, b, s.trout);
-        if (rc) return rc;
-    }
-    return ier;
-}
+};
 
 // residual evaluations of one band DQ Jacobian (idaLsBandDQJac): min(ml + mu + 1, n)
 long dq_band_evals(idaens* e) {
@@ -709,18 +499,9 @@ int attempt_round(idaens* e, std::vector<int32_t>& act, SolveCall& C) {
     for (int q = 0; q < na; ++q) {
         const int b = act[q];
         Sys& s = S[b];
-        int nflag = NFLAG_NONE;
-        double err_k = 0.0, err_km1 = 0.0;
-        if (e->constr && cflag[q] == 2) {
-            nflag = NFLAG_CONSTR_RECVR;
-            s.rr = crr[q];  // kept by handle_n_flag
-        } else if (s.nls_ret == NLS_SUCCESS) {
-            if (!test_error(s, s.ck, &norms[4 * q], &err_k, &err_km1)) nflag = NFLAG_TEST_FAIL;
-        } else if (s.nls_ret == NLS_CONV_RECVR) {
-            nflag = NFLAG_CONV_RECVR;
-        } else {
-            nflag = NFLAG_LSETUP_RECVR;
-        }
+        HostFlow be{e, b, sl};
+        double err_k, err_km1;
+        const int nflag = attempt_nflag(s, e->constr ? cflag[q] : 0, e->constr ? crr[q] : 0.0, &norms[4 * q], &err_k, &err_km1);
         if (nflag != NFLAG_NONE) {
             // restore (with the kk/ns/beta of this attempt), then handle_n_flag
             const int kk_att = s.kk, ns_att = s.ns;
@@ -732,18 +513,12 @@ int attempt_round(idaens* e, std::vector<int32_t>& act, SolveCall& C) {
                 rest_cvals.insert(rest_cvals.end(), s.cvals, s.cvals + MXORDP1);
             }
             const int kflag = handle_n_flag(s, nflag, err_k, err_km1, e->maxnef, e->maxncf);
-            if (kflag != 0) {  // step failed for good: Ida::solve's failed-step path (impl_solve.rs:300-313)
-                if (queue_solution(s, b, s.tn, sl) == 0) {
-                    s.tret = s.tn;
-                    s.tretlast = s.tn;
-                }
-                s.status = kflag;
-                s.dead = true;
-                s.ph = PH_IDLE;
+            if (kflag != 0) {
+                step_failed(s, kflag, be);
                 continue;
             }
             if (s.nst == 0) {  // reset(): psi[0] = hh; phi[1] *= rr  (Q5)
-                s.psi[0] = s.hh;
+                first_step_reset(s);
                 reset_idx.push_back(b);
                 reset_fac.push_back(s.rr);
             }
@@ -776,24 +551,9 @@ int attempt_round(idaens* e, std::vector<int32_t>& act, SolveCall& C) {
             s.ewt_bad = bad[q] != 0;
             s.nstloc += 1;
             s.ph = PH_LOOP_TOP;
-            if (e->nrtfn > 0) {  // impl_solve.rs:343-356
-                const int ier = r_check3(e, b);
-                if (ier < 0) {
-                    s.status = ier;
-                    s.dead = true;
-                    s.ph = PH_IDLE;
-                    continue;
-                }
-                if (ier == IDAENS_ROOT_RETURN) {
-                    s.irfnd = true;
-                    s.tretlast = s.tlo;
-                    s.tret = s.tlo;
-                    s.status = IDAENS_ROOT_RETURN;
-                    s.ph = PH_IDLE;
-                    continue;
-                }
-            }
-            const int istate = stop_test2(s, b, s.tout_cur, itask, sl);
+            HostFlow be{e, b, sl};
+            if (root_return_after_step(s, s.rt, e->nrtfn, be)) continue;
+            const int istate = stop_test2(s, s.tout_cur, itask, be);
             if (istate != IDAENS_UNFINISHED) {
                 s.status = istate;
                 s.ph = PH_IDLE;
@@ -921,62 +681,6 @@ int idaens_set_max_ord(idaens* e, int maxord) {
 
 namespace {
 
-// Entry of one Ida::solve(s.tout_cur) call for a system that is between calls (impl_solve.rs:179-241): root checks and
-// stop tests. Returns IDAENS_UNFINISHED when the system has to step, else the status this call returns with (tret set).
-int enter_call(idaens* e, SolveCall& C, int b) {
-    Sys& s = e->sys[b];
-    SolList& sl = C.sl;
-    const int itask = C.itask;
-    const double tout = s.tout_cur;
-    s.nstloc = 0;
-    if (itask == IDAENS_NORMAL) s.toutc = tout;
-    s.taskc = itask;
-    if (s.nst > 0 && e->nrtfn > 0) {
-        const double eps_ = std::numeric_limits<double>::epsilon();
-        const bool irfndp = s.irfnd;
-        int ier = r_check2(e, b);
-        if (ier < 0) {
-            s.dead = true;
-            return ier;
-        }
-        if (ier == IDAENS_ROOT_RETURN) {
-            s.tretlast = s.tlo;
-            s.tret = s.tlo;
-            return IDAENS_ROOT_RETURN;
-        }
-        const double troundoff = (std::fabs(s.tn) + std::fabs(s.hh)) * eps_ * 100.0;
-        if (std::fabs(s.tn - s.tretlast) > troundoff) {
-            ier = r_check3(e, b);
-            if (ier < 0) {
-                s.dead = true;
-                return ier;
-            }
-            if (ier == IDAENS_UNFINISHED) {
-                s.irfnd = false;
-                if (itask == IDAENS_ONE_STEP && irfndp) {
-                    s.tretlast = s.tn;
-                    s.tret = s.tn;
-                    queue_solution(s, b, s.tn, sl);
-                    return IDAENS_SUCCESS;
-                }
-            } else {  // root found
-                s.irfnd = true;
-                s.tretlast = s.tlo;
-                s.tret = s.tlo;
-                return IDAENS_ROOT_RETURN;
-            }
-        }
-    }
-    if (s.nst > 0) {
-        const int istate = stop_test1(s, b, tout, itask, sl);
-        if (istate != IDAENS_UNFINISHED) {
-            if (istate < 0) s.dead = true;
-            return istate;
-        }
-    }
-    return IDAENS_UNFINISHED;
-}
-
 // A system's call has just returned (s.status set, phase idle). With IDAENS_SUCCESS and touts left in the schedule it
 // enters the next call at once. Returns 1 when the system is stepping again, 0 when it is done for this call, < 0 on a
 // device failure.
@@ -993,7 +697,8 @@ int continue_schedule(idaens* e, SolveCall& C, int b) {
             const int rc = emit_outputs(e, C);
             if (rc) return rc;
         }
-        const int ist = enter_call(e, C, b);
+        HostFlow be{e, b, C.sl};
+        const int ist = enter_call(s, s.rt, e->nrtfn, C.itask, be);
         if (ist == IDAENS_UNFINISHED) {
             s.ph = PH_LOOP_TOP;
             return 1;
@@ -1053,11 +758,7 @@ int solve_core_device(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, 
     call.root_states = nullptr;
     if (e->nrtfn > 0) {
         rstate.resize(batch);
-        for (int b = 0; b < batch; ++b)
-            for (int i = 0; i < e->nrtfn; ++i) {
-                rstate[b].glo[i] = S[b].glo[i]; rstate[b].ghi[i] = S[b].ghi[i]; rstate[b].grout[i] = S[b].grout[i];
-                rstate[b].iroots[i] = S[b].iroots[i]; rstate[b].gactive[i] = S[b].gactive[i];
-            }
+        for (int b = 0; b < batch; ++b) copy_roots(rstate[b], S[b].rt, e->nrtfn);
         call.root_states = rstate.data();
     }
     std::vector<int64_t> rounds(batch, 0);
@@ -1076,10 +777,7 @@ int solve_core_device(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, 
     bool unfinished = false;
     for (int b = 0; b < batch; ++b) {
         static_cast<SysCore&>(S[b]) = st[b];
-        for (int i = 0; i < e->nrtfn; ++i) {
-            S[b].glo[i] = rstate[b].glo[i]; S[b].ghi[i] = rstate[b].ghi[i]; S[b].grout[i] = rstate[b].grout[i];
-            S[b].iroots[i] = rstate[b].iroots[i]; S[b].gactive[i] = (uint8_t)rstate[b].gactive[i];
-        }
+        if (e->nrtfn > 0) copy_roots(S[b].rt, rstate[b], e->nrtfn);
         rmax = std::max(rmax, rounds[b]);
         Sys& s = S[b];
         const int now = reached_of(s);
@@ -1118,7 +816,6 @@ int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long ma
     if (const int rcc = read_constraints(e)) return rcc;
     e->started = true;
     if (const int mode = device_ctl_applies(e, C)) return solve_core_device(e, C, hTret, hStatus, max_rounds, mode);
-    const double eps = std::numeric_limits<double>::epsilon();
     std::vector<Sys>& S = e->sys;
     SolList& sl = C.sl;
     const double tout = C.touts[0];  // the first call's tout sizes the initial step (impl_solve.rs:104-131)
@@ -1147,39 +844,14 @@ int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long ma
                 std::vector<double> fac;
                 for (size_t q = 0; q < fresh.size(); ++q) {
                     Sys& s = S[fresh[q]];
-                    const double tdist = std::fabs(tout - s.tn);
-                    const double troundoff = 2.0 * eps * (std::fabs(s.tn) + std::fabs(tout));
-                    if (tdist == 0.0 || tdist < troundoff) {
-                        s.status = IDAENS_ILL_INPUT;  // "tout too close to t0 to start integration"
-                        s.tret = s.tn;
-                        continue;
-                    }
-                    if (e->constr && viol[q]) {
-                        s.status = IDAENS_ILL_INPUT;  // "y0 fails to satisfy constraints"
-                        s.tret = s.tn;
-                        continue;
-                    }
-                    s.setup_done = true;
-                    s.hh = s.hin;
-                    if (s.hh == 0.0) {
-                        s.hh = 0.001 * tdist;
-                        if (ypnorm[q] > 2.0 / s.hh) s.hh = 0.5 / ypnorm[q];  // Q7 kept (impl_solve.rs:127)
-                        if (tout < s.tn) s.hh = -s.hh;
-                    }
-                    const double rh = std::fabs(s.hh) * e->hmax_inv;
-                    if (rh > 1.0) s.hh /= rh;
-                    s.h0u = s.hh;
-                    s.kk = 0;
-                    s.kused = 0;
-                    s.eps_newt = e->epcon;
-                    s.toldel = 0.0001 * s.eps_newt;
-                    s.phi0nrm = p0nrm[q];
+                    if (!first_call_scalars(s, tout, ypnorm[q], p0nrm[q], e->epcon, e->hmax_inv, e->constr && viol[q])) continue;  // ILL_INPUT
                     ok.push_back(fresh[q]);
                     fac.push_back(s.hh);
                 }
                 if (e->nrtfn > 0)
                     for (size_t q = 0; q < ok.size();) {  // impl_solve.rs:157-159
-                        const int rc1 = r_check1(e, ok[q]);
+                        HostFlow be{e, ok[q], sl};
+                        const int rc1 = r_check1(S[ok[q]], S[ok[q]].rt, e->nrtfn, be);
                         if (rc1 == IDAENS_RTFUNC_FAIL) {  // the user's root function failed for this system: it never starts
                             S[ok[q]].status = rc1;
                             S[ok[q]].tret = S[ok[q]].tn;
@@ -1201,7 +873,8 @@ int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long ma
             if (s.dead || !s.setup_done) continue;  // earlier fatal error / ILL_INPUT at the first call: status is sticky
             s.sched_i = 0;
             s.tout_cur = C.touts[0];
-            const int ist = enter_call(e, C, b);
+            HostFlow be{e, b, C.sl};
+            const int ist = enter_call(s, s.rt, e->nrtfn, C.itask, be);
             if (ist == IDAENS_UNFINISHED) {
                 s.ph = PH_LOOP_TOP;
                 act.push_back(b);
@@ -1234,33 +907,8 @@ int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long ma
         for (int b : act) {
             Sys& s = S[b];
             if (s.ph == PH_LOOP_TOP) {
-                if (e->mxstep > 0 && s.nstloc >= e->mxstep) {
-                    s.tret = s.tn;
-                    s.tretlast = s.tn;
-                    s.status = IDAENS_TOO_MUCH_WORK;  // recoverable for the caller: the next solve call continues
-                    s.ph = PH_IDLE;
-                    continue;
-                }
-                if (s.nst > 0 && s.ewt_bad) {
-                    queue_solution(s, b, s.tn, sl);
-                    s.tret = s.tn;
-                    s.tretlast = s.tn;
-                    s.status = IDAENS_ILL_INPUT;
-                    s.dead = true;
-                    s.ph = PH_IDLE;
-                    continue;
-                }
-                s.tolsf = eps * s.phi0nrm;
-                if (s.tolsf > 1.0) {
-                    s.tolsf *= 10.0;
-                    s.tret = s.tn;
-                    s.tretlast = s.tn;
-                    if (s.nst > 0) queue_solution(s, b, s.tn, sl);
-                    s.status = IDAENS_TOO_MUCH_ACC;
-                    s.dead = true;
-                    s.ph = PH_IDLE;
-                    continue;
-                }
+                HostFlow be{e, b, sl};
+                if (!loop_top(s, e->mxstep, be)) continue;
             }
             go.push_back(b);
         }
@@ -1278,7 +926,7 @@ int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long ma
             std::vector<int32_t> again;
             for (int b = 0; b < e->batch; ++b) {
                 Sys& s = S[b];
-                if (s.ph == PH_IDLE && !s.dead && s.setup_done && s.status == IDAENS_SUCCESS && s.sched_i == C.ntout - 1 && s.nst > 0) {
+                if (stream_restart_due(s, C.ntout)) {
                     e->retired_iters += s.niters;
                     e->passes += 1;
                     s = Sys();
@@ -1407,7 +1055,7 @@ int calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus) {
     using namespace ic;
     std::vector<Sys>& S = e->sys;
     const int batch = e->batch;
-    const double eps = std::numeric_limits<double>::epsilon();
+    const double eps = F64_EPS;
     const double steptol = std::pow(eps, 2.0 / 3.0);
     const bool dq = idahip_jacobian_dq(e->ctx) > 0;
     const long dq_evals = dq ? (idahip_band(e->ctx, nullptr, nullptr) > 0 ? dq_band_evals(e) : (long)e->n) : 0;
@@ -1708,11 +1356,11 @@ int install_roots(idaens* e, int nroots) {
     e->hy.assign(e->n, 0.0);
     e->hyp.assign(e->n, 0.0);
     for (Sys& s : e->sys) {
-        s.glo.assign(nroots, 0.0);
-        s.ghi.assign(nroots, 0.0);
-        s.grout.assign(nroots, 0.0);
-        s.iroots.assign(nroots, 0.0);
-        s.gactive.assign(nroots, 0);  // sic: false (lib.rs:373); r_check1/3 switch them on
+        s.rt.glo.assign(nroots, 0.0);
+        s.rt.ghi.assign(nroots, 0.0);
+        s.rt.grout.assign(nroots, 0.0);
+        s.rt.iroots.assign(nroots, 0.0);
+        s.rt.gactive.assign(nroots, 0);  // sic: false (lib.rs:373); r_check1/3 switch them on
     }
     return 0;
 }
@@ -1744,7 +1392,7 @@ int idaens_set_root_fn(idaens* e, int nroots, idaens_root_fn fn, void* user) {
 int idaens_get_roots(const idaens* e, int32_t* out) {
     if (!e || !out) return -1;
     for (int b = 0; b < e->batch; ++b)
-        for (int i = 0; i < e->nrtfn; ++i) out[(size_t)b * e->nrtfn + i] = (int32_t)e->sys[b].iroots[i];
+        for (int i = 0; i < e->nrtfn; ++i) out[(size_t)b * e->nrtfn + i] = (int32_t)e->sys[b].rt.iroots[i];
     return 0;
 }
 
@@ -1810,7 +1458,7 @@ int idaens_get_yp(idaens* e, double* hYP) {
 // IDAGetDky coefficients c_j^(k)(t) (lib.rs:464-508, recurrence; C IDA's loop bound, see ida_ensemble.h)
 static int get_dky_coeffs(const Sys& s, double t, int k, double* cjk) {
     if (k < 0 || k > s.kused) return IDAENS_BAD_K;
-    const double eps = std::numeric_limits<double>::epsilon();
+    const double eps = F64_EPS;
     const double tfuzz = 100.0 * eps * (std::fabs(s.tn) + std::fabs(s.hh)) * signum(s.hh);
     const double tp = s.tn - s.hused - tfuzz;
     if ((t - tp) * s.hh < 0.0) return IDAENS_BAD_T;

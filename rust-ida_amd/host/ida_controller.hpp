@@ -2,7 +2,8 @@
 // decisions taken on it. One source for both places that run it:
 //   * the host stepper (ensemble_ida.cpp, g++, pow = the platform libm's), and
 //   * the device-resident stepper (csrc/tiny_ida.hpp, hipcc, pow = glibc_pow::pow, which reproduces the same libm bit for bit),
-// so that the two cannot drift apart. Mirrors, with the reference's names:
+// so that the two cannot drift apart (the layer above it, Ida::solve's per-system flow, is ida_solve_flow.hpp, shared the same way).
+// Mirrors, with the reference's names:
 //   set_coeffs            /root/reference/src/lib.rs:722-782
 //   nonlinear_solve       /root/reference/src/lib.rs:787-812       (lsetup decision, ss resets)
 //   idaNlsConvTest        /root/reference/src/ida_nls.rs:218-266
@@ -46,6 +47,7 @@ constexpr double EPCON = 0.33;
 constexpr double XRATE = 0.25;
 constexpr int MAXNLSIT = 4;
 constexpr double RATEMAX = 0.9;
+constexpr double F64_EPS = 2.220446049250313e-16;  // f64::EPSILON
 
 enum NlsCode { NLS_SUCCESS = 0, NLS_CONV_RECVR = 1, NLS_LSETUP_RECVR = 2 };
 enum NFlag { NFLAG_NONE = 0, NFLAG_TEST_FAIL = 1, NFLAG_CONV_RECVR = 2, NFLAG_LSETUP_RECVR = 3,
@@ -396,8 +398,7 @@ IDA_HD inline void complete_step_scalars(SysCore& s, double err_k, double err_km
 // ---------------------------------------------------------------- get_solution coefficients (lib.rs:1274-1317)
 // returns 0 and fills kord/cvals/dvals, or ST_BAD_T
 IDA_HD inline int get_solution_coeffs(SysCore& s, double t, int* kord_out) {
-    const double eps = 2.220446049250313e-16;  // f64::EPSILON
-    const double tfuzz = 100.0 * eps * (IDA_FABS(s.tn) + IDA_FABS(s.hh)) * signum(s.hh);
+    const double tfuzz = 100.0 * F64_EPS * (IDA_FABS(s.tn) + IDA_FABS(s.hh)) * signum(s.hh);
     const double tp = s.tn - s.hused - tfuzz;
     if ((t - tp) * s.hh < 0.0) return ST_BAD_T;
     const int kord = (s.kused == 0) ? 1 : s.kused;

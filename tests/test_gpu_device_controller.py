@@ -396,10 +396,11 @@ def _run_with_roots(ens, touts, comps, thr, max_returns=400):
 
 @pytest.mark.parametrize("name", ["roberts", "linear_dense"])
 def test_root_finding_on_the_device_steppers(name):
-    """impl_r_check.rs on the device (ida_flow.hpp): the bracketing of idaens_set_roots' function family runs inside the
-    one-thread-per-system stepper (Roberts: the reference example's two functions) and inside the lock-step rounds (linear
-    dense, n = 24: two components crossing half of their final values). Every return -- status, t_ret, y, y', rootsfound --
-    and the counters incl. the root-function evaluations equal the host stepper's, which the oracle pins
+    """impl_r_check.rs on the device (ida_solve_flow.hpp behind ida_flow.hpp's backend): the bracketing of idaens_set_roots'
+    function family runs inside the one-thread-per-system stepper (Roberts: the reference example's two functions) and inside
+    the lock-step rounds (linear dense, n = 24: two components crossing half of their final values). Every return -- status,
+    t_ret, y, y', rootsfound -- and the counters incl. the root-function evaluations equal the host stepper's, which runs the
+    same text behind its own backend and which the oracle pins
     (tests/test_gpu_ensemble.py::test_roberts_example_with_root_finding)."""
     from idahip import problems
     if name == "roberts":
@@ -427,3 +428,26 @@ def test_root_finding_on_the_device_steppers(name):
             assert np.array_equal(x, y)
     same(state(dev), state(host))
     assert np.array_equal(dev.counter("nge"), host.counter("nge")) and (dev.counter("nge") > 0).all()
+
+
+def test_root_function_exactly_zero_at_t0_on_both_steppers():
+    """g = y1 - 1 on Roberts: y1(0) is exactly 1 for the unperturbed system, so g(t0) == 0 and r_check1 switches the function off,
+    nudges y along y' (each backend's yy_from_phi01), and switches it on again; the perturbed systems start with g(t0) < 0 and take
+    the plain path. The one-thread device stepper and the host stepper return the same everything, and nobody reports a root at t0."""
+    prob = roberts_batch(4)
+    assert prob["yy0"][0, 0] == 1.0 and (prob["yy0"][1:, 0] < 1.0).all()
+    touts = [0.4, 4.0]
+    cd, dev = make(prob, 1)
+    ch, host = make(prob, 0)
+    rd = _run_with_roots(dev, touts, [0], [1.0])
+    rh = _run_with_roots(host, touts, [0], [1.0])
+    assert dev.device_controller_active() == 1 and host.device_controller_active() == 0
+    assert len(rd) == len(rh)
+    for a, b in zip(rd, rh):
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y)
+    for r in (rd, rh):
+        st, tret = r[0][0], r[0][1]
+        assert not ((st == 2) & (tret == 0.0)).any() and (tret > 0.0).all(), (st, tret)
+    same(state(dev), state(host))
+    assert np.array_equal(dev.counter("nge"), host.counter("nge")) and (dev.counter("nge") >= 2).all()
