@@ -246,6 +246,37 @@ impl Ctx {
         unsafe { sys::idahip_krylov_fused(self.raw) == 1 }
     }
 
+    /// Krylov context: the band preconditioner of DESIGN.md section 4i with half-bandwidths (ml, mu); `None` turns it off.
+    pub fn set_krylov_band_prec(&mut self, widths: Option<(usize, usize)>) -> Result<(), Error> {
+        let (ml, mu) = widths.map_or((-1, -1), |(l, u)| (l as c_int, u as c_int));
+        let rc = unsafe { sys::idahip_set_krylov_band_prec(self.raw, ml, mu) };
+        if rc != 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(())
+    }
+
+    /// `Some((ml, mu))` with the band preconditioner on.
+    pub fn krylov_band_prec(&self) -> Option<(usize, usize)> {
+        let (mut ml, mut mu): (c_int, c_int) = (0, 0);
+        if unsafe { sys::idahip_krylov_band_prec(self.raw, &mut ml, &mut mu) } == 1 {
+            Some((ml as usize, mu as usize))
+        } else {
+            None
+        }
+    }
+
+    /// The preconditioner setup of system 0 at the context-resident yy, yp, ewt and savres -> info (0, or the 1-based column of a
+    /// zero pivot).
+    pub fn krylov_psetup(&mut self, tn: f64, cj: f64, hh: f64) -> Result<i32, Error> {
+        let (idx, mut info) = (0i32, 0i32);
+        let rc = unsafe { sys::idahip_krylov_psetup(self.raw, &tn, &cj, &hh, &mut info, &idx, 1) };
+        if rc < 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(info)
+    }
+
     pub fn n(&self) -> usize {
         self.n
     }
@@ -517,6 +548,12 @@ impl<D: DimName> HipKrylov<D> {
     pub fn with_ctx(ctx: Ctx, tn: f64, cj: f64) -> Self {
         assert!(ctx.krylov().is_some(), "HipKrylov needs a context made by Ctx::new_krylov");
         HipKrylov { ctx, tn, cj, flag: std::cell::Cell::new(0), _dim: PhantomData }
+    }
+    /// The same solver left-preconditioned by a band matrix with half-bandwidths (ml, mu). The caller runs
+    /// `ctx().krylov_psetup(tn, cj, hh)` before the first `solve`, and again whenever the point has moved too far.
+    pub fn with_band_prec(mut self, ml: usize, mu: usize) -> Result<Self, Error> {
+        self.ctx.set_krylov_band_prec(Some((ml, mu)))?;
+        Ok(self)
     }
     pub fn ctx(&mut self) -> &mut Ctx {
         &mut self.ctx

@@ -121,7 +121,11 @@ int idaens_set_root_fn(idaens* e, int nroots, idaens_root_fn fn, void* user);
  *     (a retry with a setup when the setup's data were stale, else a convergence failure of the step, counted in ncfn);
  *   - the fused first two Newton iterations are off (idaens_set_fused_newton changes nothing), idaens_device_controller_active reports 0:
  *     the host stepper runs; idaens_calc_ic is refused (negative return with a text);
- *   - solve, schedules, streams, groups, both tasks and root finding never touch the linear solver and work unchanged. */
+ *   - solve, schedules, streams, groups, both tasks and root finding never touch the linear solver and work unchanged.
+ * With the band preconditioner on (idahip_set_krylov_band_prec) the linear setup is real again: the systems that
+ * ask for one get, after their residual, one idahip_krylov_psetup call with their tn, cj and hh. Per such system: the bookkeeping
+ * above (nje stays), IDAENS_C_NPE += 1, IDAENS_C_NRE_DQ += min(ml+mu+1, n), and a zero pivot in P is a recoverable setup failure
+ * exactly as on a dense ctx (IDAENS_C_NLUFAIL counts it there). Every Newton iteration adds 1 + nli to IDAENS_C_NPS. */
 
 /* Consistent initial conditions for every system: C IDA's IDACalcIC (the reference has none, src/lib.rs:328-335), as DESIGN.md
  * section 4f defines it -- no constraints, sysindex = 1, line search always on.
@@ -197,7 +201,9 @@ enum {
     IDAENS_C_NLI = 15 /* idaLsSolve: linear iterations (0 with a direct LSolver, src/ida_ls.rs:389-400) */,
     IDAENS_C_NCFL = 16 /* idaLsSolve: linear convergence failures (src/ida_ls.rs:413-415) */,
     IDAENS_C_NRE_DQ = 17 /* residual evaluations of difference-quotient Jacobians (C IDA's nreDQ; idahip_set_jacobian_dq) */,
-    IDAENS_C_NBACKTR = 18 /* line-search backtracks of idaens_calc_ic (C IDA's nbacktr) */
+    IDAENS_C_NBACKTR = 18 /* line-search backtracks of idaens_calc_ic (C IDA's nbacktr) */,
+    IDAENS_C_NPE = 19 /* preconditioner setups of a Krylov ctx (C IDA's npe; idahip_set_krylov_band_prec) */,
+    IDAENS_C_NPS = 20 /* preconditioner solves of a Krylov ctx (C IDA's nps): 1 + nli per linear solve */
 };
 int idaens_get_counter(const idaens* e, int which, int64_t* out);
 enum { IDAENS_R_TN = 0, IDAENS_R_HUSED = 1, IDAENS_R_HH = 2, IDAENS_R_H0U = 3, IDAENS_R_TOLSF = 4 };

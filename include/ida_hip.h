@@ -151,6 +151,47 @@ int idahip_krylov_solve(idahip_ctx* ctx, const double* hTn, const double* hCj, c
  * Returns 1 if some flag is not SUCCESS (recoverable: Newton's ConvergenceRecover exit). */
 int idahip_newton_iter_krylov(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hEpsNewt, double* hDelnrm,
                               int32_t* hNli, int32_t* hFlag, const int32_t* hIdx, int nsys);
+/* ---- The BAND PRECONDITIONER of a Krylov ctx: left-preconditioned SPGMR (C IDA's IDABBDPRE with one block and left preconditioning
+ * in SPGMR; neither the reference nor a SUNDIALS copy is at hand: this text and DESIGN.md section 4i are the definition). Off by
+ * default; with it off nothing of the ctx changes.
+ *
+ * A Krylov ctx may carry a band preconditioner with half-bandwidths (ml, mu), 0 <= ml, mu < n. Storage: per system P is held in LAPACK
+ * band storage exactly as a band ctx holds its Jacobian -- ldab = 2 ml + mu + 1, [batch][ldab*n] doubles and [batch][n] int64 pivots;
+ * O((ml + mu) n) per system.
+ *   Setup (psetup): P = the band difference-quotient Jacobian of the "band:" paragraph above (same increments, same groups
+ *     g < min(ml+mu+1, n)) at the ctx-resident yy, yp, ewt, rr = savres and the caller's tn, cj, hh; then factored by the band getrf
+ *     (the register kernel for (1,1), the generic one otherwise). info = 0, or the 1-based column of a zero pivot. It costs
+ *     min(ml+mu+1, n) residual evaluations.
+ *   Solve (psolve(r) -> z): the band getrs on those factors: the interleaved forward solve, then back substitution with true division.
+ *   Left-preconditioned SPGMR: the solve of the definition above with exactly two changes.
+ *     Step 1: r = psolve(b) first, then V0_i = w_i*r_i. On the zero-iteration return (beta <= tol) x = r (C IDA copies the solver's
+ *       residual vector, which is P^-1 b). On any failure flag nothing is formed: x / delta keep what they keep without the mode.
+ *     Step 3: after Jv_i = (1/sig)*(F'_i - rr_i): u = psolve(Jv), then V_{l+1},i = w_i*u_i.
+ *   kdot, Gram-Schmidt, Givens, rho, the flags, steps 4 and 5, x_i = xc_i/w_i, the tolerance, the missing 2/(1+cjratio) scaling and
+ *   the missing re-orthogonalisation are unchanged. rho is now the norm of the preconditioned scaled residual. A solve performs
+ *   1 + nli preconditioner solves.
+ * The band kernels equal the dense LU by value (-0.0 == +0.0) and nothing in SPGMR reads the sign of a zero.
+ *
+ * idahip_set_krylov_band_prec: turns the mode on and allocates the storage; ml = mu = -1 turns it off and frees it. Kinds
+ * IDAHIP_HEAT1D and IDAHIP_HOST_CALLBACK (idahip_set_host_residual), the kinds with a band difference quotient; IDAHIP_LINEAR_DENSE is
+ * refused (-2: a random dense Jacobian has no band approximation worth factoring), and so are a ctx that is not a Krylov ctx and
+ * widths out of range. With the mode on, idahip_krylov_solve and idahip_newton_iter_krylov run the preconditioned definition; for a
+ * listed system without factors yet (no psetup, no upload) they are refused (-2, nothing launched). The four stand-alone calls below
+ * are refused the same way on a ctx with the mode off. */
+int idahip_set_krylov_band_prec(idahip_ctx* ctx, int ml, int mu);
+/* 1 with the mode on (*ml, *mu set when non-null), 0 otherwise, -1 for a null ctx */
+int idahip_krylov_band_prec(const idahip_ctx* ctx, int* ml, int* mu);
+/* psetup for the listed systems: hTn, hCj, hHh, hInfo [nsys]. Heat: one device pass; host callbacks: the pack / host residual /
+ * scatter round trip of a band ctx, once per group. Returns 1 if some info != 0. */
+int idahip_krylov_psetup(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx,
+                         int nsys);
+/* psolve alone (C IDA's IDABBDPrecSolve): hR, hZ host arrays [nsys][n] by list position; the device function the solve kernels call */
+int idahip_krylov_psolve(idahip_ctx* ctx, const double* hR, double* hZ, const int32_t* hIdx, int nsys);
+/* The factors of one system in idahip_download_lu_band's format (hAB: ldab*n doubles, hPiv: n pivots, 0-based rows). Upload is the
+ * user-supplied preconditioner: any non-singular factored band matrix of the ctx's widths is a valid P; pivots outside
+ * j <= piv[j] <= min(n-1, j+ml) are refused. */
+int idahip_krylov_download_prec(idahip_ctx* ctx, int sys, double* hAB, int64_t* hPiv);
+int idahip_krylov_upload_prec(idahip_ctx* ctx, int sys, const double* hAB, const int64_t* hPiv);
 /* `count` HIP streams on `device` for contexts that are to work SIDE BY SIDE (idaens_stream_group, ida_ensemble.h). The HIP
  * runtime maps its streams onto a few hardware queues as it sees fit, and two streams on one queue take turns; this call
  * creates streams and keeps those a probe kernel shows to run concurrently with every stream kept before. streams_out[count]

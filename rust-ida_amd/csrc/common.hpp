@@ -85,6 +85,11 @@ struct idahip_ctx {
     double* kry_stage = nullptr;  // [batch][3][n] perturbed point and its residual (split path)
     double *kry_b = nullptr, *kry_x = nullptr;  // [batch][n] right-hand sides and solutions of idahip_krylov_solve, by list position
     std::vector<double> kry_host;               // host mirror of kry_stage (host-callback residuals)
+    // band preconditioner of a Krylov ctx (idahip_set_krylov_band_prec): factors and pivots as a band ctx holds them
+    int kry_prec = 0, kry_pml = 0, kry_pmu = 0, kry_pldab = 0;
+    double* kry_pab = nullptr;       // [batch][kry_pldab * n]
+    int64_t* kry_ppiv = nullptr;     // [batch][n]
+    std::vector<uint8_t> kry_pready; // [batch] a psetup or an upload has given this system its factors
     int kry_last_nli = 0;            // sum of the iterations / maximum of the residual norms over the last solve call's list
     double kry_last_resnorm = 0.0;
     double *ic_y = nullptr, *ic_yp = nullptr;  // [batch][n] initial conditions kept for idahip_restore_initial (lazy)

@@ -249,7 +249,7 @@ int idahip_destroy(idahip_ctx* c) {
     DevGuard dev_guard__(c);
     if (!c) return 0;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* ptrs[] = {c->kry_V, c->kry_st, c->kry_stage, c->kry_b, c->kry_x, c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
+    void* ptrs[] = {c->kry_pab, c->kry_ppiv, c->kry_V, c->kry_st, c->kry_stage, c->kry_b, c->kry_x, c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
                     c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->d_constr, c->ic_y,
                     c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d};
@@ -896,14 +896,15 @@ int callback_dq_jac(idahip_ctx* c, const DqArgs& d0, const double* hTn, const in
     if (!hTn || !hIdx) return fail(c, -2, "a host-callback DQ Jacobian needs the systems' tn and ids on the host");
     const size_t per = 3 * (size_t)n;
     const size_t copies = std::max<size_t>(1, ((size_t)32 << 20) / (per * sizeof(double)));  // staging <= 32 MB (or one copy)
-    const int ngroups = (int)dq_evals(c);
+    const bool band = d0.ld > 0;  // (a band ctx, or the band preconditioner of a Krylov ctx)
+    const int ngroups = band ? std::min(d0.ml + d0.mu + 1, n) : n;
     const int msys = (int)std::min<size_t>((size_t)nsys, copies);
-    const int G = c->band ? 1 : (int)std::max<size_t>(1, std::min<size_t>((size_t)n, copies / msys));
+    const int G = band ? 1 : (int)std::max<size_t>(1, std::min<size_t>((size_t)n, copies / msys));
     int rc = dq_grow(c, &c->dq_stage, &c->dq_stage_cap, (size_t)msys * G * per);
     if (rc) return rc;
     if (c->cb_host.size() < (size_t)msys * G * per) c->cb_host.resize((size_t)msys * G * per);
     double* h = c->cb_host.data();
-    const size_t mat = c->band ? (size_t)c->ldab * n : (size_t)n * n;
+    const size_t mat = band ? (size_t)d0.ld * n : (size_t)n * n;
     for (int s0 = 0; s0 < nsys; s0 += msys) {
         const int m = std::min(msys, nsys - s0);
         DqArgs d = d0;
@@ -1348,11 +1349,14 @@ int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* h
     a.n = n; a.maxl = c->kry_maxl;
     a.params = c->params; a.A = c->A; a.Bm = c->B; a.C = c->C;
     a.skip = nullptr;
+    const bool prec = c->kry_prec != 0;
+    a.pab = c->kry_pab; a.ppiv = (const long long*)c->kry_ppiv; a.pml = c->kry_pml; a.pmu = c->kry_pmu;
     const dim3 grid(nsys), blk(KRY_T);
     if (c->kry_fused) {
         const size_t shm = kry_lds_bytes(n, 3);
-        if (c->kind == IDAHIP_HEAT1D) hipLaunchKernelGGL(krylov_fused_kernel<IDAHIP_HEAT1D>, grid, blk, shm, c->stream, a);
-        else if (c->kind == IDAHIP_LINEAR_DENSE) hipLaunchKernelGGL(krylov_fused_kernel<IDAHIP_LINEAR_DENSE>, grid, blk, shm, c->stream, a);
+        if (c->kind == IDAHIP_HEAT1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, true>), grid, blk, shm, c->stream, a);
+        else if (c->kind == IDAHIP_HEAT1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, false>), grid, blk, shm, c->stream, a);
+        else if (c->kind == IDAHIP_LINEAR_DENSE) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_LINEAR_DENSE, false>), grid, blk, shm, c->stream, a);
         else return fail(c, -2, "no fused Krylov kernel for problem kind %d", (int)c->kind);
         return post_launch(c, "krylov_fused");
     }
@@ -1365,7 +1369,8 @@ int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* h
         return 0;
     };
     int rc;
-    hipLaunchKernelGGL(krylov_begin_kernel, grid, blk, shm1, c->stream, a);
+    if (prec) hipLaunchKernelGGL(krylov_begin_kernel<true>, grid, blk, shm1, c->stream, a);
+    else hipLaunchKernelGGL(krylov_begin_kernel<false>, grid, blk, shm1, c->stream, a);
     if ((rc = post_launch(c, "krylov_begin"))) return rc;
     if ((rc = fetch_done())) return rc;
     a.skip = a.done;  // a system whose loop has ended is left alone by the launches that follow
@@ -1392,11 +1397,13 @@ int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* h
         } else {
             hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_LINEAR_DENSE>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
         }
-        hipLaunchKernelGGL(krylov_step_kernel, grid, blk, shm1, c->stream, a, l);
+        if (prec) hipLaunchKernelGGL(krylov_step_kernel<true>, grid, blk, shm1, c->stream, a, l);
+        else hipLaunchKernelGGL(krylov_step_kernel<false>, grid, blk, shm1, c->stream, a, l);
         if ((rc = post_launch(c, "krylov_step"))) return rc;
         if ((rc = fetch_done())) return rc;
     }
-    hipLaunchKernelGGL(krylov_finish_kernel, grid, blk, shm1, c->stream, a);
+    if (prec) hipLaunchKernelGGL(krylov_finish_kernel<true>, grid, blk, shm1, c->stream, a);
+    else hipLaunchKernelGGL(krylov_finish_kernel<false>, grid, blk, shm1, c->stream, a);
     return post_launch(c, "krylov_finish");
 }
 
@@ -1450,7 +1457,168 @@ int krylov_call(idahip_ctx* c, bool newton, const double* hTn, const double* hCj
     return any;
 }
 
+// a preconditioned ctx solves only systems that a psetup or an upload has given factors
+int krylov_prec_ready(idahip_ctx* c, const char* who, const int32_t* hIdx, int nsys) {
+    if (!c->kry_prec) return 0;
+    for (int s = 0; s < nsys; ++s)
+        if (!c->kry_pready[hIdx[s]])
+            return fail(c, -2, "%s: system %d has no preconditioner yet (idahip_krylov_psetup or idahip_krylov_upload_prec first)", who, hIdx[s]);
+    return 0;
+}
+
+// the four stand-alone preconditioner calls: a Krylov ctx with the mode on
+int krylov_prec_on(idahip_ctx* c, const char* who) {
+    if (!c->krylov) return fail(c, -2, "%s: not a Krylov ctx (idahip_create_krylov)", who);
+    if (!c->kry_prec) return fail(c, -2, "%s: the ctx has no band preconditioner (idahip_set_krylov_band_prec)", who);
+    return 0;
+}
+
 }  // namespace
+
+int idahip_set_krylov_band_prec(idahip_ctx* c, int ml, int mu) {
+    DevGuard dev_guard__(c);
+    if (!c) return -1;
+    if (c->band) return fail(c, -2, "idahip_set_krylov_band_prec on a band ctx: not a Krylov ctx (idahip_create_krylov)");
+    if (!c->krylov) return fail(c, -2, "idahip_set_krylov_band_prec on a dense ctx: not a Krylov ctx (idahip_create_krylov)");
+    const bool off = ml == -1 && mu == -1;
+    if (!off && c->kind == IDAHIP_LINEAR_DENSE)
+        return fail(c, -2, "idahip_set_krylov_band_prec: IDAHIP_LINEAR_DENSE has no band difference-quotient Jacobian (IDAHIP_HEAT1D or IDAHIP_HOST_CALLBACK)");
+    if (!off && (ml < 0 || mu < 0 || ml >= c->n || mu >= c->n))
+        return fail(c, -2, "idahip_set_krylov_band_prec: bandwidths ml = %d, mu = %d outside 0 <= ml, mu < n (-1, -1 turns the mode off)", ml, mu);
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->kry_pab) (void)hipFree(c->kry_pab);
+    if (c->kry_ppiv) (void)hipFree(c->kry_ppiv);
+    c->kry_pab = nullptr; c->kry_ppiv = nullptr;
+    c->kry_prec = 0; c->kry_pml = c->kry_pmu = c->kry_pldab = 0;
+    c->kry_pready.clear();
+    if (off) return 0;
+    const int ldab = 2 * ml + mu + 1;
+    const size_t bn = (size_t)c->batch * c->n;
+    if (dalloc(c, &c->kry_pab, bn * ldab) || dalloc(c, &c->kry_ppiv, bn)) {
+        if (c->kry_pab) (void)hipFree(c->kry_pab);
+        c->kry_pab = nullptr; c->kry_ppiv = nullptr;
+        return fail(c, -100, "band preconditioner storage (%zu doubles)", bn * ldab);
+    }
+    IDAHIP_HIP(c, hipMemsetAsync(c->kry_pab, 0, bn * ldab * sizeof(double), c->stream));
+    IDAHIP_HIP(c, hipMemsetAsync(c->kry_ppiv, 0, bn * sizeof(int64_t), c->stream));
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    c->kry_prec = 1; c->kry_pml = ml; c->kry_pmu = mu; c->kry_pldab = ldab;
+    c->kry_pready.assign((size_t)c->batch, 0);
+    return 0;
+}
+
+int idahip_krylov_band_prec(const idahip_ctx* c, int* ml, int* mu) {
+    if (!c) return -1;
+    if (c->kry_prec) {
+        if (ml) *ml = c->kry_pml;
+        if (mu) *mu = c->kry_pmu;
+    }
+    return c->kry_prec;
+}
+
+int idahip_krylov_psetup(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if ((rc = krylov_prec_on(c, "idahip_krylov_psetup"))) return rc;
+    if (!hTn || !hCj || !hHh || !hInfo) return fail(c, -2, "null argument");
+    if (nsys == 0) return 0;
+    const int n = c->n;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    const double* d_cj = ap.in(hCj, nsys);
+    const double* d_hh = ap.in(hHh, nsys);
+    if ((rc = ap.upload())) return rc;
+    DqArgs d;
+    d.yy = c->yy; d.yp = c->yp; d.ewt = c->ewt; d.rr = c->savres;
+    d.idx = d_idx; d.cj = d_cj; d.hh = d_hh; d.skip = nullptr;
+    d.out = c->kry_pab; d.compact = 0; d.n = n;
+    d.ml = c->kry_pml; d.mu = c->kry_pmu; d.ld = c->kry_pldab;
+    {
+        KTimer kt(c, IDAHIP_K_JAC, nsys);
+        if (c->kind == IDAHIP_HOST_CALLBACK) {
+            if ((rc = callback_dq_jac(c, d, hTn, hIdx, nsys))) return rc;
+        } else {  // (idahip_set_krylov_band_prec: IDAHIP_HEAT1D is the only device kind)
+            int chunks = 1;
+            while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
+            hipLaunchKernelGGL(heat_band_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
+            if ((rc = post_launch(c, "band DQ jac (preconditioner)"))) return rc;
+        }
+    }
+    {
+        KTimer kt(c, IDAHIP_K_LU, nsys);
+        if ((rc = band_factor(c, c->kry_pab, (long)c->kry_pldab * n, c->kry_ppiv, n, c->kry_pml, c->kry_pmu, d_idx, nsys))) return rc;
+    }
+    std::vector<int32_t> info(c->batch);
+    IDAHIP_HIP(c, hipMemcpyAsync(info.data(), c->lu_info, sizeof(int32_t) * c->batch, hipMemcpyDeviceToHost, c->stream));
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    int any = 0;
+    for (int s = 0; s < nsys; ++s) {
+        hInfo[s] = info[hIdx[s]];
+        any |= hInfo[s] != 0;
+        c->kry_pready[hIdx[s]] = 1;
+    }
+    return any ? 1 : 0;
+}
+
+int idahip_krylov_psolve(idahip_ctx* c, const double* hR, double* hZ, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if ((rc = krylov_prec_on(c, "idahip_krylov_psolve"))) return rc;
+    if (!hR || !hZ) return fail(c, -2, "null argument");
+    if ((rc = krylov_prec_ready(c, "idahip_krylov_psolve", hIdx, nsys))) return rc;
+    if (nsys == 0) return 0;
+    const int n = c->n;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    if ((rc = ap.upload())) return rc;
+    IDAHIP_HIP(c, hipMemcpyAsync(c->kry_b, hR, sizeof(double) * nsys * n, hipMemcpyHostToDevice, c->stream));
+    {
+        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
+        hipLaunchKernelGGL(krylov_psolve_kernel, dim3(nsys), dim3(KRY_T), sizeof(double) * n, c->stream, (const double*)c->kry_pab,
+                           (const long long*)c->kry_ppiv, n, c->kry_pml, c->kry_pmu, (const double*)c->kry_b, c->kry_x, d_idx);
+        if ((rc = post_launch(c, "krylov_psolve"))) return rc;
+    }
+    IDAHIP_HIP(c, hipMemcpyAsync(hZ, c->kry_x, sizeof(double) * nsys * n, hipMemcpyDeviceToHost, c->stream));
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    return ap.finish_async();
+}
+
+int idahip_krylov_download_prec(idahip_ctx* c, int sys, double* hAB, int64_t* hPiv) {
+    DevGuard dev_guard__(c);
+    if (!c) return -1;
+    int rc = krylov_prec_on(c, "idahip_krylov_download_prec");
+    if (rc) return rc;
+    if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t ne = (size_t)c->kry_pldab * c->n;
+    if (hAB) IDAHIP_HIP(c, hipMemcpy(hAB, c->kry_pab + sys * ne, sizeof(double) * ne, hipMemcpyDeviceToHost));
+    if (hPiv) IDAHIP_HIP(c, hipMemcpy(hPiv, c->kry_ppiv + (size_t)sys * c->n, sizeof(int64_t) * c->n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int idahip_krylov_upload_prec(idahip_ctx* c, int sys, const double* hAB, const int64_t* hPiv) {
+    DevGuard dev_guard__(c);
+    if (!c) return -1;
+    int rc = krylov_prec_on(c, "idahip_krylov_upload_prec");
+    if (rc) return rc;
+    if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
+    if (!hAB || !hPiv) return fail(c, -2, "null argument");
+    const int n = c->n;
+    for (int j = 0; j < n; ++j) {  // the solves index the vector by the pivots: dgbtrf's range, or nothing is uploaded
+        const int64_t hi = std::min<int64_t>((int64_t)n - 1, (int64_t)j + c->kry_pml);
+        if (hPiv[j] < j || hPiv[j] > hi) return fail(c, -2, "pivot %lld of column %d outside [%d, %lld]", (long long)hPiv[j], j, j, (long long)hi);
+    }
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t ne = (size_t)c->kry_pldab * n;
+    IDAHIP_HIP(c, hipMemcpy(c->kry_pab + sys * ne, hAB, sizeof(double) * ne, hipMemcpyHostToDevice));
+    IDAHIP_HIP(c, hipMemcpy(c->kry_ppiv + (size_t)sys * n, hPiv, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    c->kry_pready[sys] = 1;
+    return 0;
+}
 
 int idahip_krylov_solve(idahip_ctx* c, const double* hTn, const double* hCj, const double* hTol, const double* hB, double* hX, int32_t* hNli,
                         int32_t* hFlag, double* hResNorm, const int32_t* hIdx, int nsys) {
@@ -1459,6 +1627,7 @@ int idahip_krylov_solve(idahip_ctx* c, const double* hTn, const double* hCj, con
     if (rc) return rc;
     if (!c->krylov) return fail(c, -2, "idahip_krylov_solve: not a Krylov ctx (idahip_create_krylov)");
     if (!hTn || !hCj || !hTol || !hB || !hX || !hNli || !hFlag || !hResNorm) return fail(c, -2, "null argument");
+    if ((rc = krylov_prec_ready(c, "idahip_krylov_solve", hIdx, nsys))) return rc;
     if (nsys == 0) return 0;
     return krylov_call(c, false, hTn, hCj, hTol, hB, hX, nullptr, hNli, hFlag, hResNorm, hIdx, nsys);
 }
@@ -1470,6 +1639,7 @@ int idahip_newton_iter_krylov(idahip_ctx* c, const double* hTn, const double* hC
     if (rc) return rc;
     if (!c->krylov) return fail(c, -2, "idahip_newton_iter_krylov: not a Krylov ctx (idahip_create_krylov)");
     if (!hTn || !hCj || !hEpsNewt || !hDelnrm || !hNli || !hFlag) return fail(c, -2, "null argument");
+    if ((rc = krylov_prec_ready(c, "idahip_newton_iter_krylov", hIdx, nsys))) return rc;
     if (nsys == 0) return 0;
     std::vector<double> tol((size_t)nsys);
     for (int s = 0; s < nsys; ++s) tol[s] = idakry::tolerance(c->n, hEpsNewt[s]);

@@ -18,10 +18,26 @@
 // (one launch per step, the host loops over l: host-callback residuals, and the cross-check of the fused kernel).
 // The perturbed residual is computed in the operation order of the problem's residual kernel (problem_kernels.hpp), as
 // dq_kernels.hpp does. -ffp-contract=off: no FMA. All per-system scalars are written with ordinary vector stores from plain C++.
+//
+// Band preconditioner (idahip_set_krylov_band_prec; DESIGN.md section 4i and include/ida_hip.h carry the same text): C IDA's IDABBDPRE
+// with one block, applied on the left. Per system P is held in LAPACK band storage with half-bandwidths (ml, mu), ldab = 2 ml + mu + 1,
+// [batch][ldab * n] doubles and [batch][n] int64 pivots, exactly as a band ctx holds its Jacobian (band_kernels.hpp).
+//   psetup:     P = the band DQ Jacobian of dq_kernels.hpp (same increments, groups g < min(ml + mu + 1, n)) at the ctx's yy, yp, ewt,
+//               rr = savres and the caller's tn, cj, hh, factored by band_kernels.hpp's getrf; info = 0 | 1-based zero-pivot column.
+//   psolve(r):  band_kernels.hpp's getrs on those factors (interleaved forward solve, back substitution with true division).
+//   the solve:  the definition above with two changes --
+//     1. r = psolve(b); V0 = w*r; the zero-iteration return gives x = r (r is parked in the V_1 slot, unused until iteration 0).
+//     3. after Jv = (1/sig)*(F' - rr): u = psolve(Jv); V_{l+1} = w*u.
+//   Everything else is unchanged; rho is the norm of the preconditioned scaled residual; a solve performs 1 + nli psolves.
+// kry_psolve below is the one device function behind all of it: the vector lives in LDS and is solved in place. (1, 1): one lane runs
+// band_getrs_reg<1, 1> (its factor loads are prefetched off the dependent chain). (0, 0): element-wise division. Every other width:
+// the workgroup shares each step's independent row updates, one row per lane, with a workgroup barrier between a step's reads and
+// its writes and between its writes and the next step's reads; every entry receives band_getrs_generic's subtractions in its order.
 #pragma once
 #include "../host/krylov_scalar.hpp"
 #include "common.hpp"
 #include "solve_kernels.hpp"
+#include "band_kernels.hpp"
 
 namespace idahip {
 
@@ -51,6 +67,10 @@ struct KryArgs {
     int n, maxl;
     const double* params;  // heat: [batch]
     const double *A, *Bm, *C;  // linear dense
+    // band preconditioner (the kernels instantiated with PREC only): factors [batch][(2 pml + pmu + 1) * n], pivots [batch][n]
+    const double* pab;
+    const long long* ppiv;
+    int pml, pmu;
 };
 
 constexpr int KRY_T = 256;
@@ -85,7 +105,56 @@ __device__ __forceinline__ double kry_kdot(const double* __restrict__ x, const d
     return r;
 }
 
-// step 1: (newton: delta = -delta, b = delta;) V0 = w*b; returns beta
+// x <- P^-1 x for one system, x: n doubles of LDS (band_kernels.hpp's getrs on the factors A / pivots P). Called by every thread of
+// the workgroup; barriers on entry (x is complete) and on exit (x is the solution).
+__device__ __forceinline__ void kry_psolve(const double* __restrict__ A, const long long* __restrict__ P, int n, int ml, int mu, double* x) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    if (ml == 1 && mu == 1) {
+        if (t == 0) band_getrs_reg<1, 1>(A, P, n, x, [&](int i) { return x[i]; });
+        __syncthreads();
+        return;
+    }
+    const int kv = ml + mu, ld = 2 * ml + mu + 1;
+    if (kv == 0) {  // a diagonal P: no elimination, pivots j
+        for (int i = t; i < n; i += KRY_T) x[i] = x[i] / A[band_at(ld, kv, i, i)];
+        __syncthreads();
+        return;
+    }
+    // forward: step j swaps x_j / x_l (l = piv[j], j <= l <= j + lm) and eliminates with column j of L. Every lane reads x_j and x_l,
+    // then the rows j + 1 .. j + lm are updated one per lane (row l from the swapped-in x_j) and lane 0 stores the swapped-in x_l
+    for (int j = 0; j < n && ml > 0; ++j) {
+        const int lm = (n - 1 - j) < ml ? (n - 1 - j) : ml;
+        if (lm == 0) break;  // the last column: nothing below it, no swap
+        const int l = (int)P[j];
+        const double xj = x[j], bj = x[l];
+        __syncthreads();  // x_j and x_l are read
+        for (int r = 1 + t; r <= lm; r += KRY_T) {
+            const int i = j + r;
+            const double v = (i == l) ? xj : x[i];
+            x[i] = v - A[band_at(ld, kv, i, j)] * bj;
+        }
+        if (t == 0) x[j] = bj;
+        __syncthreads();  // the step's writes are visible
+    }
+    // backward: x_k = x_k / U(k, k), then the rows k - kv .. k - 1 one per lane
+    for (int k = n - 1; k >= 0; --k) {
+        const double xk = x[k] / A[band_at(ld, kv, k, k)];
+        const int lo = k - kv > 0 ? k - kv : 0;
+        __syncthreads();  // x_k is read
+        for (int i = lo + t; i < k; i += KRY_T) x[i] = x[i] - A[band_at(ld, kv, i, k)] * xk;
+        if (t == 0) x[k] = xk;
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void kry_psolve(const KryArgs& a, int b, double* x) {
+    const long ldab = 2 * a.pml + a.pmu + 1;
+    kry_psolve(a.pab + (long)b * ldab * a.n, a.ppiv + (long)b * a.n, a.n, a.pml, a.pmu, x);
+}
+
+// step 1: (newton: delta = -delta, b = delta;) V0 = w*b; returns beta. PREC: r = psolve(b) in sp, V0 = w*r, r parked in the V_1 slot
+template <bool PREC>
 __device__ __forceinline__ double kry_start(const KryArgs& a, int s, int b, double* sp, double* part) {
     const int n = a.n;
     const long vb = (long)b * n;
@@ -98,7 +167,17 @@ __device__ __forceinline__ double kry_start(const KryArgs& a, int s, int b, doub
         } else {
             bi = a.b[(long)s * n + i];
         }
-        V0[i] = a.ewt[vb + i] * bi;
+        if constexpr (PREC) sp[i] = bi;
+        else V0[i] = a.ewt[vb + i] * bi;
+    }
+    if constexpr (PREC) {
+        kry_psolve(a, b, sp);
+        double* V1 = V0 + n;
+        for (int i = threadIdx.x; i < n; i += KRY_T) {
+            const double r = sp[i];
+            V1[i] = r;
+            V0[i] = a.ewt[vb + i] * r;
+        }
     }
     __syncthreads();
     return sqrt(kry_kdot(V0, V0, n, sp, part));
@@ -172,6 +251,16 @@ __device__ __forceinline__ double kry_jv(const KryArgs& a, long e, double f) {
     const double jv = inv_sig * (f - a.rr[e]);
     return a.ewt[e] * jv;
 }
+// PREC: Jv alone (into sp); then u = psolve(Jv) and V_{l+1} = w*u
+__device__ __forceinline__ double kry_jv_raw(const KryArgs& a, long e, double f) {
+    const double inv_sig = 1.0 / idakry::dq_sigma(a.n);
+    return inv_sig * (f - a.rr[e]);
+}
+__device__ __forceinline__ void kry_prec_column(const KryArgs& a, int b, double* sp, double* __restrict__ Vn) {
+    kry_psolve(a, b, sp);
+    const long vb = (long)b * a.n;
+    for (int i = threadIdx.x; i < a.n; i += KRY_T) Vn[i] = a.ewt[vb + i] * sp[i];
+}
 
 // Modified Gram-Schmidt of V_{l+1} against V_0..V_l, hn, the Givens update of column l by one lane, the convergence decision and
 // (not converged) the normalisation of V_{l+1}; the last column without convergence ends the loop. k: the system's state (LDS or
@@ -204,6 +293,7 @@ __device__ __forceinline__ int kry_orthogonalise(const KryArgs& a, int b, int l,
 }
 
 // steps 4 and 5 and the results of list position s; newton: the Newton body's tail (ee += delta, the sum of the WRMS norm)
+template <bool PREC>
 __device__ __forceinline__ void kry_finish(const KryArgs& a, int s, int b, idakry::Sys* k, double* sp, double* part) {
     const int n = a.n;
     const long vb = (long)b * n;
@@ -224,6 +314,8 @@ __device__ __forceinline__ void kry_finish(const KryArgs& a, int s, int b, idakr
             xi = xc / a.ewt[vb + i];
         } else {
             xi = a.newton ? a.delta[vb + i] : a.b[(long)s * n + i];  // x = b (the zero-iteration return; a failure forms nothing)
+            if constexpr (PREC)
+                if (flag == idakry::SUCCESS) xi = Vb[n + i];  // the zero-iteration return: x = P^-1 b, parked in the V_1 slot
         }
         if (!a.newton) {
             xo[i] = xi;
@@ -252,7 +344,7 @@ __device__ __forceinline__ void kry_lds(double* sm, idakry::Sys** k, double** pa
 // ---------------------------------------------------------------------------------------------- fused path
 // The whole solve of one listed system in one launch (IDAHIP_HEAT1D, IDAHIP_LINEAR_DENSE). Dynamic LDS: the state and the partials,
 // then 3 n doubles (products, y', yp'); the basis lives in a.V and stays in L2.
-template <int KIND>
+template <int KIND, bool PREC>
 __global__ __launch_bounds__(KRY_T) void krylov_fused_kernel(KryArgs a) {
     extern __shared__ __align__(16) double sm[];
     idakry::Sys* k;
@@ -266,7 +358,7 @@ __global__ __launch_bounds__(KRY_T) void krylov_fused_kernel(KryArgs a) {
     const long vb = (long)b * n;
     double* Vb = a.V + (long)b * (a.maxl + 1) * n;
     const double cj = a.cj[s];
-    const double beta = kry_start(a, s, b, sp, part);
+    const double beta = kry_start<PREC>(a, s, b, sp, part);
     if (threadIdx.x == 0) part[65] = idakry::begin(*k, beta, a.tol[s]) ? 1.0 : 0.0;
     __syncthreads();
     int done = part[65] != 0.0;
@@ -276,14 +368,20 @@ __global__ __launch_bounds__(KRY_T) void krylov_fused_kernel(KryArgs a) {
         kry_point(a, b, Vb + (long)l * n, cj, sy, syp);
         __syncthreads();
         double* Vn = Vb + (long)(l + 1) * n;
-        kry_residual<KIND>(a, b, sy, syp, [&](int i, double f) { Vn[i] = kry_jv(a, vb + i, f); });
+        if constexpr (PREC) {  // the products buffer is free here: Jv into it, solved in place
+            kry_residual<KIND>(a, b, sy, syp, [&](int i, double f) { sp[i] = kry_jv_raw(a, vb + i, f); });
+            kry_prec_column(a, b, sp, Vn);
+        } else {
+            kry_residual<KIND>(a, b, sy, syp, [&](int i, double f) { Vn[i] = kry_jv(a, vb + i, f); });
+        }
         done = kry_orthogonalise(a, b, l, k, sp, part);
     }
-    kry_finish(a, s, b, k, sp, part);
+    kry_finish<PREC>(a, s, b, k, sp, part);
 }
 
 // ---------------------------------------------------------------------------------------------- split path
 // begin: steps 1 and 2; done[s] = 1 when the solve has ended there
+template <bool PREC>
 __global__ __launch_bounds__(KRY_T) void krylov_begin_kernel(KryArgs a) {
     extern __shared__ __align__(16) double sm[];
     idakry::Sys* kl;
@@ -292,7 +390,7 @@ __global__ __launch_bounds__(KRY_T) void krylov_begin_kernel(KryArgs a) {
     const int s = blockIdx.x;
     const int b = a.idx[s];
     idakry::Sys* k = a.st + b;
-    const double beta = kry_start(a, s, b, sp, part);
+    const double beta = kry_start<PREC>(a, s, b, sp, part);
     if (threadIdx.x == 0) {
         const bool ended = idakry::begin(*k, beta, a.tol[s]);
         part[65] = ended ? 1.0 : 0.0;
@@ -332,6 +430,7 @@ __global__ __launch_bounds__(KRY_T) void krylov_res_kernel(KryArgs a) {
 }
 
 // step: Jv and its scaling from the staged residual, then the rest of iteration l; done[s] = 1 when the loop has ended
+template <bool PREC>
 __global__ __launch_bounds__(KRY_T) void krylov_step_kernel(KryArgs a, int l) {
     extern __shared__ __align__(16) double sm[];
     idakry::Sys* kl;
@@ -344,11 +443,17 @@ __global__ __launch_bounds__(KRY_T) void krylov_step_kernel(KryArgs a, int l) {
     const long vb = (long)b * n;
     const double* f = a.stage + (long)s * 3 * n + 2 * n;
     double* Vn = a.V + ((long)b * (a.maxl + 1) + l + 1) * n;
-    for (int i = threadIdx.x; i < n; i += KRY_T) Vn[i] = kry_jv(a, vb + i, f[i]);
+    if constexpr (PREC) {
+        for (int i = threadIdx.x; i < n; i += KRY_T) sp[i] = kry_jv_raw(a, vb + i, f[i]);
+        kry_prec_column(a, b, sp, Vn);
+    } else {
+        for (int i = threadIdx.x; i < n; i += KRY_T) Vn[i] = kry_jv(a, vb + i, f[i]);
+    }
     const int done = kry_orthogonalise(a, b, l, a.st + b, sp, part);
     if (threadIdx.x == 0) a.done[s] = done;
 }
 
+template <bool PREC>
 __global__ __launch_bounds__(KRY_T) void krylov_finish_kernel(KryArgs a) {
     extern __shared__ __align__(16) double sm[];
     idakry::Sys* kl;
@@ -356,7 +461,20 @@ __global__ __launch_bounds__(KRY_T) void krylov_finish_kernel(KryArgs a) {
     kry_lds(sm, &kl, &part, &sp);
     const int s = blockIdx.x;
     const int b = a.idx[s];
-    kry_finish(a, s, b, a.st + b, sp, part);
+    kry_finish<PREC>(a, s, b, a.st + b, sp, part);
+}
+
+// psolve alone (idahip_krylov_psolve): z = P^-1 r for the listed systems, r and z [nsys][n] by list position (dynamic LDS: n doubles)
+__global__ __launch_bounds__(KRY_T) void krylov_psolve_kernel(const double* __restrict__ pab, const long long* __restrict__ ppiv, int n, int ml,
+                                                              int mu, const double* __restrict__ r, double* __restrict__ z,
+                                                              const int* __restrict__ idx) {
+    extern __shared__ __align__(16) double sm[];
+    const int s = blockIdx.x;
+    const int b = idx[s];
+    const long ldab = 2 * ml + mu + 1;
+    for (int i = threadIdx.x; i < n; i += KRY_T) sm[i] = r[(long)s * n + i];
+    kry_psolve(pab + (long)b * ldab * n, ppiv + (long)b * n, n, ml, mu, sm);
+    for (int i = threadIdx.x; i < n; i += KRY_T) z[(long)s * n + i] = sm[i];
 }
 
 }  // namespace idahip

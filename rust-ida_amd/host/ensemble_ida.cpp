@@ -67,6 +67,7 @@ void copy_roots(D& d, const S& s, int nr) {  // between RootVecs and the device 
 struct Sys : SysCore {
     RootVecs rt;
     long nbacktr = 0;  // idaens_calc_ic: line-search backtracks (host-only: SysCore's size is part of the device steppers' ABI)
+    long npe = 0, nps = 0;  // band preconditioner of a Krylov ctx: setups and solves (C IDA's npe, nps; host-only as well)
 };
 
 }  // namespace
@@ -228,7 +229,8 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
             L.clear(); P.clear();
             // a DQ ctx (idahip_set_jacobian_dq): sys for all of them, then the setups with their step sizes
             const bool dq = idahip_jacobian_dq(e->ctx) > 0;
-            // a Krylov ctx (idahip_create_krylov): sys for all of them; its linear setup forms and factors nothing and cannot fail
+            // a Krylov ctx (idahip_create_krylov): sys for all of them; without a preconditioner its linear setup forms and factors
+            // nothing and cannot fail
             const bool kry = idahip_krylov(e->ctx, nullptr) == 1;
             for (int b : R) (S[b].call_lsetup && !dq && !kry ? L : P).push_back(b);
             if (!P.empty()) {
@@ -237,9 +239,31 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
                 ENS_CALL(e, idahip_nls_sys(e->ctx, tn.data(), cj.data(), 1, P.data(), (int)P.size()));
             }
             for (int b : R) S[b].nre += 1;
+            int pml = 0, pmu = 0;
+            const bool prec = kry && idahip_krylov_band_prec(e->ctx, &pml, &pmu) == 1;
             if (kry)
                 for (int b : R)
                     if (S[b].call_lsetup) after_lsetup_nojac(S[b]);  // idaNlsLSetup's bookkeeping; no Jacobian: nje stays
+            if (prec) {
+                // the band preconditioner: P is formed at the residual that sys has just left and factored; a zero
+                // pivot is the recoverable setup failure of a direct solver
+                for (int b : R)
+                    if (S[b].call_lsetup) L.push_back(b);
+                if (!L.empty()) {
+                    tn.clear(); cj.clear(); hh.clear();
+                    for (int b : L) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); hh.push_back(S[b].hh); }
+                    info.assign(L.size(), 0);
+                    ENS_CALL(e, idahip_krylov_psetup(e->ctx, tn.data(), cj.data(), hh.data(), info.data(), L.data(), (int)L.size()));
+                    const long evals = std::min<long>((long)pml + pmu + 1, (long)e->n);
+                    for (size_t q = 0; q < L.size(); ++q) {
+                        Sys& s = S[L[q]];
+                        s.nls_ret = info[q] ? NLS_LSETUP_RECVR : NLS_SUCCESS;
+                        s.npe += 1;
+                        s.nre_dq += evals;
+                    }
+                    L.clear();
+                }
+            }
             if (dq)
                 for (int b : R)
                     if (S[b].call_lsetup) L.push_back(b);
@@ -330,6 +354,7 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
             for (int b : I) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); epsv.push_back(S[b].eps_newt); }
             nrm.assign(I.size(), 0.0);
             std::vector<int32_t> nli(I.size(), 0), lflag(I.size(), 0);
+            const bool prec_on = idahip_krylov_band_prec(e->ctx, nullptr, nullptr) == 1;
             ENS_CALL(e, idahip_newton_iter_krylov(e->ctx, tn.data(), cj.data(), epsv.data(), nrm.data(), nli.data(), lflag.data(), I.data(), (int)I.size()));
             for (size_t q = 0; q < I.size(); ++q) {
                 const int b = I[q];
@@ -337,6 +362,7 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
                 s.niters += 1;
                 (void)after_lsolve(s, lst, nli[q], lflag[q] != 0);
                 s.nre_dq += nli[q];
+                if (prec_on) s.nps += 1 + nli[q];
                 if (lflag[q] != 0) {
                     after_ctest(b, NLS_CONV_RECVR, false);
                     continue;
@@ -1421,6 +1447,8 @@ int idaens_get_counter(const idaens* e, int which, int64_t* out) {
             case IDAENS_C_NCFL: v = s.ncfl; break;
             case IDAENS_C_NRE_DQ: v = s.nre_dq; break;
             case IDAENS_C_NBACKTR: v = s.nbacktr; break;
+            case IDAENS_C_NPE: v = s.npe; break;
+            case IDAENS_C_NPS: v = s.nps; break;
             default: return -2;
         }
         out[b] = v;

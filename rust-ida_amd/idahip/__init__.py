@@ -47,6 +47,8 @@ HIP_SYMBOLS = [
     "idahip_set_constraints", "idahip_constraints", "idahip_post_newton_constr", "idahip_constr_check",
     "idahip_create_krylov", "idahip_krylov", "idahip_set_krylov_fused", "idahip_krylov_fused", "idahip_krylov_solve",
     "idahip_newton_iter_krylov",
+    "idahip_set_krylov_band_prec", "idahip_krylov_band_prec", "idahip_krylov_psetup", "idahip_krylov_psolve", "idahip_krylov_download_prec",
+    "idahip_krylov_upload_prec",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
@@ -168,6 +170,12 @@ def load():
     H.idahip_krylov_fused.argtypes = [vp]
     H.idahip_krylov_solve.argtypes = [vp, dp, dp, dp, dp, dp, i32p, i32p, dp, i32p, ci]
     H.idahip_newton_iter_krylov.argtypes = [vp, dp, dp, dp, dp, i32p, i32p, i32p, ci]
+    H.idahip_set_krylov_band_prec.argtypes = [vp, ci, ci]
+    H.idahip_krylov_band_prec.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+    H.idahip_krylov_psetup.argtypes = [vp, dp, dp, dp, i32p, i32p, ci]
+    H.idahip_krylov_psolve.argtypes = [vp, dp, dp, i32p, ci]
+    H.idahip_krylov_download_prec.argtypes = [vp, ci, dp, i64p]
+    H.idahip_krylov_upload_prec.argtypes = [vp, ci, dp, i64p]
     H.idahip_timing_enable.argtypes = [vp, ci]
     H.idahip_timing_get.argtypes = [vp, ci, dp, i64p, i64p]
     H.idahip_timing_reset.argtypes = [vp]
@@ -286,6 +294,51 @@ class Ctx:
         self._chk(self.H.idahip_newton_iter_krylov(self.h, _p(tn), _p(cj), _p(eps_newt), _p(out), _p(nli, i32p), _p(flag, i32p),
                                                    _p(idx, i32p), idx.size), "newton_iter_krylov")
         return out, nli, flag
+
+    def set_krylov_band_prec(self, ml, mu):
+        """Krylov ctx: the band preconditioner of DESIGN.md section 4i with half-bandwidths (ml, mu); (-1, -1) turns it off."""
+        self._chk(self.H.idahip_set_krylov_band_prec(self.h, int(ml), int(mu)), "set_krylov_band_prec")
+
+    def krylov_band_prec(self):
+        """idahip_krylov_band_prec -> (ml, mu) with the mode on, None otherwise."""
+        ml, mu = C.c_int(-1), C.c_int(-1)
+        return (ml.value, mu.value) if self.H.idahip_krylov_band_prec(self.h, C.byref(ml), C.byref(mu)) == 1 else None
+
+    def krylov_psetup(self, tn, cj, hh, idx=None):
+        """P = the band DQ Jacobian at the ctx-resident yy, yp, ewt, savres, factored, for the listed systems -> info [nsys]."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        tn, cj, hh = (_f64(np.broadcast_to(v, idx.shape)) for v in (tn, cj, hh))
+        info = np.zeros(idx.size, dtype=np.int32)
+        self._chk(self.H.idahip_krylov_psetup(self.h, _p(tn), _p(cj), _p(hh), _p(info, i32p), _p(idx, i32p), idx.size), "krylov_psetup")
+        return info
+
+    def krylov_psolve(self, r, idx=None):
+        """z = P^-1 r for the listed systems; r [nsys][n] by list position -> z [nsys][n]."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        r = _f64(r).reshape(idx.size, self.n)
+        z = np.zeros((idx.size, self.n))
+        self._chk(self.H.idahip_krylov_psolve(self.h, _p(r), _p(z), _p(idx, i32p), idx.size), "krylov_psolve")
+        return z
+
+    def krylov_download_prec(self, sys):
+        """The preconditioner's factors of one system -> (ab [n][ldab], piv [n]), as download_lu_band gives a band ctx's."""
+        w = self.krylov_band_prec()
+        ld = band_ldab(*w) if w else 0
+        ab = np.zeros((self.n, ld))
+        piv = np.zeros(self.n, dtype=np.int64)
+        self._chk(self.H.idahip_krylov_download_prec(self.h, int(sys), _p(ab), _p(piv, i64p)), "krylov_download_prec")
+        return ab, piv
+
+    def krylov_upload_prec(self, sys, ab, piv):
+        """A user-supplied preconditioner for one system: factored band storage [n][ldab] and pivots [n] (0-based rows)."""
+        w = self.krylov_band_prec()
+        ab = _f64(ab)
+        if w is not None and ab.size != self.n * band_ldab(*w):
+            raise IdaHipError("krylov_upload_prec: %d entries for n = %d, ldab = %d" % (ab.size, self.n, band_ldab(*w)))
+        piv = np.ascontiguousarray(np.asarray(piv, dtype=np.int64))
+        if piv.size != self.n:
+            raise IdaHipError("krylov_upload_prec: %d pivots for n = %d" % (piv.size, self.n))
+        self._chk(self.H.idahip_krylov_upload_prec(self.h, int(sys), _p(ab), _p(piv, i64p)), "krylov_upload_prec")
 
     def ls_type(self):
         return int(self.H.idahip_ls_type(self.h))
@@ -762,7 +815,7 @@ def band_expand_factors(ab, piv, n, ml, mu):
 
 COUNTERS = {"nst": 0, "nre": 1, "nje": 2, "nsetups": 3, "nni": 4, "netf": 5, "ncfn": 6, "n_attempts": 7, "nls_nconvfails": 8,
             "kused": 9, "kk": 10, "nge": 11, "nlufail": 12, "nconv_jcur": 13, "nfail_first": 14, "nli": 15, "ncfl": 16,
-            "nre_dq": 17, "nbacktr": 18}
+            "nre_dq": 17, "nbacktr": 18, "npe": 19, "nps": 20}
 YA_YDP_INIT, Y_INIT = 1, 2  # Ensemble.calc_ic's icopt (C IDA's IDA_YA_YDP_INIT, IDA_Y_INIT)
 REALS = {"tn": 0, "hused": 1, "hh": 2, "h0u": 3, "tolsf": 4}
 

@@ -1,14 +1,16 @@
-"""Three linear solvers on the same integrations, on one box in one call: a dense ctx, a band ctx (heat only) and a Krylov ctx
-(matrix-free SPGMR). Cases: heat n = 4096, B = 256; linear dense n = 512, B = 4096. Recorded per solver: wall
-time of idaens_solve_schedule to the common horizon (a host clock around a call that ends in a device synchronise), Newton
-iterations per second, the sums of nst / nni / nli / ncfl / ncfn over the ensemble, the statuses, and the device memory the ctx took.
+"""The linear solvers on the same integrations, on one box in one call: a dense ctx, a band ctx (heat only), a Krylov ctx
+(matrix-free SPGMR) and, for heat, a Krylov ctx with the (1, 1) band preconditioner (section 4i). Cases: heat
+n = 4096, B = 256; linear dense n = 512, B = 4096. Recorded per solver: wall time of idaens_solve_schedule to the common horizon (a
+host clock around a call that ends in a device synchronise), Newton iterations per second, the sums of nst / nni / nli / ncfl / ncfn /
+npe / nps over the ensemble, the statuses, and the device memory the ctx took (the preconditioner's storage included).
 
 The solvers differ by factors, in memory or in whether they reach the horizon at all, and no speed claim rests on the times: the
 runs are not alternated and a timed window is one schedule call (0.1 to 0.7 s), repeated once after a warm-up pass.
 Every (case, solver) run is a child process of its own under `timeout -k 10`, and the chain stops at the first one that fails.
 One JSON object per line on stdout; --json also writes them to a file.
 
-    python tools/krylov_ab.py [--json profiles/krylov_ab.json] [--outputs 1] [--limit 300] [--small]
+    python tools/krylov_ab.py [--json profiles/krylov_ab.json] [--cases heat linear] [--outputs 1] [--limit 300] [--small]
+    python tools/krylov_ab.py --cases heat --json profiles/krylov_prec_ab.json     (the figures of section 4i)
 """
 import argparse
 import json
@@ -21,8 +23,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "rust-ida_amd"))
 
-CASES = {"heat": ("heat1d", 4096, 256, ("dense", "band", "krylov")), "linear": ("linear_dense", 512, 4096, ("dense", "krylov"))}
-SMALL = {"heat": ("heat1d", 256, 16, ("dense", "band", "krylov")), "linear": ("linear_dense", 64, 32, ("dense", "krylov"))}
+CASES = {"heat": ("heat1d", 4096, 256, ("dense", "band", "krylov", "krylov_prec")), "linear": ("linear_dense", 512, 4096, ("dense", "krylov"))}
+SMALL = {"heat": ("heat1d", 256, 16, ("dense", "band", "krylov", "krylov_prec")), "linear": ("linear_dense", 64, 32, ("dense", "krylov"))}
 
 
 def one(case, solver, outputs, small):
@@ -35,7 +37,9 @@ def one(case, solver, outputs, small):
     touts = p["touts"][:outputs]
     torch.cuda.init()
     free0 = torch.cuda.mem_get_info()[0]
-    ctx = problems.make_ctx(p, band=(solver == "band"), krylov=(0 if solver == "krylov" else None))
+    ctx = problems.make_ctx(p, band=(solver == "band"), krylov=(0 if solver.startswith("krylov") else None))
+    if solver == "krylov_prec":
+        ctx.set_krylov_band_prec(1, 1)
     mem = free0 - torch.cuda.mem_get_info()[0]
     recs = []
     for rep in range(2):  # the first pass warms the code objects up; the second is the figure
@@ -50,8 +54,8 @@ def one(case, solver, outputs, small):
                      "seconds": round(sec, 4), "newton_iters_per_s": round(float(c["nni"].sum()) / sec, 1),
                      "device_controller": ens.device_controller_active(), "ctx_device_bytes": int(mem),
                      "finished": int((status == 0).sum()), "conv_fail": int((status == -4).sum()), "other_status": int(((status != 0) & (status != -4)).sum()),
-                     **{k: int(c[k].sum()) for k in ("nst", "nni", "nli", "ncfl", "ncfn", "netf", "nsetups", "nje", "nre", "nre_dq")},
-                     "host": socket.gethostname(), "command": "python tools/krylov_ab.py --outputs %d%s" % (outputs, " --small" if small else "")})
+                     **{k: int(c[k].sum()) for k in ("nst", "nni", "nli", "ncfl", "ncfn", "netf", "nsetups", "nje", "nre", "nre_dq", "npe", "nps")},
+                     "host": socket.gethostname(), "command": "python tools/krylov_ab.py --cases %s --outputs %d%s" % (case, outputs, " --small" if small else "")})
         ens.close()
     ctx.close()
     for r in recs:
@@ -61,6 +65,7 @@ def one(case, solver, outputs, small):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
+    ap.add_argument("--cases", nargs="+", default=["heat", "linear"], choices=["heat", "linear"])
     ap.add_argument("--outputs", type=int, default=1, help="outputs of the case's schedule to integrate to (1: heat 0.01, linear dense 0.1)")
     ap.add_argument("--limit", type=int, default=300, help="seconds granted to each (case, solver) child")
     ap.add_argument("--small", action="store_true", help="toy sizes: a rehearsal of the script, not a measurement")
@@ -70,6 +75,8 @@ def main():
         return one(a.one[0], a.one[1], a.outputs, a.small)
     lines = []
     for case, (_, _, _, solvers) in (SMALL if a.small else CASES).items():
+        if case not in a.cases:
+            continue
         for solver in solvers:
             cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--one", case, solver, "--outputs", str(a.outputs)]
             if a.small:
