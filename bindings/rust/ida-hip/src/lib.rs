@@ -400,6 +400,14 @@ impl Ctx {
         let rc = unsafe { sys::idahip_set_constraints(self.raw, c.map_or(ptr::null(), |v| v.as_ptr())) };
         self.check(rc).map(|_| ())
     }
+
+    /// C IDA's `IDASetSuppressAlg` (the reference's `ida_suppressalg`, src/lib.rs:138): the stepper's local error norms leave out the
+    /// algebraic components (`set_id`: id_i = 0). Read by every solve call at its start; a solve call with it on and no id is
+    /// refused, and so is `HipEnsemble::calc_ic` with it on (order: `set_id`, `calc_ic`, `set_suppress_alg(true)`, `solve`).
+    pub fn set_suppress_alg(&mut self, on: bool) -> Result<(), Error> {
+        let rc = unsafe { sys::idahip_set_suppress_alg(self.raw, on as i32) };
+        self.check(rc).map(|_| ())
+    }
 }
 
 impl Drop for Ctx {
@@ -758,6 +766,28 @@ impl HipEnsemble {
             return Err(Error::Library { code: rc, message: self.last_error() });
         }
         Ok((status, tret))
+    }
+
+    /// C IDA's `IDASetStopTime`, per system: `Some(&[t])` for every system, `Some(&[t_0, .., t_{batch-1}])` with NaN = "none for this
+    /// system", `None` clears all. A solve call that would pass a system's stop time returns `IDAENS_TSTOP_RETURN` for it with
+    /// tret == tstop exactly, and the return consumes the stop time. Refused: an infinite value, a system inside a round-limited
+    /// call, a stop time behind the current t of a system that has stepped.
+    pub fn set_stop_time(&mut self, tstop: Option<&[f64]>) -> Result<(), Error> {
+        if let Some(v) = tstop {
+            assert!(v.len() == 1 || v.len() == self.ctx.batch);
+        }
+        let rc = unsafe { sys::idaens_set_stop_time(self.raw, tstop.map_or(ptr::null(), |v| v.as_ptr()), tstop.map_or(0, |v| v.len() as c_int)) };
+        if rc != 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(())
+    }
+
+    /// The stop time of every system, NaN where there is none.
+    pub fn stop_time(&self) -> Vec<f64> {
+        let mut out = vec![0.0f64; self.ctx.batch];
+        unsafe { sys::idaens_get_stop_time(self.raw, out.as_mut_ptr()) };
+        out
     }
 
     /// Consistent initial conditions for every system before the first `solve` (C IDA's `IDACalcIC`; `tout1`: the first output

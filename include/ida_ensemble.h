@@ -46,7 +46,9 @@ enum {
     IDAENS_ILL_INPUT = -22,
     IDAENS_BAD_EWT = -24, /* idaens_calc_ic: a component of the error weights is <= 0 (IDA_BAD_EWT) */
     IDAENS_BAD_K = -25,
-    IDAENS_BAD_T = -26
+    IDAENS_BAD_T = -26,
+    IDAENS_BAD_TSTOP = -27 /* IdaError::BadStopTime: the stop time is behind the current t in the direction of integration
+                              (impl_stop_test.rs:44-52; C IDA's IDA_ILL_INPUT "tstop is behind current t") */
 };
 
 /* Ida::new(problem, yy0, yp0, tol_control) for every system of ctx (src/lib.rs:278-405); ctx must already hold the
@@ -126,6 +128,37 @@ int idaens_set_root_fn(idaens* e, int nroots, idaens_root_fn fn, void* user);
  * ask for one get, after their residual, one idahip_krylov_psetup call with their tn, cj and hh. Per such system: the bookkeeping
  * above (nje stays), IDAENS_C_NPE += 1, IDAENS_C_NRE_DQ += min(ml+mu+1, n), and a zero pivot in P is a recoverable setup failure
  * exactly as on a dense ctx (IDAENS_C_NLUFAIL counts it there). Every Newton iteration adds 1 + nli to IDAENS_C_NPS. */
+
+/* Stop time: C IDA's IDASetStopTime. The reference's Ida::solve has every stop test (ida_tstop: Option<f64>, src/impl_solve.rs:137-150,
+ * src/impl_stop_test.rs:36-211, src/lib.rs:640-644) and no setter; this is the setter. Every system is its own `Ida` object, so every
+ * system has its own stop time. hTstop: ntstop = 1 (one value for all systems) or batch values; a NaN entry means "no stop time for
+ * this system" and clears one that is set; hTstop == NULL clears all. May be called before the first solve and between solve calls.
+ * With a stop time tstop set for a system:
+ *   - first call: if (tstop - t0) * h0 <= 0 the system does not start: IDAENS_ILL_INPUT with tret = t0, exactly as for a tout too
+ *     close to t0 -- nothing of its state has changed, the caller sets another stop time (or none) and calls again; if the first
+ *     step would pass tstop, h0 = (tstop - t0)(1 - 4 eps);
+ *   - no step passes tstop: before every step that would, hh = (tstop - tn)(1 - 4 eps);
+ *   - a solve call whose tout lies beyond tstop returns IDAENS_TSTOP_RETURN with tret = tstop exactly and yy, yp = y(tstop), y'(tstop)
+ *     once tn is within 100 eps (|tn| + |hh|) of tstop; a tout at or before tstop is reached first (IDAENS_SUCCESS). Both tasks;
+ *   - the return consumes the stop time (ida_tstop = None): idaens_get_stop_time reports NaN from then on and the caller sets the
+ *     next one. (For IDAENS_ONE_STEP the reference's text forgets this at the entry of a call, src/impl_stop_test.rs:109-113, and
+ *     would report TSTOP for ever; this library clears it as C IDA does -- SURVEY.md quirk Q15.)
+ *   - a solve call that finds tstop behind tn returns IDAENS_BAD_TSTOP, which is sticky like every negative status;
+ *   - in idaens_solve_schedule / _group an IDAENS_TSTOP_RETURN ends that system's schedule exactly as a root return does;
+ *   - root finding, constraints, every ctx kind (dense, band, Krylov, DQ Jacobians, host callbacks) and all three steppers work;
+ *     idaens_device_controller_active reports what it reports without one.
+ * Refused (negative return with a text, nothing changed): ntstop other than 1 or batch; an infinite value; any system still inside
+ * a round-limited call (it last returned IDAENS_UNFINISHED); for a system that has taken a step (nst > 0), (tstop - tn) * hh < 0 --
+ * C IDA's check in IDASetStopTime; the text names the first such system. idaens_stream and idaens_stream_group are refused (negative
+ * return with a text, nothing launched) while any system has a stop time: a restarted system is Ida::new, which has none. */
+int idaens_set_stop_time(idaens* e, const double* hTstop, int ntstop);
+int idaens_get_stop_time(const idaens* e, double* hTstop /* [batch], NaN where none */);
+
+/* Masked error norms: C IDA's IDASetSuppressAlg, the reference's ida_suppressalg (src/lib.rs:138). The switch belongs to the ctx
+ * (idahip_set_suppress_alg, ida_hip.h), as the id vector and the constraints do, and is read at the start of every solve call. With
+ * it on, every local error norm of the stepper leaves out the algebraic components (id_i = 0). Refused (negative return with a
+ * text, nothing launched): any solve call with the switch on and no id vector (C IDA's IDA_MISSING_ID), and idaens_calc_ic with the
+ * switch on -- the supported order is idahip_set_id, idaens_calc_ic, idahip_set_suppress_alg(ctx, 1), idaens_solve. */
 
 /* Consistent initial conditions for every system: C IDA's IDACalcIC (the reference has none, src/lib.rs:328-335), as DESIGN.md
  * section 4f defines it -- no constraints, sysindex = 1, line search always on.

@@ -213,10 +213,25 @@ int idahip_kind(const idahip_ctx* ctx); /* the idahip_problem the ctx was create
 /* TolControlSS (natol == 1) / TolControlSV (natol == n), src/tol_control.rs:6-82; shared by the ensemble */
 int idahip_set_tolerances(idahip_ctx* ctx, double rtol, const double* hAtol, int natol);
 /* C IDA's IDASetId: hId[i] = 1.0 marks component i as differential, 0.0 as algebraic (any other value: -2); shared by the
- * ensemble, as the tolerances are; NULL clears it. Read by idahip_ic_trial / idaens_calc_ic with IDAHIP_IC_YA_YDP only. */
+ * ensemble, as the tolerances are; NULL clears it. Read by idahip_ic_trial / idaens_calc_ic with IDAHIP_IC_YA_YDP, and by the masked
+ * error norms (idahip_set_suppress_alg, idahip_wrms_masked). */
 int idahip_set_id(idahip_ctx* ctx, const double* hId /* [n] or NULL */);
 /* 1 if an id is set (hId, when non-null, receives it), 0 if not, -1 for a null ctx */
 int idahip_id(const idahip_ctx* ctx, double* hId);
+/* C IDA's IDASetSuppressAlg, the reference's ida_suppressalg (src/lib.rs:138, no setter there): on != 0 masks the LOCAL ERROR norms
+ * of the stepper with the id vector -- per element p = (x_i w_i) m_i with m_i = 1.0 where id_i != 0 and 0.0 elsewhere, the p p added
+ * left to right from 0.0 by one lane, divided by the FULL n, then the square root (src/norm_rms.rs:49-57; a non-finite masked element
+ * still makes the norm NaN). Default off. The switch belongs to the ctx, as id and the constraints do, is shared by the ensemble and
+ * is read at the start of every call, so it may change between solve calls. Masked when on -- every norm the reference passes
+ * ida_suppressalg to: ypnorm and ||phi[0]|| of idahip_init_first, the four sums of idahip_post_newton / _post_newton_constr,
+ * ||phi[0]|| of idahip_complete_step, and the same sums inside idahip_tiny_solve / idahip_round_solve. Never masked: Newton's delnrm
+ * (idahip_newton_iter, _iter2, _iter_krylov), the constraint correction's norm, SPGMR's norms, DQ increments, idahip_wrms and
+ * everything of the idahip_ic_* calls. With the switch off every kernel does exactly what it did without it.
+ * Refused (-2 with a text, nothing launched): the calls above with the switch on and no id set (C IDA's IDA_MISSING_ID), and
+ * idaens_calc_ic with the switch on: the supported order is idahip_set_id, idaens_calc_ic, idahip_set_suppress_alg(ctx, 1), solve. */
+int idahip_set_suppress_alg(idahip_ctx* ctx, int on);
+/* 1 on, 0 off, -1 for a null ctx */
+int idahip_suppress_alg(const idahip_ctx* ctx);
 /* C IDA's IDASetConstraints (the reference has none; DESIGN.md section 4g is the definition): hC[i] = 0.0 no constraint on component
  * i, 1.0: y_i >= 0, -1.0: y_i <= 0, 2.0: y_i > 0, -2.0: y_i < 0; any other value: -2. Shared by the ensemble, as the tolerances are;
  * NULL clears it; an all-zero vector counts as set (the check runs and always passes). Read by idahip_post_newton_constr,
@@ -262,6 +277,9 @@ int idahip_ls_num_iters(const idahip_ctx* ctx);
 double idahip_ls_res_norm(const idahip_ctx* ctx);
 /* NormRms::norm_wrms (src/norm_rms.rs:31-38): hOut[s] = sqrt(sum_i (x_i w_i)^2 / n), summed left to right */
 int idahip_wrms(idahip_ctx* ctx, const double* dX, const double* dW, double* hOut, const int32_t* hIdx, int nsys);
+/* the masked variant (src/norm_rms.rs:49-57) with the ctx's id as the mask: hOut[s] = sqrt(sum_i ((x_i w_i) m_i)^2 / n), m_i = 1.0 where
+ * id_i != 0, 0.0 elsewhere. It does not look at idahip_set_suppress_alg; without an id it is refused (-2). */
+int idahip_wrms_masked(idahip_ctx* ctx, const double* dX, const double* dW, double* hOut, const int32_t* hIdx, int nsys);
 
 /* IdaNLProblem::sys immediately followed by IdaNLProblem::setup for the same systems -- the order Newton::solve runs them
  * in when call_lsetup is set (crates/nonlinear/src/newton.rs:73-96; src/ida_nls.rs:118-188). Same results as

@@ -53,6 +53,7 @@ struct idahip_ctx {
     // idahip_set_id: 1.0 differential / 0.0 algebraic component, shared by the ensemble (idaens_calc_ic)
     double* d_id = nullptr;      // [n] or null
     std::vector<double> h_id;    // host copy (empty: no id set)
+    bool suppress_alg = false;   // idahip_set_suppress_alg: the local error norms leave out the components with id == 0
     // idahip_set_constraints: 0 / +-1 / +-2 per component, shared by the ensemble
     double* d_constr = nullptr;      // [n] or null
     std::vector<double> h_constr;    // host copy (empty: no constraints set)

@@ -42,7 +42,10 @@ struct FlowArgs {
 // the no-roots kernels registers and scratch otherwise -- config 2: 57 -> 46 M iters/s with it compiled in).
 // CONSTR = true compiles the inequality-constraint check in: V then also provides
 // post_newton_constr(s, checked, norms[4], &rr) -> 0 passed | 1 corrected | 2 recover, and constr_phi0_violated().
-template <class V, bool ROOTS = false, bool CONSTR = false>
+// TSTOP = false compiles the stop time (idaens_set_stop_time) out: for a call in which no system has one. The lock-step rounds'
+// kernels are instantiated both ways (host/ida_solve_flow.hpp says what it costs them otherwise); the one-thread stepper, whose
+// occupancy does not change with it, always has it in.
+template <class V, bool ROOTS = false, bool CONSTR = false, bool TSTOP = true>
 struct IdaFlow {
     const FlowArgs& a;
     idactl::SysCore& s;
@@ -89,10 +92,10 @@ struct IdaFlow {
     __device__ __attribute__((always_inline)) int enter_call() const {
         const Backend be{*this};
         if constexpr (ROOTS) {
-            return idactl::enter_call(s, *rt, a.nrt, IDAENS_NORMAL, be);
+            return idactl::enter_call<TSTOP>(s, *rt, a.nrt, IDAENS_NORMAL, be);
         } else {
             idactl::NoRoots none;
-            return idactl::enter_call(s, none, 0, IDAENS_NORMAL, be);
+            return idactl::enter_call<TSTOP>(s, none, 0, IDAENS_NORMAL, be);
         }
     }
     // the call has returned (s.status set, phase idle): with IDAENS_SUCCESS and touts left it enters the next call at once;
@@ -122,7 +125,7 @@ struct IdaFlow {
         if (s.ph == idactl::PH_IDLE && s.nst == 0 && !s.setup_done && !s.dead) {
             double ypnorm, p0nrm;
             v.init_first(&ypnorm, &p0nrm);
-            if (idactl::first_call_scalars(s, tout, ypnorm, p0nrm, a.epcon, a.hmax_inv, start_violates())) {
+            if (idactl::first_call_scalars<TSTOP>(s, tout, ypnorm, p0nrm, a.epcon, a.hmax_inv, start_violates())) {
                 if constexpr (ROOTS) {
                     if (a.nrt > 0) {  // impl_solve.rs:157-159
                         const Backend be{*this};
@@ -151,7 +154,7 @@ struct IdaFlow {
     }
     // a step attempt up to the Newton solve: step() prologue, set_coeffs, tn += hh, lsetup decision, prediction
     __device__ void attempt_begin() const {
-        idactl::begin_attempt(s);
+        idactl::begin_attempt<TSTOP>(s);
         v.predict(s);
     }
     // the rest of the attempt once the Newton solve has set s.nls_ret; true = the system steps on
@@ -185,7 +188,7 @@ struct IdaFlow {
         if constexpr (ROOTS) {
             if (idactl::root_return_after_step(s, *rt, a.nrt, be)) return false;
         }
-        const int istate = idactl::stop_test2(s, s.tout_cur, IDAENS_NORMAL, be);
+        const int istate = idactl::stop_test2<TSTOP>(s, s.tout_cur, IDAENS_NORMAL, be);
         if (istate != IDAENS_UNFINISHED) {
             s.status = istate;
             s.ph = idactl::PH_IDLE;

@@ -67,7 +67,14 @@ VecState vec_state(idahip_ctx* c) {
     s.ewt = c->ewt; s.ee = c->ee; s.delta = c->delta;
     s.n = c->n;
     s.rtol = c->rtol; s.atol_s = c->atol_s; s.atol_v = c->d_atol_v;
+    s.mask = (c->suppress_alg && !c->h_id.empty()) ? c->d_id : nullptr;
     return s;
+}
+
+// C IDA's IDA_MISSING_ID: the masked norms (idahip_set_suppress_alg) need the id vector; nothing is launched without it
+int missing_id(idahip_ctx* c, const char* who) {
+    if (c->suppress_alg && c->h_id.empty()) return fail(c, -2, "%s: suppress_alg is on and no id vector is set (idahip_set_id)", who);
+    return 0;
 }
 
 int post_launch(idahip_ctx* c, const char* what) {
@@ -445,6 +452,14 @@ int idahip_id(const idahip_ctx* c, double* hId) {
     return 1;
 }
 
+int idahip_set_suppress_alg(idahip_ctx* c, int on) {
+    if (!c) return -1;
+    c->suppress_alg = on != 0;
+    return 0;
+}
+
+int idahip_suppress_alg(const idahip_ctx* c) { return c ? (c->suppress_alg ? 1 : 0) : -1; }
+
 int idahip_set_constraints(idahip_ctx* c, const double* hC) {
     if (c && c->krylov) return fail(c, -2, "idahip_set_constraints on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
@@ -756,6 +771,31 @@ int idahip_wrms(idahip_ctx* c, const double* dX, const double* dW, double* hOut,
     if ((rc = ap.fetch())) return rc;
     const double* h = ap.host_of(d_out);
     for (int s = 0; s < nsys; ++s) hOut[s] = sqrt(h[s] / (double)n);  // divide, then sqrt: host libm (norm_rms.rs:36-37)
+    return 0;
+}
+
+int idahip_wrms_masked(idahip_ctx* c, const double* dX, const double* dW, double* hOut, const int32_t* hIdx, int nsys) {
+    DevGuard dev_guard__(c);
+    int rc = check_list(c, hIdx, nsys);
+    if (rc) return rc;
+    if (!dX || !dW || !hOut) return fail(c, -2, "null argument");
+    if (c->h_id.empty()) return fail(c, -2, "idahip_wrms_masked: no id vector is set (idahip_set_id)");
+    if (nsys == 0) return 0;
+    const int n = c->n;
+    ArgPack ap;
+    if ((rc = ap.begin(c))) return rc;
+    const int* d_idx = ap.in(hIdx, nsys);
+    double* d_out = ap.out<double>(nsys);
+    if ((rc = ap.ok())) return rc;
+    if ((rc = ap.upload())) return rc;
+    {
+        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+        hipLaunchKernelGGL(wrms_masked_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, dX, dW, (const double*)c->d_id, d_out, n, d_idx);
+        if ((rc = post_launch(c, "wrms_masked"))) return rc;
+    }
+    if ((rc = ap.fetch())) return rc;
+    const double* h = ap.host_of(d_out);
+    for (int s = 0; s < nsys; ++s) hOut[s] = sqrt(h[s] / (double)n);  // by the full n (norm_rms.rs:56)
     return 0;
 }
 
@@ -1652,6 +1692,7 @@ int idahip_init_first(idahip_ctx* c, double* hYpnorm, double* hPhi0Nrm, const in
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
     if (!hYpnorm || !hPhi0Nrm) return fail(c, -2, "null argument");
+    if ((rc = missing_id(c, "idahip_init_first"))) return rc;
     if (nsys == 0) return 0;
     ArgPack ap;
     if ((rc = ap.begin(c))) return rc;
@@ -1720,6 +1761,7 @@ int idahip_post_newton(idahip_ctx* c, const double* hCj, const int32_t* hKk, dou
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
     if (!hCj || !hKk || !hNorms) return fail(c, -2, "null argument");
+    if ((rc = missing_id(c, "idahip_post_newton"))) return rc;
     if (nsys == 0) return 0;
     for (int s = 0; s < nsys; ++s)
         if (hKk[s] < 1 || hKk[s] >= MXORDP1) return fail(c, -2, "bad kk at list position %d", s);
@@ -1748,6 +1790,7 @@ int idahip_post_newton_constr(idahip_ctx* c, const double* hCj, const int32_t* h
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
     if (!hCj || !hKk || !hEpsNewt || !hCheck || !hNorms || !hFlag || !hRr) return fail(c, -2, "null argument");
+    if ((rc = missing_id(c, "idahip_post_newton_constr"))) return rc;
     if (c->h_constr.empty()) return fail(c, -2, "idahip_post_newton_constr on a ctx without constraints (idahip_set_constraints)");
     if (nsys == 0) return 0;
     for (int s = 0; s < nsys; ++s)
@@ -1836,6 +1879,7 @@ int idahip_complete_step(idahip_ctx* c, const int32_t* hKused, const double* hCk
     int rc = check_list(c, hIdx, nsys);
     if (rc) return rc;
     if (!hKused || !hCk || !hPhi0Nrm || !hEwtBad) return fail(c, -2, "null argument");
+    if ((rc = missing_id(c, "idahip_complete_step"))) return rc;
     if (maxord < 1 || maxord > 5) return fail(c, -2, "bad maxord");
     if (nsys == 0) return 0;
     for (int s = 0; s < nsys; ++s)
@@ -2318,6 +2362,7 @@ int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_
     if (c->n != 3 || (c->kind != IDAHIP_ROBERTS && c->kind != IDAHIP_LORENZ63))
         return fail(c, -2, "the device-resident stepper takes the Roberts and Lorenz63 problems (n = 3)");
     if (c->jac_dq && !c->h_constr.empty()) return fail(c, -2, "difference-quotient Jacobians and constraints do not combine (DESIGN.md section 4g)");
+    if (const int rcm = missing_id(c, "idahip_tiny_solve")) return rcm;
     if (call->recycle && (!c->ic_y || !c->ic_yp)) return fail(c, -2, "recycle needs idahip_snapshot_initial");
     if (call->recycle && call->max_rounds < 1) return fail(c, -2, "recycle needs a round limit");
     const int batch = c->batch, n = c->n;
@@ -2437,6 +2482,7 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     if (c->n <= TINY_N || !(lin || heat) || c->lu_variant < 4)
         return fail(c, -2, "the device-resident lock-step stepper takes linear dense and heat problems with %d < n <= %d (LU variant 4)", TINY_N, LU_BIG_MAX_N);
     if (!c->h_constr.empty()) return fail(c, -2, "the device lock-step stepper does not check constraints: the host stepper does (DESIGN.md section 4g)");
+    if (const int rcm = missing_id(c, "idahip_round_solve")) return rcm;
     if (call->recycle && (!c->ic_y || !c->ic_yp)) return fail(c, -2, "recycle needs idahip_snapshot_initial");
     if (call->recycle && call->max_rounds < 1) return fail(c, -2, "recycle needs a round limit");
     const int batch = c->batch, n = c->n;
@@ -2447,6 +2493,9 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     if (!c->rnd_d) rc |= dalloc(c, &c->rnd_d, (size_t)4 * batch);
     if (rc) return rc;
     if (!c->rnd_host) IDAHIP_HIP(c, hipHostMalloc((void**)&c->rnd_host, 4 * sizeof(int32_t)));
+    // whether any system of the call has a stop time: the kernels without it are the ones that ran before there was one
+    bool tstop = false;
+    for (int b = 0; b < batch; ++b) tstop = tstop || static_cast<const idactl::SysCore*>(hSys)[b].tstopset;
     const size_t ysz = (size_t)call->ntout * batch * n;
     IDAHIP_HIP(c, hipMemcpyAsync(c->tiny_sys, hSys, (size_t)batch * sizeof(idactl::SysCore), hipMemcpyHostToDevice, c->stream));
     IDAHIP_HIP(c, hipMemcpyAsync(c->tiny_touts, call->touts, sizeof(double) * call->ntout, hipMemcpyHostToDevice, c->stream));
@@ -2488,8 +2537,9 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
         a.first_round = r == 0;
         {
             KTimer kt(c, IDAHIP_K_VECTOR, 0);
-            if (call->nroots > 0) hipLaunchKernelGGL(round_begin_kernel<true>, dim3(batch), dim3(WG_NT), shm_wg, c->stream, a);
-            else hipLaunchKernelGGL(round_begin_kernel<false>, dim3(batch), dim3(WG_NT), shm_wg, c->stream, a);
+            auto kern = call->nroots > 0 ? (tstop ? round_begin_kernel<true, true> : round_begin_kernel<true, false>)
+                                         : (tstop ? round_begin_kernel<false, true> : round_begin_kernel<false, false>);
+            hipLaunchKernelGGL(kern, dim3(batch), dim3(WG_NT), shm_wg, c->stream, a);
             hipLaunchKernelGGL(round_lists_kernel, dim3(1), dim3(1024), 0, c->stream, a);
         }
         // n > 1024 (config 4): a factorisation is ~640 launches, most of them one workgroup per matrix, and a third of a small
@@ -2553,8 +2603,9 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
         IDAHIP_HIP(c, hipMemsetAsync(a.summary, 0, sizeof(int), c->stream));
         {
             KTimer kt(c, IDAHIP_K_VECTOR, 0);
-            if (call->nroots > 0) hipLaunchKernelGGL(round_end_kernel<true>, dim3(batch), dim3(WG_NT), shm_wg, c->stream, a);
-            else hipLaunchKernelGGL(round_end_kernel<false>, dim3(batch), dim3(WG_NT), shm_wg, c->stream, a);
+            auto kern = call->nroots > 0 ? (tstop ? round_end_kernel<true, true> : round_end_kernel<true, false>)
+                                         : (tstop ? round_end_kernel<false, true> : round_end_kernel<false, false>);
+            hipLaunchKernelGGL(kern, dim3(batch), dim3(WG_NT), shm_wg, c->stream, a);
             if ((rc = post_launch(c, "round_end"))) return rc;
         }
         if (!call->recycle) {  // one synchronisation per round: does any system still step?

@@ -75,9 +75,9 @@ struct WgVec {
             const double y = phi(0, i);
             const double e = ewt_of(a.v, y, i);
             a.v.ewt[vb + i] = e;
-            const double p = phi(1, i) * e;
+            const double p = mask_term(a.v.mask, i, phi(1, i) * e);
             sm[i] = p * p;
-            const double q = y * e;
+            const double q = mask_term(a.v.mask, i, y * e);
             sm[n + i] = q * q;
         }
         __syncthreads();
@@ -113,26 +113,26 @@ struct WgVec {
             const double w = a.v.ewt[vb + i];
             a.v.yy[vb + i] = a.v.yypredict[vb + i] + e;
             a.v.yp[vb + i] = a.v.yppredict[vb + i] + s.cj * e;
-            double p = e * w;
+            double p = mask_term(a.v.mask, i, e * w);
             sm[i] = p * p;
             double d = 0.0;
             if (kk > 1) {
                 d = phi(kk, i) + e;
-                p = d * w;
+                p = mask_term(a.v.mask, i, d * w);
                 sm[n + i] = p * p;
             } else {
                 sm[n + i] = 0.0;
             }
             if (kk > 2) {
                 d = d + phi(kk - 1, i);
-                p = d * w;
+                p = mask_term(a.v.mask, i, d * w);
                 sm[2 * n + i] = p * p;
             } else {
                 sm[2 * n + i] = 0.0;
             }
             if (kk + 1 < MXORDP1) {
                 const double tmp = e - phi(kk + 1, i);
-                p = tmp * w;
+                p = mask_term(a.v.mask, i, tmp * w);
                 sm[3 * n + i] = p * p;
             } else {
                 sm[3 * n + i] = 0.0;
@@ -164,7 +164,7 @@ struct WgVec {
             const double w = ewt_of(a.v, tmp, i);
             a.v.ewt[vb + i] = w;
             if (w <= 0.0) res()[1] = 1.0;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
-            const double p = tmp * w;
+            const double p = mask_term(a.v.mask, i, tmp * w);
             sm[i] = p * p;
         }
         __syncthreads();
@@ -218,7 +218,7 @@ struct WgVec {
 // ---- begin of a round: who steps, begin_attempt + prediction, which residual kernel serves the system
 // The workgroup (one wavefront) keeps ONE copy of its system's controller record, in LDS: every lane runs the scalar logic
 // on it in lock-step (same loads, same stores of the same values). A private copy per lane meant 64 reads and a spilled
-// 736-byte struct per system and kernel.
+// 752-byte struct per system and kernel.
 static_assert(sizeof(idactl::SysCore) % 8 == 0 && WG_NT == 64, "word copies of the record; one wave per workgroup");
 __device__ __forceinline__ void wg_copy_words(void* dst, const void* src) {
     for (int i = threadIdx.x; i < (int)(sizeof(idactl::SysCore) / 8); i += WG_NT)
@@ -230,7 +230,7 @@ __device__ __forceinline__ void wg_copy_root(void* dst, const void* src) {
     if (threadIdx.x < (int)(sizeof(idahip_root_state) / 8)) static_cast<unsigned long long*>(dst)[threadIdx.x] = static_cast<const unsigned long long*>(src)[threadIdx.x];
 }
 
-template <bool ROOTS>
+template <bool ROOTS, bool TSTOP>
 __global__ __launch_bounds__(WG_NT) void round_begin_kernel(RoundArgs a) {
     extern __shared__ __align__(16) double sm[];
     const int b = blockIdx.x;
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(WG_NT) void round_begin_kernel(RoundArgs a) {
     __syncthreads();
     idactl::SysCore& s = *reinterpret_cast<idactl::SysCore*>(s_raw);
     WgVec v{a, b, a.v.n, (long)b * a.v.n, sm};
-    const IdaFlow<WgVec, ROOTS> F{a.f, s, v, ROOTS ? &s_rt : nullptr};
+    const IdaFlow<WgVec, ROOTS, false, TSTOP> F{a.f, s, v, ROOTS ? &s_rt : nullptr};
     const long long ground = a.round_base + a.round;
     bool stepping = a.first_round ? F.enter(ground, b) : (a.stepping[b] != 0);
     int kind = 0;  // 1: residual only, 2: residual + Jacobian + LU
@@ -364,7 +364,7 @@ __global__ void round_newton_ctl_kernel(RoundArgs a, int phase) {
     if (m_iter != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&a.stats[IDAHIP_K_NEWTON_ITER], (unsigned long long)__popcll(m_iter));
     bool again = false;
     if (mine) {
-        idactl::SysCore& s = a.sys[b];  // in place: the few fields this step touches, not the 736-byte record both ways
+        idactl::SysCore& s = a.sys[b];  // in place: the few fields this step touches, not the 752-byte record both ways
         const int n = a.v.n;
         if (phase == 0) {
             s.nre += 1;  // sys(y0)
@@ -418,7 +418,7 @@ __global__ void round_newton_ctl_kernel(RoundArgs a, int phase) {
 }
 
 // ---- end of a round: the rest of the attempt, the schedule, Ida::new again when streaming, the round's summary
-template <bool ROOTS>
+template <bool ROOTS, bool TSTOP>
 __global__ __launch_bounds__(WG_NT) void round_end_kernel(RoundArgs a) {
     extern __shared__ __align__(16) double sm[];
     const int b = blockIdx.x;
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(WG_NT) void round_end_kernel(RoundArgs a) {
     __syncthreads();
     idactl::SysCore& s = *reinterpret_cast<idactl::SysCore*>(s_raw);
     WgVec v{a, b, a.v.n, (long)b * a.v.n, sm};
-    const IdaFlow<WgVec, ROOTS> F{a.f, s, v, ROOTS ? &s_rt : nullptr};
+    const IdaFlow<WgVec, ROOTS, false, TSTOP> F{a.f, s, v, ROOTS ? &s_rt : nullptr};
     bool stepping = a.stepping[b] != 0;
     // (both calls inlined by force: a call out of line keeps the pointers in vector registers and spills around it)
     if (stepping && a.in_newton[b] && !s.newton_retry) [[clang::always_inline]] stepping = F.attempt_end();

@@ -38,13 +38,13 @@ struct TinyIdaArgs {
     long long* piv;        // [batch][n]
     const double* params;
     int nparam;
+    int jac_dq;                  // idahip_set_jacobian_dq: difference-quotient Jacobians (dq_kernels.hpp)
     const double *ic_y, *ic_yp;  // initial conditions (idaens_stream's restarts)
     long max_rounds;             // step attempts per system in this launch (0: until done)
     long long round_base;        // rounds executed before this launch
     double *yout, *ypout;        // [ntout][batch][n] or null: y, y' at every tout reached
     long long* rounds_done;      // [batch] rounds this system took part in during this launch
     idahip_root_state* roots;    // [batch] or null (f.nrt == 0)
-    int jac_dq;                  // idahip_set_jacobian_dq: difference-quotient Jacobians (dq_kernels.hpp)
 };
 
 // vector backend of IdaFlow: one thread owns system b (the arithmetic of vector_kernels.hpp, element for element)
@@ -63,9 +63,9 @@ struct TinyVec {
             const double y = phi(0, i);
             const double e = ewt_of(a.v, y, i);
             a.v.ewt[vb + i] = e;
-            const double p = phi(1, i) * e;
+            const double p = mask_term(a.v.mask, i, phi(1, i) * e);
             s1 = s1 + p * p;
-            const double q = y * e;
+            const double q = mask_term(a.v.mask, i, y * e);
             s0 = s0 + q * q;
         }
         *ypnorm = sqrt(s1 / (double)n);
@@ -100,22 +100,22 @@ struct TinyVec {
             const double w = a.v.ewt[vb + i];
             a.v.yy[vb + i] = a.v.yypredict[vb + i] + e;
             a.v.yp[vb + i] = a.v.yppredict[vb + i] + s.cj * e;
-            double p = e * w;
+            double p = mask_term(a.v.mask, i, e * w);
             s0 = s0 + p * p;
             double d = 0.0;
             if (kk > 1) {
                 d = phi(kk, i) + e;
-                p = d * w;
+                p = mask_term(a.v.mask, i, d * w);
                 s1 = s1 + p * p;
             }
             if (kk > 2) {
                 d = d + phi(kk - 1, i);
-                p = d * w;
+                p = mask_term(a.v.mask, i, d * w);
                 s2 = s2 + p * p;
             }
             if (kk + 1 < MXORDP1) {
                 const double tmp = e - phi(kk + 1, i);
-                p = tmp * w;
+                p = mask_term(a.v.mask, i, tmp * w);
                 s3 = s3 + p * p;
             }
         }
@@ -146,7 +146,7 @@ struct TinyVec {
             const double w = ewt_of(a.v, tmp, i);
             a.v.ewt[vb + i] = w;
             if (w <= 0.0) bad = true;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
-            const double p = tmp * w;
+            const double p = mask_term(a.v.mask, i, tmp * w);
             acc = acc + p * p;
         }
         s.phi0nrm = sqrt(acc / (double)n);
@@ -255,22 +255,22 @@ struct TinyVecConstr : TinyVec {
         for (int i = 0; i < n; ++i) {
             const double e = a.v.ee[vb + i];
             const double w = a.v.ewt[vb + i];
-            double p = e * w;
+            double p = mask_term(a.v.mask, i, e * w);
             s0 = s0 + p * p;
             double d = 0.0;
             if (kk > 1) {
                 d = phi(kk, i) + e;
-                p = d * w;
+                p = mask_term(a.v.mask, i, d * w);
                 s1 = s1 + p * p;
             }
             if (kk > 2) {
                 d = d + phi(kk - 1, i);
-                p = d * w;
+                p = mask_term(a.v.mask, i, d * w);
                 s2 = s2 + p * p;
             }
             if (kk + 1 < MXORDP1) {
                 const double tmp = e - phi(kk + 1, i);
-                p = tmp * w;
+                p = mask_term(a.v.mask, i, tmp * w);
                 s3 = s3 + p * p;
             }
         }
@@ -403,7 +403,7 @@ struct TinyNewton {
 // its factors (n^2) and the pivots (n)
 __host__ __device__ constexpr int tiny_lds_doubles(int n) { return 14 * n + n * n + n; }
 
-// Everything a system owns sits in LDS for the length of the launch -- the controller record (736 B) and, when the launch was
+// Everything a system owns sits in LDS for the length of the launch -- the controller record (752 B) and, when the launch was
 // given room for them (lds_vec), its vectors and its Jacobian: one lane walks dependent fp64 chains, and what it waits for is
 // the latency of its own state (scratch and global memory: ~500 cycles a touch; LDS: ~60). The vector code is the same either way: the
 // per-thread copy of the arguments points each field at this thread's block and the offsets vb / lub are zero. Config 2 (Lorenz63, 1024 systems): 26.0 -> 31.0 M iterations/s with the controller

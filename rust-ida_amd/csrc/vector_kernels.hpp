@@ -23,7 +23,14 @@ struct VecState {
     int n;
     double rtol, atol_s;
     const double* atol_v;
+    const double* mask;  // the ctx's id vector [n] when idahip_set_suppress_alg is on, else null: the local error norms leave out id_i == 0
 };
+
+// one summand of a local error norm: p = x_i w_i, times the mask's 1.0 / 0.0 when there is one (norm_rms.rs:49-57 -- the product is
+// formed either way, so a non-finite masked element still makes the norm NaN). Without a mask this is p itself.
+__device__ __forceinline__ double mask_term(const double* mask, int i, double p) {
+    return mask ? p * (mask[i] != 0.0 ? 1.0 : 0.0) : p;
+}
 
 __device__ __forceinline__ double ewt_of(const VecState& s, double y, int i) {
     const double at = s.atol_v ? s.atol_v[i] : s.atol_s;
@@ -39,9 +46,9 @@ __global__ __launch_bounds__(256) void init_first_kernel(VecState s, const int* 
         const double y = s.phi[vb + i];
         const double e = ewt_of(s, y, i);
         s.ewt[vb + i] = e;
-        const double p = s.phi[s.phistride + vb + i] * e;
+        const double p = mask_term(s.mask, i, s.phi[s.phistride + vb + i] * e);
         sm[i] = p * p;
-        const double q = y * e;
+        const double q = mask_term(s.mask, i, y * e);
         sm[s.n + i] = q * q;
     }
     __syncthreads();
@@ -100,26 +107,26 @@ __global__ __launch_bounds__(256) void post_newton_kernel(VecState s, const int*
         const double w = s.ewt[vb + i];
         s.yy[vb + i] = s.yypredict[vb + i] + e;
         s.yp[vb + i] = s.yppredict[vb + i] + cj * e;
-        double p = e * w;
+        double p = mask_term(s.mask, i, e * w);
         sm[i] = p * p;
         double d = 0.0;
         if (kk > 1) {
             d = s.phi[kk * s.phistride + vb + i] + e;  // delta = phi[kk] + ee   (lib.rs:992)
-            p = d * w;
+            p = mask_term(s.mask, i, d * w);
             sm[n + i] = p * p;
         } else {
             sm[n + i] = 0.0;
         }
         if (kk > 2) {
             d = d + s.phi[(kk - 1) * s.phistride + vb + i];  // delta += phi[kk-1]  (lib.rs:1002)
-            p = d * w;
+            p = mask_term(s.mask, i, d * w);
             sm[2 * n + i] = p * p;
         } else {
             sm[2 * n + i] = 0.0;
         }
         if (kk + 1 < MXORDP1) {
             const double tmp = e - s.phi[(kk + 1) * s.phistride + vb + i];  // ee - phi[kk+1]  (impl_complete_step.rs:75)
-            p = tmp * w;
+            p = mask_term(s.mask, i, tmp * w);
             sm[3 * n + i] = p * p;
         } else {
             sm[3 * n + i] = 0.0;
@@ -213,26 +220,26 @@ __global__ __launch_bounds__(256) void post_newton_constr_kernel(VecState s, con
                 s.ee[vb + i] = e;
             }
         }
-        double p = e * w;
+        double p = mask_term(s.mask, i, e * w);
         sm[i] = p * p;
         double d = 0.0;
         if (kk > 1) {
             d = s.phi[kk * s.phistride + vb + i] + e;
-            p = d * w;
+            p = mask_term(s.mask, i, d * w);
             sm[n + i] = p * p;
         } else {
             sm[n + i] = 0.0;
         }
         if (kk > 2) {
             d = d + s.phi[(kk - 1) * s.phistride + vb + i];
-            p = d * w;
+            p = mask_term(s.mask, i, d * w);
             sm[2 * n + i] = p * p;
         } else {
             sm[2 * n + i] = 0.0;
         }
         if (kk + 1 < MXORDP1) {
             const double tmp = e - s.phi[(kk + 1) * s.phistride + vb + i];
-            p = tmp * w;
+            p = mask_term(s.mask, i, tmp * w);
             sm[3 * n + i] = p * p;
         } else {
             sm[3 * n + i] = 0.0;
@@ -244,6 +251,20 @@ __global__ __launch_bounds__(256) void post_newton_constr_kernel(VecState s, con
         flag[blockIdx.x] = fl;
         rr[blockIdx.x] = 0.0;
     }
+}
+
+// the masked weighted norm on its own (idahip_wrms_masked): out[s] = sum_i ((x_i w_i) m_i)^2, m = 1.0 where mask_i != 0, left to right
+__global__ __launch_bounds__(256) void wrms_masked_kernel(const double* __restrict__ X, const double* __restrict__ W,
+                                                          const double* __restrict__ mask, double* __restrict__ out, int n,
+                                                          const int* __restrict__ idx) {
+    extern __shared__ __align__(16) double sm[];
+    const long vb = (long)idx[blockIdx.x] * n;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const double p = (X[vb + i] * W[vb + i]) * (mask[i] != 0.0 ? 1.0 : 0.0);
+        sm[i] = p * p;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = seq_sum_lds(sm, n);
 }
 
 // the constraint mask of one field (x: [batch][n]): violated[s] = 1 when a component of listed system s violates cvec
@@ -297,7 +318,7 @@ __global__ __launch_bounds__(256) void complete_step_kernel(VecState s, const in
         const double w = ewt_of(s, tmp, i);  // tmp == new phi[0]
         s.ewt[vb + i] = w;
         if (w <= 0.0) s_bad = 1;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
-        const double p = tmp * w;
+        const double p = mask_term(s.mask, i, tmp * w);
         sm[i] = p * p;
     }
     __syncthreads();

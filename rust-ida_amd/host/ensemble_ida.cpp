@@ -23,8 +23,8 @@
 //
 // Deviations from the reference text, identical to the oracle's: Q1 (jac at tn), Q2 (LU failure is a
 // recoverable lsetup failure), Q3 (Newton breaks out on ConvergenceRecover with a current Jacobian), Q4 (Newton
-// ConvergenceRecover is recoverable at step level), Q5 (reset() rescales phi[1] only). Constraints and tstop are out of
-// scope (the reference has no setter for either).
+// ConvergenceRecover is recoverable at step level), Q5 (reset() rescales phi[1] only), Q15 (ONE_STEP's TSTOP return consumes the stop
+// time). The stop time is per system (idaens_set_stop_time) and lives in SysCore, so it travels to the device steppers.
 //
 // A system whose solve call ended in a fatal IdaError (too much work, error-test or convergence failures, ...) is `dead`:
 // the reference's Ida::solve could be called again after such an error and would try to continue; here the status is
@@ -697,6 +697,35 @@ int idaens_set_fused_newton(idaens* e, int on) {
     return 0;
 }
 
+int idaens_set_stop_time(idaens* e, const double* hTstop, int ntstop) {
+    if (!e) return -1;
+    if (hTstop && ntstop != 1 && ntstop != e->batch) return efail(e, -2, "idaens_set_stop_time: ntstop is 1 or batch (%d), not %d", e->batch, ntstop);
+    for (int b = 0; b < e->batch; ++b)
+        if (e->sys[b].ph != PH_IDLE)
+            return efail(e, -2, "idaens_set_stop_time: system %d is inside a round-limited call (IDAENS_UNFINISHED): finish that call first", b);
+    for (int b = 0; b < e->batch && hTstop; ++b) {
+        const double t = hTstop[ntstop == 1 ? 0 : b];
+        const Sys& s = e->sys[b];
+        if (t != t) continue;
+        if (std::isinf(t)) return efail(e, -2, "idaens_set_stop_time: the stop time of system %d is infinite", b);
+        if (s.nst > 0 && (t - s.tn) * s.hh < 0.0)  // IDASetStopTime's check
+            return efail(e, -2, "idaens_set_stop_time: the stop time %.17g of system %d is behind its current t = %.17g in the direction of integration",
+                         t, b, s.tn);
+    }
+    for (int b = 0; b < e->batch; ++b) {
+        const double t = hTstop ? hTstop[ntstop == 1 ? 0 : b] : std::nan("");
+        Sys& s = e->sys[b];
+        s.tstopset = t == t;
+        s.tstop = s.tstopset ? t : 0.0;
+    }
+    return 0;
+}
+int idaens_get_stop_time(const idaens* e, double* hTstop) {
+    if (!e || !hTstop) return -1;
+    for (int b = 0; b < e->batch; ++b) hTstop[b] = e->sys[b].tstopset ? e->sys[b].tstop : std::nan("");
+    return 0;
+}
+
 int idaens_set_max_ord(idaens* e, int maxord) {
     if (!e || maxord < 1 || maxord > MAXORD_DEFAULT) return -1;
     e->maxord = maxord;
@@ -838,8 +867,17 @@ int read_constraints(idaens* e) {
     return 0;
 }
 
+// The masked error norms (idahip_set_suppress_alg) need the id vector: C IDA's IDA_MISSING_ID. Read by every solve call, as the
+// constraints are.
+int check_suppress_alg(idaens* e) {
+    if (idahip_suppress_alg(e->ctx) == 1 && idahip_id(e->ctx, nullptr) != 1)
+        return efail(e, -2, "suppress_alg is on and the ctx has no id vector (idahip_set_id)");
+    return 0;
+}
+
 int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long max_rounds) {
     if (const int rcc = read_constraints(e)) return rcc;
+    if (const int rcm = check_suppress_alg(e)) return rcm;
     e->started = true;
     if (const int mode = device_ctl_applies(e, C)) return solve_core_device(e, C, hTret, hStatus, max_rounds, mode);
     std::vector<Sys>& S = e->sys;
@@ -1023,6 +1061,9 @@ int idaens_stream(idaens* e, const double* touts, int ntout, long max_rounds, lo
         for (int b = 0; b < e->batch; ++b) e->start_round[b] = e->total_rounds + (int64_t)b * stagger_rounds / e->batch;
     }
     if (e->nrtfn > 0) return efail(e, -2, "idaens_stream does not combine with root finding");
+    for (int b = 0; b < e->batch; ++b)
+        if (e->sys[b].tstopset)
+            return efail(e, -2, "idaens_stream does not combine with a stop time (system %d has one): a restarted system is Ida::new, which has none", b);
     if (!e->have_ic) return efail(e, -2, "no snapshot of the initial conditions (idaens_create failed to take it)");
     SolveCall C;
     C.touts = touts;
@@ -1314,6 +1355,8 @@ extern "C" int idaens_calc_ic(idaens* e, int icopt, double tout1, int32_t* hStat
     if (e->started) return efail(e, -2, "idaens_calc_ic: only before the first solve, solve_schedule or stream call");
     if (idahip_constraints(e->ctx, nullptr) == 1) return efail(e, -2, "idaens_calc_ic: a ctx with constraints is not supported (idahip_set_constraints)");
     if (idahip_krylov(e->ctx, nullptr) == 1) return efail(e, -2, "idaens_calc_ic: a Krylov ctx is not supported (idahip_create_krylov)");
+    if (idahip_suppress_alg(e->ctx) == 1)
+        return efail(e, -2, "idaens_calc_ic: not with suppress_alg on (set_id, calc_ic, idahip_set_suppress_alg(1), solve is the supported order)");
     if (!e->have_ic) return efail(e, -2, "no snapshot of the initial conditions (idaens_create failed to take it)");
     return calc_ic(e, icopt, tout1, hStatus);
 }

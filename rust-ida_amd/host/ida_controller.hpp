@@ -100,6 +100,9 @@ struct SysCore {
     double tlo = 0.0, thi = 0.0, trout = 0.0, ttol = 0.0, toutc = 0.0;
     int taskc = 0;
     long nge = 0;
+    // --- stop time (C IDA's IDASetStopTime; idaens_set_stop_time): ida_tstop = Some(tstop) when tstopset (src/lib.rs:147)
+    double tstop = 0.0;
+    bool tstopset = false;
 };
 
 IDA_HD inline double signum(double x) {  // f64::signum
@@ -144,6 +147,8 @@ IDA_HD inline double set_coeffs(SysCore& s) {
 
 // ---------------------------------------------------------------- one step attempt begins: step() prologue (lib.rs:619-653),
 // set_coeffs, tn += hh, and the prologue of nonlinear_solve (lib.rs:792-812: lsetup decision, ss resets)
+// TS = false compiles the stop time out (the device lock-step rounds are instantiated both ways, see stop_test1 in ida_solve_flow.hpp)
+template <bool TS = true>
 IDA_HD inline void begin_attempt(SysCore& s) {
     if (s.ph == PH_LOOP_TOP) {  // entering step()
         s.saved_t = s.tn;
@@ -163,6 +168,9 @@ IDA_HD inline void begin_attempt(SysCore& s) {
     s.n_attempts += 1;
     s.ck = set_coeffs(s);
     s.tn += s.hh;
+    if constexpr (TS) {
+        if (s.tstopset && (s.tn - s.tstop) * s.hh > 1.0) s.tn = s.tstop;  // Q6 kept (lib.rs:640-644: `> 1` where C IDA has `> 0`)
+    }
     s.call_lsetup = false;
     if (s.nst == 0) {
         s.cjold = s.cj;

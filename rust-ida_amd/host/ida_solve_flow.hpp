@@ -5,7 +5,7 @@
 //   * the device steppers (csrc/ida_flow.hpp, hipcc): per thread (tiny_ida.hpp) or per workgroup (round_ida.hpp).
 // Mirrors, with the reference's names:
 //   Ida::solve            src/impl_solve.rs:69-376  (first-call scalars, call entry, loop-top checks, failed step)
-//   stop_test1/2          src/impl_stop_test.rs:36-211 (no tstop: the reference has no setter)
+//   stop_test1/2          src/impl_stop_test.rs:36-211 (tstop: idaens_set_stop_time; the reference has the tests but no setter)
 //   r_check1/2/3, root_finding  src/impl_r_check.rs:32-576
 // Whatever touches vectors goes through a backend B, a small adapter each side writes. Every member returns 0 or a negative
 // IDAENS_* code, which the functions here pass up unchanged (a backend that always returns 0 costs nothing: the checks fold):
@@ -228,45 +228,103 @@ IDA_HD inline int r_check3(SysCore& s, RS& rs, int nr, B& be) {
     return ier;
 }
 
-// ---------------------------------------------------------------- stop tests (impl_stop_test.rs:36-211), tstop == None
-template <class B>
+// ---------------------------------------------------------------- stop tests (impl_stop_test.rs:36-211)
+// With a stop time (s.tstopset, idaens_set_stop_time) a test may return IDAENS_TSTOP_RETURN -- y(tstop) interpolated, tret = tretlast =
+// tstop, the stop time consumed (ida_tstop = None) -- or IDAENS_BAD_TSTOP, or clip hh so that the next step ends at tstop.
+// One deviation from the reference's text: the ONE_STEP branch of stop_test1 returns TSTOP without clearing the
+// stop time there (impl_stop_test.rs:109-113), so every later ONE_STEP call would return TSTOP again; C IDA clears it, and so does this.
+IDA_HD inline double tstop_roundoff(const SysCore& s) { return 100.0 * F64_EPS * (IDA_FABS(s.tn) + IDA_FABS(s.hh)); }
+// the step after this one would pass tstop: it ends there instead
+IDA_HD inline void tstop_clip_hh(SysCore& s) {
+    if ((s.tn + s.hh - s.tstop) * s.hh > 0.0) s.hh = (s.tstop - s.tn) * (1.0 - 4.0 * F64_EPS);
+}
+
+// whether tn has reached the stop time (within the round-off of the step)
+template <bool TS>
+IDA_HD inline bool tstop_reached(const SysCore& s) {
+    if constexpr (TS) return s.tstopset && IDA_FABS(s.tn - s.tstop) <= tstop_roundoff(s);
+    else return false;
+}
+template <bool TS>
+IDA_HD inline bool tstop_is_set(const SysCore& s) {
+    if constexpr (TS) return s.tstopset;
+    else return false;
+}
+// TS = false compiles the stop time out of the functions below, for a caller that knows no system of its call has one: with it
+// compiled in, stop_test1 alone costs the no-roots round_begin_kernel of the device lock-step rounds 58 -> 75 vector registers and a
+// wave of occupancy, so those kernels are instantiated both ways, as they are for ROOTS.
+
+// (each test interpolates at ONE place, for tout or for tstop: the device steppers inline get_solution at every call site)
+template <bool TS = true, class B>
 IDA_HD inline int stop_test1(SysCore& s, double tout, int itask, B& be) {
+    if (tstop_is_set<TS>(s)) {
+        if ((s.tn - s.tstop) * s.hh > 0.0) return IDAENS_BAD_TSTOP;  // the stop time is behind tn
+    }
+    double t;
+    bool at_tstop = false;
     if (itask == IDAENS_NORMAL) {
         if (tout == s.tretlast) {
             s.tretlast = tout;
             s.tret = tout;
             return IDAENS_SUCCESS;
         }
-        if ((s.tn - tout) * s.hh >= 0.0) {
-            const int ier = be.solution_at(tout);
-            if (ier) return ier;
-            s.tretlast = tout;
-            s.tret = tout;
-            return IDAENS_SUCCESS;
+        if ((s.tn - tout) * s.hh >= 0.0) t = tout;
+        else if (tstop_reached<TS>(s)) at_tstop = true;
+        else {
+            if (tstop_is_set<TS>(s)) tstop_clip_hh(s);
+            return IDAENS_UNFINISHED;  // ContinueSteps
         }
-        return IDAENS_UNFINISHED;  // ContinueSteps
+    } else {
+        if ((s.tn - s.tretlast) * s.hh > 0.0) t = s.tn;
+        else if (tstop_reached<TS>(s)) at_tstop = true;
+        else {
+            if (tstop_is_set<TS>(s)) tstop_clip_hh(s);
+            return IDAENS_UNFINISHED;
+        }
     }
-    if ((s.tn - s.tretlast) * s.hh > 0.0) {
-        (void)be.solution_at(s.tn);
-        s.tretlast = s.tn;
-        s.tret = s.tn;
-        return IDAENS_SUCCESS;
-    }
-    return IDAENS_UNFINISHED;
+    if (at_tstop) t = s.tstop;
+    const int ier = be.solution_at(t);
+    // a failed interpolation: returned as it is for tout (and for ONE_STEP's tstop, :109), BAD_TSTOP for NORMAL's tstop (:71-75);
+    // ONE_STEP's interpolation at tn itself cannot fail and the reference ignores its result (:97)
+    if (ier && (at_tstop || itask == IDAENS_NORMAL)) return (at_tstop && itask == IDAENS_NORMAL) ? IDAENS_BAD_TSTOP : ier;
+    s.tretlast = t;
+    s.tret = t;
+    if (!at_tstop) return IDAENS_SUCCESS;
+    s.tstopset = false;  // consumed. Q15: the reference leaves it set in the ONE_STEP branch (:109-113)
+    return IDAENS_TSTOP_RETURN;
 }
 
-template <class B>
+template <bool TS = true, class B>
 IDA_HD inline int stop_test2(SysCore& s, double tout, int itask, B& be) {
     if (itask == IDAENS_NORMAL) {
-        if ((s.tn - tout) * s.hh >= 0.0) {
-            s.tret = tout;
-            s.tretlast = tout;
-            (void)be.solution_at(tout);
-            return IDAENS_SUCCESS;
+        double t;
+        bool at_tstop = false;
+        if ((s.tn - tout) * s.hh >= 0.0) t = tout;
+        else if (tstop_reached<TS>(s)) {
+            at_tstop = true;
+            t = s.tstop;
+        } else {
+            if (tstop_is_set<TS>(s)) tstop_clip_hh(s);
+            return IDAENS_UNFINISHED;
         }
-        return IDAENS_UNFINISHED;
+        s.tret = t;
+        s.tretlast = t;
+        (void)be.solution_at(t);
+        if (!at_tstop) return IDAENS_SUCCESS;
+        s.tstopset = false;
+        return IDAENS_TSTOP_RETURN;
     }
-    s.tret = s.tn;  // OneStep: yy/yp already hold y(tn)
+    if (tstop_is_set<TS>(s)) {  // OneStep
+        if (tstop_reached<TS>(s)) {
+            (void)be.solution_at(s.tstop);
+            s.tret = s.tstop;
+            s.tretlast = s.tstop;
+            s.tstopset = false;
+            return IDAENS_TSTOP_RETURN;
+        }
+        tstop_clip_hh(s);
+    }
+    s.tret = s.tn;  // yy/yp already hold y(tn)
     s.tretlast = s.tn;
     return IDAENS_SUCCESS;
 }
@@ -274,7 +332,7 @@ IDA_HD inline int stop_test2(SysCore& s, double tout, int itask, B& be) {
 // ---------------------------------------------------------------- entry of one Ida::solve(s.tout_cur) call for a system that is
 // between calls (impl_solve.rs:179-241): root checks and stop tests. IDAENS_UNFINISHED when the system has to step, else the
 // status this call returns with (tret set).
-template <class RS, class B>
+template <bool TS = true, class RS, class B>
 IDA_HD inline int enter_call(SysCore& s, RS& rs, int nr, int itask, B& be) {
     const double tout = s.tout_cur;
     s.nstloc = 0;
@@ -318,7 +376,7 @@ IDA_HD inline int enter_call(SysCore& s, RS& rs, int nr, int itask, B& be) {
         }
     }
     if (s.nst > 0) {
-        const int istate = stop_test1(s, tout, itask, be);
+        const int istate = stop_test1<TS>(s, tout, itask, be);
         if (istate != IDAENS_UNFINISHED) {
             if (istate < 0) s.dead = true;
             return istate;
@@ -330,6 +388,7 @@ IDA_HD inline int enter_call(SysCore& s, RS& rs, int nr, int itask, B& be) {
 // ---------------------------------------------------------------- the scalars of the first-call block (impl_solve.rs:84-173)
 // ypnorm = ||phi[1]|| for the h0 heuristic, p0nrm = ||phi[0]|| for the first tolsf test. false: the call returns IDAENS_ILL_INPUT
 // for this system; true: it has started (the caller runs r_check1, then scales phi[1] by hh).
+template <bool TS = true>
 IDA_HD inline bool first_call_scalars(SysCore& s, double tout, double ypnorm, double p0nrm, double epcon, double hmax_inv, bool y0_violates) {
     const double tdist = IDA_FABS(tout - s.tn);
     const double troundoff = 2.0 * F64_EPS * (IDA_FABS(s.tn) + IDA_FABS(tout));
@@ -343,15 +402,24 @@ IDA_HD inline bool first_call_scalars(SysCore& s, double tout, double ypnorm, do
         s.tret = s.tn;
         return false;
     }
-    s.setup_done = true;
-    s.hh = s.hin;
-    if (s.hh == 0.0) {
-        s.hh = 0.001 * tdist;
-        if (ypnorm > 2.0 / s.hh) s.hh = 0.5 / ypnorm;  // Q7 kept (impl_solve.rs:127)
-        if (tout < s.tn) s.hh = -s.hh;
+    double hh = s.hin;
+    if (hh == 0.0) {
+        hh = 0.001 * tdist;
+        if (ypnorm > 2.0 / hh) hh = 0.5 / ypnorm;  // Q7 kept (impl_solve.rs:127)
+        if (tout < s.tn) hh = -hh;
     }
-    const double rh = IDA_FABS(s.hh) * hmax_inv;
-    if (rh > 1.0) s.hh /= rh;
+    const double rh = IDA_FABS(hh) * hmax_inv;
+    if (rh > 1.0) hh /= rh;
+    if (tstop_is_set<TS>(s)) {  // impl_solve.rs:137-150
+        if ((s.tstop - s.tn) * hh <= 0.0) {
+            s.status = IDAENS_ILL_INPUT;  // the stop time is behind t0 in the direction of integration: nothing of the record has changed
+            s.tret = s.tn;
+            return false;
+        }
+        if ((s.tn + hh - s.tstop) * hh > 0.0) hh = (s.tstop - s.tn) * (1.0 - 4.0 * F64_EPS);
+    }
+    s.setup_done = true;
+    s.hh = hh;
     s.h0u = s.hh;
     s.kk = 0;
     s.kused = 0;

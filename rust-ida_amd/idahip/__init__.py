@@ -49,12 +49,14 @@ HIP_SYMBOLS = [
     "idahip_newton_iter_krylov",
     "idahip_set_krylov_band_prec", "idahip_krylov_band_prec", "idahip_krylov_psetup", "idahip_krylov_psolve", "idahip_krylov_download_prec",
     "idahip_krylov_upload_prec",
+    "idahip_set_suppress_alg", "idahip_suppress_alg", "idahip_wrms_masked",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
     "idaens_get_roots", "idaens_solve", "idaens_solve_schedule", "idaens_stream", "idaens_stream_group", "idaens_solve_schedule_group",
     "idaens_get_counter", "idaens_get_real", "idaens_get_yy", "idaens_get_yp", "idaens_get_dky", "idaens_total_newton_iters",
     "idaens_total_rounds", "idaens_trace_system", "idaens_trace_len", "idaens_trace_get", "idaens_calc_ic",
+    "idaens_set_stop_time", "idaens_get_stop_time",
 ]
 
 _libs = None
@@ -151,6 +153,9 @@ def load():
     H.idahip_nls_lsetup_dq.argtypes = [vp, dp, dp, dp, i32p, i32p, ci]
     H.idahip_set_id.argtypes = [vp, dp]
     H.idahip_id.argtypes = [vp, dp]
+    H.idahip_set_suppress_alg.argtypes = [vp, ci]
+    H.idahip_suppress_alg.argtypes = [vp]
+    H.idahip_wrms_masked.argtypes = [vp, vp, vp, dp, i32p, ci]
     H.idahip_set_constraints.argtypes = [vp, dp]
     H.idahip_constraints.argtypes = [vp, dp]
     H.idahip_post_newton_constr.argtypes = [vp, dp, i32p, dp, i32p, dp, i32p, dp, i32p, ci]
@@ -197,6 +202,8 @@ def load():
     E.idaens_solve_schedule.argtypes = [vp, dp, ci, dp, i32p, i32p, dp, dp, C.c_long]
     E.idaens_stream.argtypes = [vp, dp, ci, C.c_long, C.c_long, i64p]
     E.idaens_calc_ic.argtypes = [vp, ci, cd, i32p]
+    E.idaens_set_stop_time.argtypes = [vp, dp, ci]
+    E.idaens_get_stop_time.argtypes = [vp, dp]
     E.idaens_get_counter.argtypes = [vp, ci, i64p]
     E.idaens_get_real.argtypes = [vp, ci, dp]
     E.idaens_get_yy.argtypes = [vp, dp]
@@ -401,6 +408,14 @@ class Ctx:
         out = np.zeros(self.n)
         return out if self._chk(self.H.idahip_id(self.h, _p(out)), "id") == 1 else None
 
+    def set_suppress_alg(self, on=True):
+        """C IDA's IDASetSuppressAlg: the stepper's local error norms leave out the algebraic components (id[i] == 0). Belongs to
+        the ctx, is read at the start of every solve call; a solve call with it on and no id set is refused."""
+        self._chk(self.H.idahip_set_suppress_alg(self.h, 1 if on else 0), "set_suppress_alg")
+
+    def suppress_alg(self):
+        return self._chk(self.H.idahip_suppress_alg(self.h), "suppress_alg") == 1
+
     def set_constraints(self, c):
         """C IDA's IDASetConstraints: c[i] = 0.0 none, 1.0: y_i >= 0, -1.0: y_i <= 0, 2.0: y_i > 0,
         -2.0: y_i < 0, shared by the ensemble. None clears them; any other value is refused (-2)."""
@@ -597,6 +612,13 @@ class Ctx:
         idx = self.all_idx() if idx is None else _i32(idx)
         out = np.zeros(idx.size)
         self._chk(self.H.idahip_wrms(self.h, dX, dW, _p(out), _p(idx, i32p), idx.size), "wrms")
+        return out
+
+    def wrms_masked(self, dX, dW, idx=None):
+        """The weighted norm masked with the ctx's id: sqrt(sum_i ((x_i w_i) m_i)^2 / n), m_i = 1.0 where id[i] != 0."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        out = np.zeros(idx.size)
+        self._chk(self.H.idahip_wrms_masked(self.h, dX, dW, _p(out), _p(idx, i32p), idx.size), "wrms_masked")
         return out
 
     # --- NLProblem
@@ -899,6 +921,19 @@ class Ensemble:
     def set_max_ord(self, maxord):
         if self.E.idaens_set_max_ord(self.h, int(maxord)) != 0:
             raise IdaHipError("set_max_ord(%d) rejected" % maxord)
+
+    def set_stop_time(self, t):
+        """C IDA's IDASetStopTime, per system: a scalar (every system), an array [batch] in which NaN means "none for this
+        system", or None (clear all). A TSTOP_RETURN (status 1) consumes a system's stop time. Refusals raise IdaHipError."""
+        a = None if t is None else _f64(np.atleast_1d(t))
+        if self.E.idaens_set_stop_time(self.h, _p(a), 0 if a is None else a.size) != 0:
+            raise IdaHipError("set_stop_time: %s" % (self.E.idaens_last_error(self.h) or b"").decode())
+
+    def stop_time(self):
+        """The stop times [batch], NaN where a system has none."""
+        out = np.zeros(self.ctx.batch)
+        assert self.E.idaens_get_stop_time(self.h, _p(out)) == 0
+        return out
 
     def calc_ic(self, icopt, tout1):
         """C IDA's IDACalcIC for every system, before the first solve: YA_YDP_INIT corrects the algebraic components of y0 and
