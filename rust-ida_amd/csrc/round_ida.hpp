@@ -56,8 +56,8 @@ struct RoundArgs {
 };
 
 // vector backend of IdaFlow: a workgroup of WG_NT threads (one wavefront: every lane runs the scalar logic, in lock-step, on the
-// workgroup's one copy of the controller record in LDS) owns system b; sums are accumulated left to right by one lane
-// (seq_sum_lds) and broadcast through LDS, exactly as the batched kernels of vector_kernels.hpp do
+// workgroup's one copy of the controller record in LDS) owns system b. The arithmetic of an element is vector_elems.hpp's, as in
+// the batched kernels of vector_kernels.hpp; the scalars come from the record and the sums are broadcast through LDS (res()).
 constexpr int WG_NT = 64;
 
 struct WgVec {
@@ -66,20 +66,11 @@ struct WgVec {
     const long vb;
     double* sm;  // LDS: 4 * n doubles of summands + 8 doubles of results
 
-    __device__ double& phi(int j, int i) const { return a.v.phi[j * a.v.phistride + vb + i]; }
     __device__ double* res() const { return sm + 4 * n; }
 
     __device__ void init_first(double* ypnorm, double* p0nrm) const {
         __syncthreads();
-        for (int i = threadIdx.x; i < n; i += WG_NT) {
-            const double y = phi(0, i);
-            const double e = ewt_of(a.v, y, i);
-            a.v.ewt[vb + i] = e;
-            const double p = mask_term(a.v.mask, i, phi(1, i) * e);
-            sm[i] = p * p;
-            const double q = mask_term(a.v.mask, i, y * e);
-            sm[n + i] = q * q;
-        }
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_init_first(a.v, vb, i, LdsSink{sm + i, n});
         __syncthreads();
         if (threadIdx.x < 2) res()[threadIdx.x] = seq_sum_lds(sm + threadIdx.x * n, n);
         __syncthreads();
@@ -87,57 +78,15 @@ struct WgVec {
         *p0nrm = sqrt(res()[1] / (double)n);
     }
     __device__ void scale_phi1(double f) const {
-        for (int i = threadIdx.x; i < n; i += WG_NT) phi(1, i) *= f;
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_phi(a.v, 1, vb, i) *= f;
     }
     __device__ void predict(const idactl::SysCore& s) const {
-        for (int i = threadIdx.x; i < n; i += WG_NT) {
-            double yyp = 0.0, ypp = 0.0;
-            for (int j = 0; j <= s.kk; ++j) {
-                double p = phi(j, i);
-                if (j >= s.ns) {
-                    p *= s.beta[j];
-                    phi(j, i) = p;
-                }
-                yyp = yyp + p;
-                if (j >= 1) ypp = ypp + s.gamma[j] * p;
-            }
-            a.v.yypredict[vb + i] = yyp;
-            a.v.yppredict[vb + i] = ypp;
-        }
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_predict(a.v, vb, i, s.kk, s.ns, s.beta, s.gamma);
     }
     __device__ void post_newton(const idactl::SysCore& s, double* norms) const {
         const int kk = s.kk;
         __syncthreads();
-        for (int i = threadIdx.x; i < n; i += WG_NT) {
-            const double e = a.v.ee[vb + i];
-            const double w = a.v.ewt[vb + i];
-            a.v.yy[vb + i] = a.v.yypredict[vb + i] + e;
-            a.v.yp[vb + i] = a.v.yppredict[vb + i] + s.cj * e;
-            double p = mask_term(a.v.mask, i, e * w);
-            sm[i] = p * p;
-            double d = 0.0;
-            if (kk > 1) {
-                d = phi(kk, i) + e;
-                p = mask_term(a.v.mask, i, d * w);
-                sm[n + i] = p * p;
-            } else {
-                sm[n + i] = 0.0;
-            }
-            if (kk > 2) {
-                d = d + phi(kk - 1, i);
-                p = mask_term(a.v.mask, i, d * w);
-                sm[2 * n + i] = p * p;
-            } else {
-                sm[2 * n + i] = 0.0;
-            }
-            if (kk + 1 < MXORDP1) {
-                const double tmp = e - phi(kk + 1, i);
-                p = mask_term(a.v.mask, i, tmp * w);
-                sm[3 * n + i] = p * p;
-            } else {
-                sm[3 * n + i] = 0.0;
-            }
-        }
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_post_newton(a.v, vb, i, kk, s.cj, true, LdsSink{sm + i, n});
         __syncthreads();
         if (threadIdx.x < 4) res()[threadIdx.x] = seq_sum_lds(sm + threadIdx.x * n, n);
         __syncthreads();
@@ -145,27 +94,14 @@ struct WgVec {
     }
     __device__ void restore_vec(const idactl::SysCore& s, int kk_att, int ns_att) const {
         if (ns_att > kk_att) return;
-        for (int i = threadIdx.x; i < n; i += WG_NT)
-            for (int j = ns_att; j <= kk_att; ++j) phi(j, i) *= s.cvals[j - ns_att];
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_restore(a.v, vb, i, kk_att, ns_att, s.cvals);
     }
     __device__ void complete_step_vec(idactl::SysCore& s, int kused, double ck, int maxord) const {
         __syncthreads();
         if (threadIdx.x == 0) res()[1] = 0.0;
         __syncthreads();
         for (int i = threadIdx.x; i < n; i += WG_NT) {
-            const double e = a.v.ee[vb + i];
-            if (kused < maxord) phi(kused + 1, i) = e;
-            double tmp = e;
-            for (int j = kused; j >= 0; --j) {
-                tmp = tmp + phi(j, i);
-                phi(j, i) = tmp;
-            }
-            a.v.ee[vb + i] = e * ck;
-            const double w = ewt_of(a.v, tmp, i);
-            a.v.ewt[vb + i] = w;
-            if (w <= 0.0) res()[1] = 1.0;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
-            const double p = mask_term(a.v.mask, i, tmp * w);
-            sm[i] = p * p;
+            if (el_complete_step(a.v, vb, i, kused, ck, maxord, LdsSink{sm + i, n})) res()[1] = 1.0;
         }
         __syncthreads();
         if (threadIdx.x == 0) res()[0] = seq_sum_lds(sm, n);
@@ -174,26 +110,17 @@ struct WgVec {
         s.ewt_bad = res()[1] != 0.0;
     }
     __device__ void get_solution_vec(const idactl::SysCore& s, int kord) const {
-        for (int i = threadIdx.x; i < n; i += WG_NT) {
-            double y = 0.0, yp = 0.0;
-            for (int j = 0; j <= kord; ++j) {
-                const double p = phi(j, i);
-                y = y + s.cvals[j] * p;
-                if (j >= 1) yp = yp + s.dvals[j - 1] * p;
-            }
-            a.v.yy[vb + i] = y;
-            a.v.yp[vb + i] = yp;
-        }
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_get_solution(a.v, vb, i, kord, s.cvals, s.dvals);
     }
     // root functions (ida_flow.hpp): an element of yy may have been written by another thread of the workgroup
     __device__ void sync() const { __syncthreads(); }
     __device__ double yy_at(int i) const { return a.v.yy[vb + i]; }
-    __device__ double phi_at(int j, int i) const { return a.v.phi[j * a.v.phistride + vb + i]; }
+    __device__ double phi_at(int j, int i) const { return el_phi(a.v, j, vb, i); }
     __device__ void yy_from_phi01(double f) const {
-        for (int i = threadIdx.x; i < n; i += WG_NT) a.v.yy[vb + i] = phi(0, i) + f * phi(1, i);
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_yy_from_phi01(a.v, vb, i, f);
     }
     __device__ void yy_add_phi1(double f) const {
-        for (int i = threadIdx.x; i < n; i += WG_NT) a.v.yy[vb + i] = a.v.yy[vb + i] + f * phi(1, i);
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_yy_add_phi1(a.v, vb, i, f);
     }
     __device__ void emit_output(int slot) const {
         // (yy / yp were written by this thread's own get_solution_vec just before, same index mapping: no barrier needed)
@@ -204,13 +131,7 @@ struct WgVec {
     }
     __device__ void restore_initial() const {
         __syncthreads();
-        for (int i = threadIdx.x; i < n; i += WG_NT) {
-            const double y = a.ic_y[vb + i], yp = a.ic_yp[vb + i];
-            phi(0, i) = y;
-            phi(1, i) = yp;
-            a.v.yy[vb + i] = y;
-            a.v.yp[vb + i] = yp;
-        }
+        for (int i = threadIdx.x; i < n; i += WG_NT) el_restore_initial(a.v, vb, i, a.ic_y[vb + i], a.ic_yp[vb + i]);
         __syncthreads();
     }
 };

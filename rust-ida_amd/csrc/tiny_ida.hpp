@@ -6,10 +6,11 @@
 // The scalar decisions are the SAME source as the host stepper's (host/ida_controller.hpp: set_coeffs, begin_attempt,
 // conv_test, test_error, handle_n_flag, complete_step_scalars, get_solution_coeffs), compiled for the device with
 // pow = glibc_pow::pow (glibc_pow.hpp: glibc's __pow_fma restated instruction for instruction), so h, order and every counter
-// carry the reference's bits. The vector parts repeat the arithmetic of the batched kernels (vector_kernels.hpp,
-// problem_kernels.hpp, solve_kernels.hpp, lu_kernels.hpp's tiny_getrf) element for element; with one thread per system every
-// sum is sequential by construction. The control flow of Ida::solve is ida_flow.hpp's (shared with the workgroup-per-system
-// stepper of round_ida.hpp); this file supplies the one-thread vector backend and the in-thread Newton solve:
+// carry the reference's bits. The arithmetic of a vector element is vector_elems.hpp's, shared with the batched kernels
+// (vector_kernels.hpp); the residuals, the Jacobians and the LU repeat problem_kernels.hpp, solve_kernels.hpp and lu_kernels.hpp's
+// tiny_getrf element for element. With one thread per system every sum is sequential by construction. The control flow of
+// Ida::solve is ida_flow.hpp's (shared with the workgroup-per-system stepper of round_ida.hpp); this file supplies the
+// one-thread vector backend and the in-thread Newton solve:
 //   Ida::solve            /root/reference/src/impl_solve.rs:69-376     (first-call block, loop-top checks, stop tests)
 //   Ida::step             /root/reference/src/lib.rs:613-711
 //   nonlinear_solve       /root/reference/src/lib.rs:787-890
@@ -47,133 +48,61 @@ struct TinyIdaArgs {
     idahip_root_state* roots;    // [batch] or null (f.nrt == 0)
 };
 
-// vector backend of IdaFlow: one thread owns system b (the arithmetic of vector_kernels.hpp, element for element)
+// vector backend of IdaFlow: one thread owns system b and loops over its elements (vector_elems.hpp's arithmetic; the sums
+// accumulate in registers)
 struct TinyVec {
     const TinyIdaArgs& a;
     const int b, n;
     const long vb;   // offset of the system's vectors in a.v's arrays (0 when they are this thread's block of LDS)
     const long gvb;  // offset of the system in the global arrays (initial conditions)
 
-    __device__ double& phi(int j, int i) const { return a.v.phi[j * a.v.phistride + vb + i]; }
+    __device__ double& phi(int j, int i) const { return el_phi(a.v, j, vb, i); }
 
-    // initial_setup's ewt_set(phi[0]) and the two norms of the first call (init_first_kernel)
+    // initial_setup's ewt_set(phi[0]) and the two norms of the first call
     __device__ void init_first(double* ypnorm, double* p0nrm) const {
-        double s1 = 0.0, s0 = 0.0;
-        for (int i = 0; i < n; ++i) {
-            const double y = phi(0, i);
-            const double e = ewt_of(a.v, y, i);
-            a.v.ewt[vb + i] = e;
-            const double p = mask_term(a.v.mask, i, phi(1, i) * e);
-            s1 = s1 + p * p;
-            const double q = mask_term(a.v.mask, i, y * e);
-            s0 = s0 + q * q;
-        }
-        *ypnorm = sqrt(s1 / (double)n);
-        *p0nrm = sqrt(s0 / (double)n);
+        double acc[2] = {0.0, 0.0};
+        for (int i = 0; i < n; ++i) el_init_first(a.v, vb, i, AccSink{acc});
+        *ypnorm = sqrt(acc[0] / (double)n);
+        *p0nrm = sqrt(acc[1] / (double)n);
     }
     __device__ void scale_phi1(double f) const {
         for (int i = 0; i < n; ++i) phi(1, i) *= f;
     }
-    // predict_kernel
     __device__ void predict(const idactl::SysCore& s) const {
-        for (int i = 0; i < n; ++i) {
-            double yyp = 0.0, ypp = 0.0;
-            for (int j = 0; j <= s.kk; ++j) {
-                double p = phi(j, i);
-                if (j >= s.ns) {
-                    p *= s.beta[j];
-                    phi(j, i) = p;
-                }
-                yyp = yyp + p;
-                if (j >= 1) ypp = ypp + s.gamma[j] * p;
-            }
-            a.v.yypredict[vb + i] = yyp;
-            a.v.yppredict[vb + i] = ypp;
-        }
+        for (int i = 0; i < n; ++i) el_predict(a.v, vb, i, s.kk, s.ns, s.beta, s.gamma);
     }
-    // final yy/yp and the four error-test norms (post_newton_kernel)
-    __device__ void post_newton(const idactl::SysCore& s, double* norms) const {
+    // the four error-test norms of the ee in memory, after the final yy / yp when write_yy
+    __device__ void post_newton(const idactl::SysCore& s, double* norms, bool write_yy = true) const {
         const int kk = s.kk;
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        for (int i = 0; i < n; ++i) {
-            const double e = a.v.ee[vb + i];
-            const double w = a.v.ewt[vb + i];
-            a.v.yy[vb + i] = a.v.yypredict[vb + i] + e;
-            a.v.yp[vb + i] = a.v.yppredict[vb + i] + s.cj * e;
-            double p = mask_term(a.v.mask, i, e * w);
-            s0 = s0 + p * p;
-            double d = 0.0;
-            if (kk > 1) {
-                d = phi(kk, i) + e;
-                p = mask_term(a.v.mask, i, d * w);
-                s1 = s1 + p * p;
-            }
-            if (kk > 2) {
-                d = d + phi(kk - 1, i);
-                p = mask_term(a.v.mask, i, d * w);
-                s2 = s2 + p * p;
-            }
-            if (kk + 1 < MXORDP1) {
-                const double tmp = e - phi(kk + 1, i);
-                p = mask_term(a.v.mask, i, tmp * w);
-                s3 = s3 + p * p;
-            }
-        }
-        norms[0] = sqrt(s0 / (double)n);
-        norms[1] = sqrt(s1 / (double)n);
-        norms[2] = sqrt(s2 / (double)n);
-        norms[3] = sqrt(s3 / (double)n);
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int i = 0; i < n; ++i) el_post_newton(a.v, vb, i, kk, s.cj, write_yy, AccSink{acc});
+        for (int k = 0; k < 4; ++k) norms[k] = sqrt(acc[k] / (double)n);
     }
-    // restore_kernel with the kk / ns of the failed attempt (cvals from restore_scalars)
+    // the kk / ns of the failed attempt (cvals from restore_scalars)
     __device__ void restore_vec(const idactl::SysCore& s, int kk_att, int ns_att) const {
-        if (ns_att > kk_att) return;
-        for (int i = 0; i < n; ++i)
-            for (int j = ns_att; j <= kk_att; ++j) phi(j, i) *= s.cvals[j - ns_att];
+        for (int i = 0; i < n; ++i) el_restore(a.v, vb, i, kk_att, ns_att, s.cvals);
     }
-    // complete_step_kernel: the phi recurrence, ee *= ck, the new ewt and ||phi[0]||
+    // the phi recurrence, ee *= ck, the new ewt and ||phi[0]||
     __device__ void complete_step_vec(idactl::SysCore& s, int kused, double ck, int maxord) const {
         bool bad = false;
         double acc = 0.0;
-        for (int i = 0; i < n; ++i) {
-            const double e = a.v.ee[vb + i];
-            if (kused < maxord) phi(kused + 1, i) = e;
-            double tmp = e;
-            for (int j = kused; j >= 0; --j) {
-                tmp = tmp + phi(j, i);
-                phi(j, i) = tmp;
-            }
-            a.v.ee[vb + i] = e * ck;
-            const double w = ewt_of(a.v, tmp, i);
-            a.v.ewt[vb + i] = w;
-            if (w <= 0.0) bad = true;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
-            const double p = mask_term(a.v.mask, i, tmp * w);
-            acc = acc + p * p;
-        }
+        for (int i = 0; i < n; ++i)
+            if (el_complete_step(a.v, vb, i, kused, ck, maxord, AccSink{&acc})) bad = true;
         s.phi0nrm = sqrt(acc / (double)n);
         s.ewt_bad = bad;
     }
-    // get_solution_kernel
     __device__ void get_solution_vec(const idactl::SysCore& s, int kord) const {
-        for (int i = 0; i < n; ++i) {
-            double y = 0.0, yp = 0.0;
-            for (int j = 0; j <= kord; ++j) {
-                const double p = phi(j, i);
-                y = y + s.cvals[j] * p;
-                if (j >= 1) yp = yp + s.dvals[j - 1] * p;
-            }
-            a.v.yy[vb + i] = y;
-            a.v.yp[vb + i] = yp;
-        }
+        for (int i = 0; i < n; ++i) el_get_solution(a.v, vb, i, kord, s.cvals, s.dvals);
     }
     // root functions (ida_flow.hpp's backend of the shared root finding): one thread owns the system, nothing to synchronise
     __device__ void sync() const {}
     __device__ double yy_at(int i) const { return a.v.yy[vb + i]; }
     __device__ double phi_at(int j, int i) const { return phi(j, i); }
     __device__ void yy_from_phi01(double f) const {
-        for (int i = 0; i < n; ++i) a.v.yy[vb + i] = phi(0, i) + f * phi(1, i);
+        for (int i = 0; i < n; ++i) el_yy_from_phi01(a.v, vb, i, f);
     }
     __device__ void yy_add_phi1(double f) const {
-        for (int i = 0; i < n; ++i) a.v.yy[vb + i] = a.v.yy[vb + i] + f * phi(1, i);
+        for (int i = 0; i < n; ++i) el_yy_add_phi1(a.v, vb, i, f);
     }
     __device__ void emit_output(int slot) const {  // the output of the tout just reached (idaens_solve_schedule's hYout / hYPout)
         if (a.yout)
@@ -181,14 +110,8 @@ struct TinyVec {
         if (a.ypout)
             for (int i = 0; i < n; ++i) a.ypout[((long)slot * a.f.batch + b) * n + i] = a.v.yp[vb + i];
     }
-    __device__ void restore_initial() const {  // Ida::new again: restore_initial_kernel
-        for (int i = 0; i < n; ++i) {
-            const double y = a.ic_y[gvb + i], yp = a.ic_yp[gvb + i];
-            phi(0, i) = y;
-            phi(1, i) = yp;
-            a.v.yy[vb + i] = y;
-            a.v.yp[vb + i] = yp;
-        }
+    __device__ void restore_initial() const {  // Ida::new again
+        for (int i = 0; i < n; ++i) el_restore_initial(a.v, vb, i, a.ic_y[gvb + i], a.ic_yp[gvb + i]);
     }
 };
 
@@ -205,79 +128,24 @@ struct TinyVecConstr : TinyVec {
         if (checked) {
             bool any = false;
             double sv = 0.0;
-            for (int i = 0; i < n; ++i) {
-                const double e = a.v.ee[vb + i];
-                const double y = a.v.yypredict[vb + i] + e;
-                a.v.yy[vb + i] = y;
-                a.v.yp[vb + i] = a.v.yppredict[vb + i] + s.cj * e;
-                const double c = constr[i], w = a.v.ewt[vb + i];
-                double v = 0.0;
-                if (idactl::constr_violated(c, y)) {
-                    v = idactl::constr_correction(c, y, w);
-                    any = true;
-                }
-                const double p = v * w;
-                sv = sv + p * p;
-            }
+            for (int i = 0; i < n; ++i)
+                if (el_constr_check(a.v, vb, i, constr[i], s.cj, AccSink{&sv})) any = true;
             if (any) {
                 if (sqrt(sv / (double)n) <= s.eps_newt) {
-                    for (int i = 0; i < n; ++i) {
-                        const double c = constr[i], y = a.v.yy[vb + i];
-                        if (idactl::constr_violated(c, y)) a.v.ee[vb + i] = a.v.ee[vb + i] - idactl::constr_correction(c, y, a.v.ewt[vb + i]);
-                    }
+                    for (int i = 0; i < n; ++i) el_constr_correct(a.v, vb, i, constr[i]);
                 } else {
                     double q = idactl::CONSTR_QMAX;
-                    for (int i = 0; i < n; ++i) {
-                        const double y = a.v.yy[vb + i];
-                        if (!idactl::constr_violated(constr[i], y)) continue;
-                        const double p0 = phi(0, i);
-                        const double t = p0 - y;
-                        if (t != 0.0) {
-                            const double quot = p0 / t;
-                            if (quot < q) q = quot;
-                        }
-                    }
+                    for (int i = 0; i < n; ++i) q = el_constr_quot(a.v, vb, i, constr[i], q);
                     *rr = idactl::constr_rr(q);
                     norms[0] = norms[1] = norms[2] = norms[3] = 0.0;
                     return 2;
                 }
-                error_norms(s, norms);  // of the corrected ee; yy and yp keep their uncorrected values
+                post_newton(s, norms, false);  // of the corrected ee; yy and yp keep their uncorrected values
                 return 1;
             }
         }
         post_newton(s, norms);
         return 0;
-    }
-    // the four sums of post_newton without its writes to yy and yp
-    __device__ void error_norms(const idactl::SysCore& s, double* norms) const {
-        const int kk = s.kk;
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        for (int i = 0; i < n; ++i) {
-            const double e = a.v.ee[vb + i];
-            const double w = a.v.ewt[vb + i];
-            double p = mask_term(a.v.mask, i, e * w);
-            s0 = s0 + p * p;
-            double d = 0.0;
-            if (kk > 1) {
-                d = phi(kk, i) + e;
-                p = mask_term(a.v.mask, i, d * w);
-                s1 = s1 + p * p;
-            }
-            if (kk > 2) {
-                d = d + phi(kk - 1, i);
-                p = mask_term(a.v.mask, i, d * w);
-                s2 = s2 + p * p;
-            }
-            if (kk + 1 < MXORDP1) {
-                const double tmp = e - phi(kk + 1, i);
-                p = mask_term(a.v.mask, i, tmp * w);
-                s3 = s3 + p * p;
-            }
-        }
-        norms[0] = sqrt(s0 / (double)n);
-        norms[1] = sqrt(s1 / (double)n);
-        norms[2] = sqrt(s2 / (double)n);
-        norms[3] = sqrt(s3 / (double)n);
     }
     // the start check: a component of phi[0] violates its constraint
     __device__ bool constr_phi0_violated() const {

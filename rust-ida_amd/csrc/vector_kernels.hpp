@@ -1,56 +1,16 @@
-// Elementwise / norm kernels for the vector parts of the stepper that share the device-resident IDA state
-// (SURVEY.md 8(f)-1). One workgroup per listed system; all sums that feed decisions are accumulated left to right
-// by one lane so they carry the reference's bits.
-//   ewt_set        <- /root/reference/src/tol_control.rs:36-44, 71-82
-//   set_coeffs phi <- /root/reference/src/lib.rs:768-779
-//   predict        <- /root/reference/src/lib.rs:894-959
-//   final yy/yp    <- /root/reference/src/lib.rs:845-849
-//   test_error     <- /root/reference/src/lib.rs:983-1004 (vector part)
-//   restore        <- /root/reference/src/lib.rs:1057-1082
-//   complete_step  <- /root/reference/src/impl_complete_step.rs:74-77, 152-176; /root/reference/src/lib.rs:708
-//   get_solution   <- /root/reference/src/lib.rs:1319-1340
+// Kernels for the vector parts of the stepper that share the device-resident IDA state. One workgroup of 256
+// threads per listed system. The arithmetic of an element is vector_elems.hpp's, shared with the device-resident steppers; a
+// kernel takes its scalars from the per-list arrays and writes its sums (one lane each, left to right) to out[].
 #pragma once
-#include "common.hpp"
-#include "solve_kernels.hpp"
-#include "../host/ida_controller.hpp"
+#include "vector_elems.hpp"
 
 namespace idahip {
-
-struct VecState {
-    double* phi;  // [6][batch][n]
-    long phistride;  // batch*n
-    double *yy, *yp, *yypredict, *yppredict, *ewt, *ee, *delta;
-    int n;
-    double rtol, atol_s;
-    const double* atol_v;
-    const double* mask;  // the ctx's id vector [n] when idahip_set_suppress_alg is on, else null: the local error norms leave out id_i == 0
-};
-
-// one summand of a local error norm: p = x_i w_i, times the mask's 1.0 / 0.0 when there is one (norm_rms.rs:49-57 -- the product is
-// formed either way, so a non-finite masked element still makes the norm NaN). Without a mask this is p itself.
-__device__ __forceinline__ double mask_term(const double* mask, int i, double p) {
-    return mask ? p * (mask[i] != 0.0 ? 1.0 : 0.0) : p;
-}
-
-__device__ __forceinline__ double ewt_of(const VecState& s, double y, int i) {
-    const double at = s.atol_v ? s.atol_v[i] : s.atol_s;
-    return 1.0 / (s.rtol * fabs(y) + at);
-}
 
 // ewt = ewt_set(phi[0]); out[2s] = sum (phi[1]*ewt)^2; out[2s+1] = sum (phi[0]*ewt)^2
 __global__ __launch_bounds__(256) void init_first_kernel(VecState s, const int* __restrict__ idx, double* __restrict__ out) {
     extern __shared__ __align__(16) double sm[];
-    const int b = idx[blockIdx.x];
-    const long vb = (long)b * s.n;
-    for (int i = threadIdx.x; i < s.n; i += 256) {
-        const double y = s.phi[vb + i];
-        const double e = ewt_of(s, y, i);
-        s.ewt[vb + i] = e;
-        const double p = mask_term(s.mask, i, s.phi[s.phistride + vb + i] * e);
-        sm[i] = p * p;
-        const double q = mask_term(s.mask, i, y * e);
-        sm[s.n + i] = q * q;
-    }
+    const long vb = (long)idx[blockIdx.x] * s.n;
+    for (int i = threadIdx.x; i < s.n; i += 256) el_init_first(s, vb, i, LdsSink{sm + i, s.n});
     __syncthreads();
     if (threadIdx.x < 2) out[2 * blockIdx.x + threadIdx.x] = seq_sum_lds(sm + threadIdx.x * s.n, s.n);
 }
@@ -68,29 +28,8 @@ __global__ __launch_bounds__(256) void predict_kernel(VecState s, const int* __r
     const int b = idx[blockIdx.x];
     const long vb = (long)b * s.n;
     const int kk = kkns[2 * blockIdx.x], ns = kkns[2 * blockIdx.x + 1];
-    double bt[MXORDP1], gm[MXORDP1];
-#pragma unroll
-    for (int j = 0; j < MXORDP1; ++j) {
-        bt[j] = beta[MXORDP1 * blockIdx.x + j];
-        gm[j] = gamma[MXORDP1 * blockIdx.x + j];
-    }
-    for (int i = threadIdx.x; i < s.n; i += 256) {
-        double yyp = 0.0, ypp = 0.0;
-#pragma unroll
-        for (int j = 0; j < MXORDP1; ++j) {
-            if (j <= kk) {
-                double p = s.phi[j * s.phistride + vb + i];
-                if (j >= ns) {
-                    p *= bt[j];
-                    s.phi[j * s.phistride + vb + i] = p;
-                }
-                yyp = yyp + p;
-                if (j >= 1) ypp = ypp + gm[j] * p;
-            }
-        }
-        s.yypredict[vb + i] = yyp;
-        s.yppredict[vb + i] = ypp;
-    }
+    const double *bt = beta + MXORDP1 * blockIdx.x, *gm = gamma + MXORDP1 * blockIdx.x;
+    for (int i = threadIdx.x; i < s.n; i += 256) el_predict(s, vb, i, kk, ns, bt, gm);
 }
 
 // yy = yypredict + ee; yp = yppredict + cj*ee; four sequential squared-norm sums
@@ -102,36 +41,7 @@ __global__ __launch_bounds__(256) void post_newton_kernel(VecState s, const int*
     const long vb = (long)b * n;
     const double cj = cjs[blockIdx.x];
     const int kk = kks[blockIdx.x];
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const double e = s.ee[vb + i];
-        const double w = s.ewt[vb + i];
-        s.yy[vb + i] = s.yypredict[vb + i] + e;
-        s.yp[vb + i] = s.yppredict[vb + i] + cj * e;
-        double p = mask_term(s.mask, i, e * w);
-        sm[i] = p * p;
-        double d = 0.0;
-        if (kk > 1) {
-            d = s.phi[kk * s.phistride + vb + i] + e;  // delta = phi[kk] + ee   (lib.rs:992)
-            p = mask_term(s.mask, i, d * w);
-            sm[n + i] = p * p;
-        } else {
-            sm[n + i] = 0.0;
-        }
-        if (kk > 2) {
-            d = d + s.phi[(kk - 1) * s.phistride + vb + i];  // delta += phi[kk-1]  (lib.rs:1002)
-            p = mask_term(s.mask, i, d * w);
-            sm[2 * n + i] = p * p;
-        } else {
-            sm[2 * n + i] = 0.0;
-        }
-        if (kk + 1 < MXORDP1) {
-            const double tmp = e - s.phi[(kk + 1) * s.phistride + vb + i];  // ee - phi[kk+1]  (impl_complete_step.rs:75)
-            p = mask_term(s.mask, i, tmp * w);
-            sm[3 * n + i] = p * p;
-        } else {
-            sm[3 * n + i] = 0.0;
-        }
-    }
+    for (int i = threadIdx.x; i < n; i += 256) el_post_newton(s, vb, i, kk, cj, true, LdsSink{sm + i, n});
     __syncthreads();
     if (threadIdx.x < 4) out[4 * blockIdx.x + threadIdx.x] = seq_sum_lds(sm + threadIdx.x * n, n);
 }
@@ -163,19 +73,10 @@ __global__ __launch_bounds__(256) void post_newton_constr_kernel(VecState s, con
     }
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += 256) {
-        const double e = s.ee[vb + i];
-        const double y = s.yypredict[vb + i] + e;
-        s.yy[vb + i] = y;
-        s.yp[vb + i] = s.yppredict[vb + i] + cj * e;
         if (chk) {
-            const double c = cvec[i], w = s.ewt[vb + i];
-            double v = 0.0;
-            if (idactl::constr_violated(c, y)) {
-                v = idactl::constr_correction(c, y, w);
-                s_any = 1;
-            }
-            const double p = v * w;
-            sm[i] = p * p;
+            if (el_constr_check(s, vb, i, cvec[i], cj, LdsSink{sm + i, n})) s_any = 1;
+        } else {
+            el_final_yy(s, vb, i, s.ee[vb + i], cj);
         }
     }
     __syncthreads();
@@ -187,16 +88,7 @@ __global__ __launch_bounds__(256) void post_newton_constr_kernel(VecState s, con
     const int fl = s_flag;
     if (fl == 2) {
         double q = idactl::CONSTR_QMAX;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const double y = s.yy[vb + i];
-            if (!idactl::constr_violated(cvec[i], y)) continue;
-            const double p0 = s.phi[vb + i];
-            const double t = p0 - y;
-            if (t != 0.0) {
-                const double quot = p0 / t;
-                if (quot < q) q = quot;
-            }
-        }
+        for (int i = threadIdx.x; i < n; i += 256) q = el_constr_quot(s, vb, i, cvec[i], q);
         s_q[threadIdx.x] = q;
         __syncthreads();
         for (int w = 128; w > 0; w >>= 1) {
@@ -211,39 +103,8 @@ __global__ __launch_bounds__(256) void post_newton_constr_kernel(VecState s, con
         return;
     }
     for (int i = threadIdx.x; i < n; i += 256) {
-        double e = s.ee[vb + i];
-        const double w = s.ewt[vb + i];
-        if (fl == 1) {
-            const double c = cvec[i], y = s.yy[vb + i];
-            if (idactl::constr_violated(c, y)) {
-                e = e - idactl::constr_correction(c, y, w);
-                s.ee[vb + i] = e;
-            }
-        }
-        double p = mask_term(s.mask, i, e * w);
-        sm[i] = p * p;
-        double d = 0.0;
-        if (kk > 1) {
-            d = s.phi[kk * s.phistride + vb + i] + e;
-            p = mask_term(s.mask, i, d * w);
-            sm[n + i] = p * p;
-        } else {
-            sm[n + i] = 0.0;
-        }
-        if (kk > 2) {
-            d = d + s.phi[(kk - 1) * s.phistride + vb + i];
-            p = mask_term(s.mask, i, d * w);
-            sm[2 * n + i] = p * p;
-        } else {
-            sm[2 * n + i] = 0.0;
-        }
-        if (kk + 1 < MXORDP1) {
-            const double tmp = e - s.phi[(kk + 1) * s.phistride + vb + i];
-            p = mask_term(s.mask, i, tmp * w);
-            sm[3 * n + i] = p * p;
-        } else {
-            sm[3 * n + i] = 0.0;
-        }
+        if (fl == 1) el_constr_correct(s, vb, i, cvec[i]);
+        el_post_newton(s, vb, i, kk, cj, false, LdsSink{sm + i, n});
     }
     __syncthreads();
     if (threadIdx.x < 4) out[4 * blockIdx.x + threadIdx.x] = seq_sum_lds(sm + threadIdx.x * n, n);
@@ -287,9 +148,7 @@ __global__ __launch_bounds__(256) void restore_kernel(VecState s, const int* __r
     const long vb = (long)b * s.n;
     const int kk = kkns[2 * blockIdx.x], ns = kkns[2 * blockIdx.x + 1];
     if (ns > kk) return;
-    for (int i = threadIdx.x; i < s.n; i += 256) {
-        for (int j = ns; j <= kk; ++j) s.phi[j * s.phistride + vb + i] *= cvals[MXORDP1 * blockIdx.x + (j - ns)];
-    }
+    for (int i = threadIdx.x; i < s.n; i += 256) el_restore(s, vb, i, kk, ns, cvals + MXORDP1 * blockIdx.x);
 }
 
 // phi[kused+1] = ee (kused < maxord); tmp = ee; for j = kused..0: tmp += phi[j]; phi[j] = tmp; ee *= ck;
@@ -307,25 +166,11 @@ __global__ __launch_bounds__(256) void complete_step_kernel(VecState s, const in
     if (threadIdx.x == 0) s_bad = 0;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += 256) {
-        const double e = s.ee[vb + i];
-        if (kused < maxord) s.phi[(kused + 1) * s.phistride + vb + i] = e;
-        double tmp = e;
-        for (int j = kused; j >= 0; --j) {
-            tmp = tmp + s.phi[j * s.phistride + vb + i];
-            s.phi[j * s.phistride + vb + i] = tmp;
-        }
-        s.ee[vb + i] = e * ck;
-        const double w = ewt_of(s, tmp, i);  // tmp == new phi[0]
-        s.ewt[vb + i] = w;
-        if (w <= 0.0) s_bad = 1;  // `x <= 0` (impl_solve.rs:272): a NaN component is not bad
-        const double p = mask_term(s.mask, i, tmp * w);
-        sm[i] = p * p;
+        if (el_complete_step(s, vb, i, kused, ck, maxord, LdsSink{sm + i, n})) s_bad = 1;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        out[blockIdx.x] = seq_sum_lds(sm, n);
-        ewtbad[blockIdx.x] = s_bad;
-    }
+    if (threadIdx.x == 0) out[blockIdx.x] = seq_sum_lds(sm, n);
+    if (threadIdx.x == 0) ewtbad[blockIdx.x] = s_bad;
 }
 
 // yy = sum_{j<=kord} cvals[j]*phi[j]; yp = sum_{1<=j<=kord} dvals[j-1]*phi[j]  (from zero, scaled_add)
@@ -334,16 +179,7 @@ __global__ __launch_bounds__(256) void get_solution_kernel(VecState s, const int
     const int b = idx[blockIdx.x];
     const long vb = (long)b * s.n;
     const int kord = kords[blockIdx.x];
-    for (int i = threadIdx.x; i < s.n; i += 256) {
-        double y = 0.0, yp = 0.0;
-        for (int j = 0; j <= kord; ++j) {
-            const double p = s.phi[j * s.phistride + vb + i];
-            y = y + cvals[MXORDP1 * blockIdx.x + j] * p;
-            if (j >= 1) yp = yp + dvals[5 * blockIdx.x + (j - 1)] * p;
-        }
-        s.yy[vb + i] = y;
-        s.yp[vb + i] = yp;
-    }
+    for (int i = threadIdx.x; i < s.n; i += 256) el_get_solution(s, vb, i, kord, cvals + MXORDP1 * blockIdx.x, dvals + 5 * blockIdx.x);
 }
 
 // IDAGetDky (lib.rs:517-526): dky = sum_{j = k .. kused} cjk[j] * phi[j], from zero in ascending j, product then sum
@@ -365,13 +201,7 @@ __global__ __launch_bounds__(256) void restore_initial_kernel(VecState s, const 
                                                               const int* __restrict__ idx) {
     const int b = idx[blockIdx.x];
     const long vb = (long)b * s.n;
-    for (int i = threadIdx.x; i < s.n; i += 256) {
-        const double y = icy[vb + i], yp = icyp[vb + i];
-        s.phi[vb + i] = y;
-        s.phi[s.phistride + vb + i] = yp;
-        s.yy[vb + i] = y;
-        s.yp[vb + i] = yp;
-    }
+    for (int i = threadIdx.x; i < s.n; i += 256) el_restore_initial(s, vb, i, icy[vb + i], icyp[vb + i]);
 }
 
 }  // namespace idahip
