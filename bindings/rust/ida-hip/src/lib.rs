@@ -66,6 +66,9 @@ pub enum Problem {
     Heat1D,
     /// any residual / Jacobian pair evaluated on the host ([`HostProblem`])
     HostCallback,
+    /// 1-D Brusselator (reaction-diffusion) by the method of lines, two interleaved species (n = 2m, m >= 5); parameters
+    /// [a, b, d, ub, vb] per system; nonlinear, bandwidths (2, 2)
+    Bruss1D,
 }
 
 impl Problem {
@@ -76,6 +79,7 @@ impl Problem {
             Problem::LinearDense => sys::IDAHIP_LINEAR_DENSE,
             Problem::Heat1D => sys::IDAHIP_HEAT1D,
             Problem::HostCallback => sys::IDAHIP_HOST_CALLBACK,
+            Problem::Bruss1D => sys::IDAHIP_BRUSS1D,
         }
     }
 }
@@ -199,7 +203,7 @@ impl Ctx {
     }
 
     /// A band context (`idahip_create_band`): Jacobians with lower bandwidth `ml` and upper bandwidth `mu` are stored, factored and
-    /// solved in LAPACK band storage instead of n x n. `Problem::Heat1D` (ml, mu >= 1) or a host-callback problem, 8 < n <= 4096.
+    /// solved in LAPACK band storage instead of n x n. `Problem::Heat1D` (ml, mu >= 1), `Problem::Bruss1D` (ml, mu >= 2) or a host-callback problem, 8 < n <= 4096.
     pub fn new_band(device: i32, n: usize, batch: usize, problem: Problem, ml: usize, mu: usize) -> Result<Self, Error> {
         let mut raw: *mut sys::idahip_ctx = ptr::null_mut();
         let rc = unsafe {
@@ -212,7 +216,7 @@ impl Ctx {
     }
 
     /// A Krylov context (`idahip_create_krylov`): the matrix-free SPGMR solver of DESIGN.md section 4h, no matrix, no factors.
-    /// `Problem::Heat1D`, `Problem::LinearDense` or a host-callback problem (its residual alone), 8 < n <= 4096; `maxl` = 0 means 5,
+    /// `Problem::Heat1D`, `Problem::Bruss1D`, `Problem::LinearDense` or a host-callback problem (its residual alone), 8 < n <= 4096; `maxl` = 0 means 5,
     /// at most 16 and at most n.
     pub fn new_krylov(device: i32, n: usize, batch: usize, problem: Problem, maxl: usize) -> Result<Self, Error> {
         let mut raw: *mut sys::idahip_ctx = ptr::null_mut();

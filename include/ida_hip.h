@@ -37,8 +37,24 @@ typedef enum {
     IDAHIP_LORENZ63 = 1,     /* tests/lorenz63.rs:17-25,47-53; params [p, r, b] per system            (n = 3) */
     IDAHIP_LINEAR_DENSE = 2, /* F = A y' + B y - c, A/B dense column-major per system */
     IDAHIP_HEAT1D = 3,       /* 1-D heat, method of lines; params [kappa/dx^2] per system (config 4)           */
-    IDAHIP_HOST_CALLBACK = 4 /* any IdaProblem: res / jac are host functions (idahip_set_host_problem); slow path   */
+    IDAHIP_HOST_CALLBACK = 4, /* any IdaProblem: res / jac are host functions (idahip_set_host_problem); slow path  */
+    IDAHIP_BRUSS1D = 5       /* 1-D Brusselator (reaction-diffusion), method of lines; params [a, b, d, ub, vb] per system: below */
 } idahip_problem;
+
+/* IDAHIP_BRUSS1D: the nonlinear, stiff, banded device problem. m grid points, two species interleaved: n = 2m (even, n >= 10),
+ * y[2i] = u_i, y[2i+1] = v_i; parameters [a, b, d, ub, vb] per system (idahip_set_problem_params, nparam = 5), d = the diffusion
+ * coefficient divided by dx^2. The operation order is the definition; every line is one IEEE operation, nothing is contracted.
+ *   end points i = 0 and i = m-1 (algebraic):   r[2i] = u_i - ub;   r[2i+1] = v_i - vb
+ *   interior:  w  = (u_i*u_i)*v_i
+ *              lu = (u_{i-1} - 2.0*u_i) + u_{i+1};   lv = (v_{i-1} - 2.0*v_i) + v_{i+1}
+ *              r[2i]   = u'_i - (((a - (b + 1.0)*u_i) + w) + d*lu)
+ *              r[2i+1] = v'_i - ((b*u_i - w) + d*lv)
+ * J = dF/dy + cj dF/dy': identity rows at the end points; interior rows, with t2 = (2.0*u_i)*v_i and uu = u_i*u_i:
+ *   J(2i,  2i-2) = -d     J(2i,  2i)   = cj - ((t2 - (b + 1.0)) - 2.0*d)     J(2i,  2i+1) = -uu      J(2i,  2i+2) = -d
+ *   J(2i+1,2i-1) = -d     J(2i+1,2i)   = -(b - t2)     J(2i+1,2i+1) = cj + (uu + 2.0*d)              J(2i+1,2i+3) = -d
+ * and +0.0 everywhere else, the in-band entries such as J(2i, 2i-1) included: ml = mu = 2. Every ctx constructor refuses the kind
+ * for odd n or n < 10 (-2). It runs wherever IDAHIP_HEAT1D runs: dense, band (ml, mu >= 2) and Krylov ctx, band preconditioner of any
+ * width, difference-quotient Jacobians, idahip_ic_*, and the device lock-step rounds. */
 
 /* The user problem of kind IDAHIP_HOST_CALLBACK: Residual::res and Jacobian::jac of src/traits.rs:12-70 as C callbacks, called on
  * the host for one listed system at a time (`sys` = its index in the batch, `user` = the pointer given at registration).
@@ -78,7 +94,7 @@ int idahip_destroy(idahip_ctx* ctx);
 /* A BAND ctx (the SUNLinSol_Band of C IDA; the reference ships only `Dense`, crates/linear/src/traits.rs is where it plugs in):
  * the same ensemble, but the Jacobian of every system has lower bandwidth ml and upper bandwidth mu and is stored, factored and
  * solved in LAPACK band storage ([batch][ldab * n], ldab = 2 ml + mu + 1, rust-ida_amd/csrc/band_kernels.hpp) instead of n x n.
- * Kinds IDAHIP_HEAT1D (ml, mu >= 1) and IDAHIP_HOST_CALLBACK (idahip_set_host_band_problem), 8 < n <= 4096, 0 <= ml, mu < n;
+ * Kinds IDAHIP_HEAT1D (ml, mu >= 1), IDAHIP_BRUSS1D (ml, mu >= 2) and IDAHIP_HOST_CALLBACK (idahip_set_host_band_problem), 8 < n <= 4096, 0 <= ml, mu < n;
  * anything else is refused (-2). Exactness: pivots are those of dense_get_rf on the same matrix; factors, solutions and
  * integrations equal the dense ones by value (-0.0 == +0.0; steps, orders, counters, hused and tn bit-identical) for finite
  * inputs -- the contract in band_kernels.hpp. Dense-only calls (idahip_download_lu, idahip_set_linear_dense,
@@ -99,7 +115,7 @@ int idahip_ls_solve_band(idahip_ctx* ctx, int ml, int mu, const double* dAB, con
 /* ---- A KRYLOV ctx: matrix-free SPGMR behind the iterative branch of idaLsSolve (the reference has no iterative solver; this text and
  * DESIGN.md section 4h are the definition). C IDA's default iterative setup: SPGMR, no preconditioner, scaling by ewt on both sides,
  * modified Gram-Schmidt, maxl = 5, no restarts, J v by a difference quotient of the residual (idaLsDQJtimes). The ctx holds no work
- * matrix, no factors and no pivots: memory per system is O(maxl n) instead of O(n^2). Kinds IDAHIP_HEAT1D, IDAHIP_LINEAR_DENSE (the
+ * matrix, no factors and no pivots: memory per system is O(maxl n) instead of O(n^2). Kinds IDAHIP_HEAT1D, IDAHIP_BRUSS1D, IDAHIP_LINEAR_DENSE (the
  * problem's own A and B remain) and IDAHIP_HOST_CALLBACK (idahip_set_host_residual: there is no Jacobian to ask for); 8 < n <= 4096;
  * maxl = 0 means 5; maxl > 16 or maxl > n is refused (-2).
  *
@@ -173,7 +189,7 @@ int idahip_newton_iter_krylov(idahip_ctx* ctx, const double* hTn, const double* 
  * The band kernels equal the dense LU by value (-0.0 == +0.0) and nothing in SPGMR reads the sign of a zero.
  *
  * idahip_set_krylov_band_prec: turns the mode on and allocates the storage; ml = mu = -1 turns it off and frees it. Kinds
- * IDAHIP_HEAT1D and IDAHIP_HOST_CALLBACK (idahip_set_host_residual), the kinds with a band difference quotient; IDAHIP_LINEAR_DENSE is
+ * IDAHIP_HEAT1D, IDAHIP_BRUSS1D and IDAHIP_HOST_CALLBACK (idahip_set_host_residual), the kinds with a band difference quotient; IDAHIP_LINEAR_DENSE is
  * refused (-2: a random dense Jacobian has no band approximation worth factoring), and so are a ctx that is not a Krylov ctx and
  * widths out of range. With the mode on, idahip_krylov_solve and idahip_newton_iter_krylov run the preconditioned definition; for a
  * listed system without factors yet (no psetup, no upload) they are refused (-2, nothing launched). The four stand-alone calls below
@@ -181,7 +197,7 @@ int idahip_newton_iter_krylov(idahip_ctx* ctx, const double* hTn, const double* 
 int idahip_set_krylov_band_prec(idahip_ctx* ctx, int ml, int mu);
 /* 1 with the mode on (*ml, *mu set when non-null), 0 otherwise, -1 for a null ctx */
 int idahip_krylov_band_prec(const idahip_ctx* ctx, int* ml, int* mu);
-/* psetup for the listed systems: hTn, hCj, hHh, hInfo [nsys]. Heat: one device pass; host callbacks: the pack / host residual /
+/* psetup for the listed systems: hTn, hCj, hHh, hInfo [nsys]. Heat and Brusselator: one device pass; host callbacks: the pack / host residual /
  * scatter round trip of a band ctx, once per group. Returns 1 if some info != 0. */
 int idahip_krylov_psetup(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx,
                          int nsys);
@@ -242,7 +258,7 @@ int idahip_suppress_alg(const idahip_ctx* ctx);
 int idahip_set_constraints(idahip_ctx* ctx, const double* hC /* [n] or NULL = clear */);
 /* 1 if constraints are set (hC, when non-null, receives them), 0 if not, -1 for a null ctx */
 int idahip_constraints(const idahip_ctx* ctx, double* hC);
-/* per-system problem parameters, systems [first, first+count): LORENZ63 [count][3], HEAT1D [count][1] */
+/* per-system problem parameters, systems [first, first+count): LORENZ63 [count][3], HEAT1D [count][1], BRUSS1D [count][5] */
 int idahip_set_problem_params(idahip_ctx* ctx, int first, int count, const double* hParams, int nparam);
 /* LINEAR_DENSE data, systems [first, first+count): hA, hB [count][n*n] column-major, hC [count][n] */
 int idahip_set_linear_dense(idahip_ctx* ctx, int first, int count, const double* hA, const double* hB, const double* hC);
@@ -313,7 +329,7 @@ int idahip_nls_lsetup(idahip_ctx* ctx, const double* hTn, const double* hCj, int
  *          J(i,j) = (1/inc_j)*(rtemp_i - rr_i) for max(0, j-mu) <= i <= min(n-1, j+ml); every other band entry +0.0.
  * A dense DQ Jacobian costs n residual evaluations, a band one min(width, n); libidaens counts them in IDAENS_C_NRE_DQ (C IDA's
  * nreDQ), not in nre. The heat kernel writes, on a dense ctx, only rows j-1..j+1 of column j, as its analytic kernel does:
- * entries that the definition gives as -0.0 there are +0.0. Constraints flip inc's sign in C IDA; here a ctx with both constraints
+ * entries that the definition gives as -0.0 there are +0.0. The Brusselator kernel does the same with rows j-2..j+2. Constraints flip inc's sign in C IDA; here a ctx with both constraints
  * (idahip_set_constraints) and DQ Jacobians is refused by the steppers instead.
  * A DQ ctx refuses idahip_nls_lsetup and idahip_nls_sys_setup (-2: they carry no step sizes); idahip_nls_lsetup_dq is
  * idahip_nls_lsetup with them, and returns -2 on a ctx without DQ. */
@@ -465,7 +481,7 @@ typedef struct idahip_tiny_call {
 int idahip_tiny_solve(idahip_ctx* ctx, void* hSys, size_t sys_bytes, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc,
                       double* hYout, double* hYPout);
 int idahip_pow_batch(idahip_ctx* ctx, const double* hX, const double* hY, double* hOut, size_t count);
-/* The same call for larger systems (8 < n <= 4096, IDAHIP_LINEAR_DENSE or IDAHIP_HEAT1D, LU variant 4) as LOCK-STEP ROUNDS driven from the
+/* The same call for larger systems (8 < n <= 4096, IDAHIP_LINEAR_DENSE, IDAHIP_HEAT1D or IDAHIP_BRUSS1D, LU variant 4) as LOCK-STEP ROUNDS driven from the
  * device side: a round = one step attempt of every stepping system (Ida::step's attempt loop body, src/lib.rs:613-711, with
  * Newton::solve, crates/nonlinear/src/newton.rs:51-167, and the batched kernels of this library inside), the controller
  * state of every system and the index lists live on the device, the host only enqueues each round's fixed launch sequence:
@@ -484,7 +500,7 @@ int idahip_set_lu_variant(idahip_ctx* ctx, int variant);
 int idahip_lu_variant(const idahip_ctx* ctx); /* the variant in force */
 /* Matrices with more than 1024 rows: how a 64-column super-panel is factored. 1 = in one launch of the left-looking
  * workgroup-per-matrix kernel (lu_superpanel_kernel): the faster pipeline for BANDED matrices in dense storage (config 4's heat
- * Jacobians: 238 against 322 us per 4096 x 4096 matrix) and the default for IDAHIP_HEAT1D; 0 = eight 8-column panel launches with a
+ * Jacobians: 238 against 322 us per 4096 x 4096 matrix) and the default for IDAHIP_HEAT1D and IDAHIP_BRUSS1D; 0 = eight 8-column panel launches with a
  * narrow update after each, faster on DENSE matrices (they spread the update over several workgroups per matrix) and the default for
  * every other problem kind. A hint about structure, never about results: the factors are bit-identical either way. */
 int idahip_set_lu_superpanel(idahip_ctx* ctx, int on);

@@ -99,7 +99,7 @@ struct idahip_ctx {
     // n > 1024: 1 = a 64-column super-panel is ONE launch of lu_superpanel_kernel (left-looking; made for banded matrices in dense
     // storage, where it is 26 % faster: config 4), 0 = round 4's eight 8-column panel launches with a narrow update after each,
     // which spread a dense matrix's update over up to 8 workgroups and stay faster there (dense n = 1536 / 2048 / 4096: 6 / 11 / 48 %).
-    // Default by problem: on for IDAHIP_HEAT1D (tridiagonal content by construction), off otherwise; idahip_set_lu_superpanel
+    // Default by problem: on for IDAHIP_HEAT1D and IDAHIP_BRUSS1D (banded content by construction), off otherwise; idahip_set_lu_superpanel
     // or IDAHIP_LU_SUPERPANEL=0/1 (read at idahip_create) override. Bit-identical factors either way (tests run both).
     int lu_superpanel = 0;
     // device lock-step stepper: linear setups batched over rounds (round_lists_kernel): with k > 1 a round postpones its setups unless

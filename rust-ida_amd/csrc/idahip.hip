@@ -116,8 +116,12 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     if (!out) return -1;
     *out = nullptr;
     if (n < 1 || batch < 1) return -2;
-    if ((int)kind < 0 || (int)kind > (int)IDAHIP_HOST_CALLBACK) return -2;
+    if ((int)kind < 0 || (int)kind > (int)IDAHIP_BRUSS1D) return -2;
     if ((kind == IDAHIP_ROBERTS || kind == IDAHIP_LORENZ63) && n != 3) return -2;
+    if (kind == IDAHIP_BRUSS1D && (n % 2 != 0 || n < 10)) {
+        std::fprintf(stderr, "IDAHIP_BRUSS1D: n = %d is not 2 m with m >= 5 grid points (two interleaved species)\n", n);
+        return -2;
+    }
     idahip_ctx* c = new idahip_ctx();
     c->device = device; c->n = n; c->batch = batch; c->kind = kind;
     if (band) {
@@ -130,7 +134,7 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     const bool nomat = band || krylov_maxl > 0;  // no n x n storage
     c->npad16 = (n + 15) & ~15;
     c->list_seen.assign(((size_t)batch + 63) / 64, 0);
-    c->lu_superpanel = kind == IDAHIP_HEAT1D ? 1 : 0;
+    c->lu_superpanel = (kind == IDAHIP_HEAT1D || kind == IDAHIP_BRUSS1D) ? 1 : 0;  // banded content
     if (const char* sp = std::getenv("IDAHIP_LU_SUPERPANEL")) c->lu_superpanel = std::strtol(sp, nullptr, 10) != 0 ? 1 : 0;
     if (const char* sp = std::getenv("IDAHIP_LU_PERIOD")) {
         const int v = (int)std::strtol(sp, nullptr, 10);
@@ -182,6 +186,7 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     }
     if (kind == IDAHIP_LORENZ63) { c->nparam = 3; rc |= dalloc(c, &c->params, (size_t)batch * 3); }
     if (kind == IDAHIP_HEAT1D) { c->nparam = 1; rc |= dalloc(c, &c->params, (size_t)batch); }
+    if (kind == IDAHIP_BRUSS1D) { c->nparam = BRUSS_NPARAM; rc |= dalloc(c, &c->params, (size_t)batch * BRUSS_NPARAM); }
     if (kind == IDAHIP_HOST_CALLBACK) rc |= dalloc(c, &c->cb_stage, 3 * bn);
     c->slot_cap = (size_t)batch * 256 + 4096;  // per call: <= ~110 B of scalars per system (predict) + list ids + results
     for (int i = 0; i < NSLOT && !rc; ++i) {
@@ -228,16 +233,16 @@ int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem
 int idahip_create_band(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, int ml, int mu) {
     if (!out) return -1;
     *out = nullptr;
-    if (kind != IDAHIP_HEAT1D && kind != IDAHIP_HOST_CALLBACK) {
-        std::fprintf(stderr, "idahip_create_band: problem kind %d has no band form (IDAHIP_HEAT1D or IDAHIP_HOST_CALLBACK)\n", (int)kind);
+    if (kind != IDAHIP_HEAT1D && kind != IDAHIP_BRUSS1D && kind != IDAHIP_HOST_CALLBACK) {
+        std::fprintf(stderr, "idahip_create_band: problem kind %d has no band form (IDAHIP_HEAT1D, IDAHIP_BRUSS1D or IDAHIP_HOST_CALLBACK)\n", (int)kind);
         return -2;
     }
     if (n <= TINY_N || n > LU_BIG_MAX_N) {
         std::fprintf(stderr, "idahip_create_band: n = %d outside %d < n <= %d\n", n, TINY_N, LU_BIG_MAX_N);
         return -2;
     }
-    if (ml < 0 || mu < 0 || ml >= n || mu >= n || (kind == IDAHIP_HEAT1D && (ml < 1 || mu < 1))) {
-        std::fprintf(stderr, "idahip_create_band: bandwidths ml = %d, mu = %d outside 0 <= ml, mu < n (>= 1 for IDAHIP_HEAT1D)\n", ml, mu);
+    if (ml < 0 || mu < 0 || ml >= n || mu >= n || (kind == IDAHIP_HEAT1D && (ml < 1 || mu < 1)) || (kind == IDAHIP_BRUSS1D && (ml < 2 || mu < 2))) {
+        std::fprintf(stderr, "idahip_create_band: bandwidths ml = %d, mu = %d outside 0 <= ml, mu < n (>= 1 for IDAHIP_HEAT1D, >= 2 for IDAHIP_BRUSS1D)\n", ml, mu);
         return -2;
     }
     return create_ctx(out, device, n, batch, kind, hip_stream, true, ml, mu);
@@ -903,6 +908,9 @@ int launch_sys(idahip_ctx* c, const SysArgs& a, int nsys, double* jac_out, const
         case IDAHIP_HEAT1D:
             hipLaunchKernelGGL(heat_sys_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, a, (const double*)c->params);
             break;
+        case IDAHIP_BRUSS1D:
+            hipLaunchKernelGGL(bruss_sys_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, a, (const double*)c->params);
+            break;
     }
     return post_launch(c, "nls_sys");
 }
@@ -970,6 +978,14 @@ int callback_dq_jac(idahip_ctx* c, const DqArgs& d0, const double* hTn, const in
     return post_launch(c, "DQ jac (host callback)");
 }
 
+// the band DQ kernel of the ctx's device kind (a band ctx, or the band preconditioner of a Krylov ctx)
+void launch_band_dq(idahip_ctx* c, const DqArgs& d, int nsys) {
+    int chunks = 1;
+    while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
+    if (c->kind == IDAHIP_BRUSS1D) hipLaunchKernelGGL(bruss_band_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
+    else hipLaunchKernelGGL(heat_band_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
+}
+
 // DQ Jacobians of the listed systems at the ctx's yy, yp, ewt and savres: into `out` by system id (the work matrices or the band
 // storage) or, with `compact`, by list position. d_hh: the systems' step sizes, per list position.
 int launch_dq_jac(idahip_ctx* c, double* out, bool compact, const int* d_idx, const double* d_cj, const double* d_hh, int nsys,
@@ -982,10 +998,8 @@ int launch_dq_jac(idahip_ctx* c, double* out, bool compact, const int* d_idx, co
     d.out = out; d.compact = compact ? 1 : 0; d.n = n;
     d.ml = c->band ? c->ml : 0; d.mu = c->band ? c->mu : 0; d.ld = c->band ? c->ldab : 0;
     if (c->kind == IDAHIP_HOST_CALLBACK) return callback_dq_jac(c, d, hTn, hIdx, nsys);
-    if (c->band) {  // (idahip_create_band: IDAHIP_HEAT1D is the band ctx's only device kind)
-        int chunks = 1;
-        while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
-        hipLaunchKernelGGL(heat_band_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
+    if (c->band) {  // (idahip_create_band: IDAHIP_HEAT1D and IDAHIP_BRUSS1D are the band ctx's device kinds)
+        launch_band_dq(c, d, nsys);
         return post_launch(c, "band DQ jac");
     }
     switch (c->kind) {
@@ -1016,6 +1030,13 @@ int launch_dq_jac(idahip_ctx* c, double* out, bool compact, const int* d_idx, co
                                (!compact && out == c->jw) ? (const int*)c->lu_jwzero : nullptr);
             break;
         }
+        case IDAHIP_BRUSS1D: {
+            int chunks = 1;
+            while ((long)nsys * chunks < 2048 && chunks < n) chunks *= 2;
+            hipLaunchKernelGGL(bruss_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks,
+                               (!compact && out == c->jw) ? (const int*)c->lu_jwzero : nullptr);
+            break;
+        }
         default: return fail(c, -2, "no DQ Jacobian for problem kind %d", (int)c->kind);
     }
     return post_launch(c, "DQ jac");
@@ -1034,8 +1055,12 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
         if (c->kind == IDAHIP_HOST_CALLBACK) return callback_jac(c, c->bab, d_idx, hTn, hCj, hIdx, nsys);
         int chunks = 1;
         while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
-        hipLaunchKernelGGL(heat_band_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, c->bab, n, c->ml, c->mu, (const double*)c->params, d_idx,
-                           d_cj, chunks, d_skip);
+        if (c->kind == IDAHIP_BRUSS1D)
+            hipLaunchKernelGGL(bruss_band_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, c->bab, n, c->ml, c->mu, (const double*)c->yy,
+                               (const double*)c->params, d_idx, d_cj, chunks, d_skip);
+        else
+            hipLaunchKernelGGL(heat_band_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, c->bab, n, c->ml, c->mu, (const double*)c->params, d_idx,
+                               d_cj, chunks, d_skip);
         return post_launch(c, "band jac");
     }
     switch (c->kind) {
@@ -1061,6 +1086,13 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
             while ((long)nsys * chunks < 2048 && chunks < n) chunks *= 2;
             hipLaunchKernelGGL(heat_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->params, d_idx, d_cj, chunks, d_skip,
                                (work == c->jw) ? (const int*)c->lu_jwzero : nullptr);
+            break;
+        }
+        case IDAHIP_BRUSS1D: {
+            int chunks = 1;
+            while ((long)nsys * chunks < 2048 && chunks < n) chunks *= 2;
+            hipLaunchKernelGGL(bruss_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->yy, (const double*)c->params, d_idx,
+                               d_cj, chunks, d_skip, (work == c->jw) ? (const int*)c->lu_jwzero : nullptr);
             break;
         }
     }
@@ -1346,8 +1378,8 @@ int idahip_kind(const idahip_ctx* c) { return c ? (int)c->kind : -1; }
 int idahip_create_krylov(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, int maxl) {
     if (!out) return -1;
     *out = nullptr;
-    if (kind != IDAHIP_HEAT1D && kind != IDAHIP_LINEAR_DENSE && kind != IDAHIP_HOST_CALLBACK) {
-        std::fprintf(stderr, "idahip_create_krylov: problem kind %d (IDAHIP_HEAT1D, IDAHIP_LINEAR_DENSE or IDAHIP_HOST_CALLBACK)\n", (int)kind);
+    if (kind != IDAHIP_HEAT1D && kind != IDAHIP_BRUSS1D && kind != IDAHIP_LINEAR_DENSE && kind != IDAHIP_HOST_CALLBACK) {
+        std::fprintf(stderr, "idahip_create_krylov: problem kind %d (IDAHIP_HEAT1D, IDAHIP_BRUSS1D, IDAHIP_LINEAR_DENSE or IDAHIP_HOST_CALLBACK)\n", (int)kind);
         return -2;
     }
     if (n <= TINY_N || n > LU_BIG_MAX_N) {
@@ -1396,6 +1428,8 @@ int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* h
         const size_t shm = kry_lds_bytes(n, 3);
         if (c->kind == IDAHIP_HEAT1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, true>), grid, blk, shm, c->stream, a);
         else if (c->kind == IDAHIP_HEAT1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, false>), grid, blk, shm, c->stream, a);
+        else if (c->kind == IDAHIP_BRUSS1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_BRUSS1D, true>), grid, blk, shm, c->stream, a);
+        else if (c->kind == IDAHIP_BRUSS1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_BRUSS1D, false>), grid, blk, shm, c->stream, a);
         else if (c->kind == IDAHIP_LINEAR_DENSE) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_LINEAR_DENSE, false>), grid, blk, shm, c->stream, a);
         else return fail(c, -2, "no fused Krylov kernel for problem kind %d", (int)c->kind);
         return post_launch(c, "krylov_fused");
@@ -1434,6 +1468,8 @@ int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* h
             IDAHIP_HIP(c, hipMemcpyAsync(c->kry_stage, h, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
         } else if (c->kind == IDAHIP_HEAT1D) {
             hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_HEAT1D>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
+        } else if (c->kind == IDAHIP_BRUSS1D) {
+            hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_BRUSS1D>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
         } else {
             hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_LINEAR_DENSE>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
         }
@@ -1522,7 +1558,7 @@ int idahip_set_krylov_band_prec(idahip_ctx* c, int ml, int mu) {
     if (!c->krylov) return fail(c, -2, "idahip_set_krylov_band_prec on a dense ctx: not a Krylov ctx (idahip_create_krylov)");
     const bool off = ml == -1 && mu == -1;
     if (!off && c->kind == IDAHIP_LINEAR_DENSE)
-        return fail(c, -2, "idahip_set_krylov_band_prec: IDAHIP_LINEAR_DENSE has no band difference-quotient Jacobian (IDAHIP_HEAT1D or IDAHIP_HOST_CALLBACK)");
+        return fail(c, -2, "idahip_set_krylov_band_prec: IDAHIP_LINEAR_DENSE has no band difference-quotient Jacobian (IDAHIP_HEAT1D, IDAHIP_BRUSS1D or IDAHIP_HOST_CALLBACK)");
     if (!off && (ml < 0 || mu < 0 || ml >= c->n || mu >= c->n))
         return fail(c, -2, "idahip_set_krylov_band_prec: bandwidths ml = %d, mu = %d outside 0 <= ml, mu < n (-1, -1 turns the mode off)", ml, mu);
     IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
@@ -1579,10 +1615,8 @@ int idahip_krylov_psetup(idahip_ctx* c, const double* hTn, const double* hCj, co
         KTimer kt(c, IDAHIP_K_JAC, nsys);
         if (c->kind == IDAHIP_HOST_CALLBACK) {
             if ((rc = callback_dq_jac(c, d, hTn, hIdx, nsys))) return rc;
-        } else {  // (idahip_set_krylov_band_prec: IDAHIP_HEAT1D is the only device kind)
-            int chunks = 1;
-            while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
-            hipLaunchKernelGGL(heat_band_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
+        } else {  // (idahip_set_krylov_band_prec: IDAHIP_HEAT1D and IDAHIP_BRUSS1D are the device kinds)
+            launch_band_dq(c, d, nsys);
             if ((rc = post_launch(c, "band DQ jac (preconditioner)"))) return rc;
         }
     }
@@ -2072,6 +2106,11 @@ int launch_ic_sys(idahip_ctx* c, const SysArgsIC& a, int nsys, const double* hTn
             else hipLaunchKernelGGL(ic_heat_sys_kernel<1>, dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
             break;
         }
+        case IDAHIP_BRUSS1D: {  // (n is even)
+            const size_t shm = (a.lu ? 2 : 1) * sizeof(double) * n;
+            hipLaunchKernelGGL(ic_bruss_sys_kernel, dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
+            break;
+        }
     }
     return post_launch(c, "ic_res");
 }
@@ -2478,9 +2517,9 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     if (!hSys || !call || !hRoundsDone || !hAcc || !rounds_run || !call->touts || call->ntout < 1) return fail(c, -2, "null argument");
     if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
     const bool lin = c->kind == IDAHIP_LINEAR_DENSE && c->n <= LU_BIG_MAX_N;
-    const bool heat = c->kind == IDAHIP_HEAT1D && c->n <= LU_BIG_MAX_N;
-    if (c->n <= TINY_N || !(lin || heat) || c->lu_variant < 4)
-        return fail(c, -2, "the device-resident lock-step stepper takes linear dense and heat problems with %d < n <= %d (LU variant 4)", TINY_N, LU_BIG_MAX_N);
+    const bool banded = (c->kind == IDAHIP_HEAT1D || c->kind == IDAHIP_BRUSS1D) && c->n <= LU_BIG_MAX_N;
+    if (c->n <= TINY_N || !(lin || banded) || c->lu_variant < 4)
+        return fail(c, -2, "the device-resident lock-step stepper takes linear dense, heat and Brusselator problems with %d < n <= %d (LU variant 4)", TINY_N, LU_BIG_MAX_N);
     if (!c->h_constr.empty()) return fail(c, -2, "the device lock-step stepper does not check constraints: the host stepper does (DESIGN.md section 4g)");
     if (const int rcm = missing_id(c, "idahip_round_solve")) return rcm;
     if (call->recycle && (!c->ic_y || !c->ic_yp)) return fail(c, -2, "recycle needs idahip_snapshot_initial");

@@ -38,6 +38,7 @@
 #include "common.hpp"
 #include "solve_kernels.hpp"
 #include "band_kernels.hpp"
+#include "problem_kernels.hpp"
 
 namespace idahip {
 
@@ -65,7 +66,7 @@ struct KryArgs {
     double* nrm;        // [nsys] newton: sum_i (delta_i ewt_i)^2 left to right, 0 for a flag other than SUCCESS
     int* done;          // [nsys] split path: the loop of this system has ended
     int n, maxl;
-    const double* params;  // heat: [batch]
+    const double* params;  // heat: [batch]; Brusselator: [batch][5]
     const double *A, *Bm, *C;  // linear dense
     // band preconditioner (the kernels instantiated with PREC only): factors [batch][(2 pml + pmu + 1) * n], pivots [batch][n]
     const double* pab;
@@ -202,7 +203,8 @@ __device__ __forceinline__ void kry_point(const KryArgs& a, int b, const double*
     }
 }
 
-// row i of the residual at (y', yp'): heat_sys_kernel's expression / linear_sys_kernel's two chains over ascending columns
+// row i of the residual at (y', yp'): heat_sys_kernel's expression / linear_sys_kernel's two chains over ascending columns (the
+// Brusselator's row is bruss_row_perturbed itself)
 __device__ __forceinline__ double kry_res_heat(const double* y, const double* ypv, int n, int i, double coef) {
     if (i == 0 || i == n - 1) return y[i];
     return ypv[i] - coef * ((y[i - 1] - 2.0 * y[i]) + y[i + 1]);
@@ -238,6 +240,9 @@ __device__ __forceinline__ void kry_residual(const KryArgs& a, int b, const doub
     if constexpr (KIND == IDAHIP_HEAT1D) {
         const double coef = a.params[b];
         for (int i = threadIdx.x; i < n; i += KRY_T) put(i, kry_res_heat(y, ypv, n, i, coef));
+    } else if constexpr (KIND == IDAHIP_BRUSS1D) {
+        const double* __restrict__ prm = a.params + (long)b * BRUSS_NPARAM;
+        for (int i = threadIdx.x; i < n; i += KRY_T) put(i, bruss_row_perturbed(n, i, ypv[i], prm, [&](int k) { return y[k]; }));
     } else {
         const double* __restrict__ Ab = a.A + (long)b * n * n;
         const double* __restrict__ Bb = a.Bm + (long)b * n * n;
@@ -342,7 +347,7 @@ __device__ __forceinline__ void kry_lds(double* sm, idakry::Sys** k, double** pa
 }
 
 // ---------------------------------------------------------------------------------------------- fused path
-// The whole solve of one listed system in one launch (IDAHIP_HEAT1D, IDAHIP_LINEAR_DENSE). Dynamic LDS: the state and the partials,
+// The whole solve of one listed system in one launch (IDAHIP_HEAT1D, IDAHIP_BRUSS1D, IDAHIP_LINEAR_DENSE). Dynamic LDS: the state and the partials,
 // then 3 n doubles (products, y', yp'); the basis lives in a.V and stays in L2.
 template <int KIND, bool PREC>
 __global__ __launch_bounds__(KRY_T) void krylov_fused_kernel(KryArgs a) {

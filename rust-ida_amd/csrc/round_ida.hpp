@@ -1,4 +1,4 @@
-// Device-resident LOCK-STEP stepper for larger systems (8 < n <= 1024 linear dense, n <= 4096 heat; device residual): a round = one step attempt of every
+// Device-resident LOCK-STEP stepper for larger systems (8 < n <= 1024 linear dense, n <= 4096 heat and Brusselator; device residual): a round = one step attempt of every
 // system that is stepping, as in host/ensemble_ida.cpp -- but the scalar controller of every system lives on the device, the
 // index lists are built there, and the host only enqueues the round's fixed sequence of launches. No host round trip inside a
 // round; in throughput mode (idaens_stream, a fixed number of rounds) none at all between rounds.

@@ -773,7 +773,7 @@ int device_ctl_applies(const idaens* e, const SolveCall& C) {
     if (e->nrtfn != 0 && (e->rt_fn != nullptr || e->nrtfn > IDAHIP_MAX_ROOTS || C.recycle)) return 0;
     if (e->n <= 8 && (k == IDAHIP_ROBERTS || k == IDAHIP_LORENZ63)) return 1;
     if (idahip_constraints(e->ctx, nullptr) == 1) return 0;  // the lock-step device rounds have no constraint check
-    if (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D) && idahip_lu_variant(e->ctx) >= 4) return 2;
+    if (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D || k == IDAHIP_BRUSS1D) && idahip_lu_variant(e->ctx) >= 4) return 2;
     return 0;
 }
 

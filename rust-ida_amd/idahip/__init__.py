@@ -18,8 +18,9 @@ dp = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
 i64p = C.POINTER(C.c_int64)
 
-ROBERTS, LORENZ63, LINEAR_DENSE, HEAT1D, HOST_CALLBACK = 0, 1, 2, 3, 4
-KIND = {"roberts": ROBERTS, "lorenz63": LORENZ63, "linear_dense": LINEAR_DENSE, "heat1d": HEAT1D, "host_callback": HOST_CALLBACK}
+ROBERTS, LORENZ63, LINEAR_DENSE, HEAT1D, HOST_CALLBACK, BRUSS1D = 0, 1, 2, 3, 4, 5
+KIND = {"roberts": ROBERTS, "lorenz63": LORENZ63, "linear_dense": LINEAR_DENSE, "heat1d": HEAT1D, "host_callback": HOST_CALLBACK,
+        "bruss1d": BRUSS1D}
 RES_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
 JAC_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                      C.POINTER(C.c_double), C.c_void_p)
@@ -759,7 +760,7 @@ class Ctx:
         return out
 
     def set_lu_superpanel(self, on):
-        """n > 1024: a super-panel in one launch (banded matrices; default for heat1d) or panel by panel (dense matrices)."""
+        """n > 1024: a super-panel in one launch (banded matrices; default for heat1d and bruss1d) or panel by panel (dense matrices)."""
         self._chk(self.H.idahip_set_lu_superpanel(self.h, int(on)), "set_lu_superpanel")
 
     def lu_superpanel(self):

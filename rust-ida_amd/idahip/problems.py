@@ -276,15 +276,52 @@ def heat1d(n=4096, batch=256):
             "atol": np.array([1.0e-8]), "touts": 0.01 * np.arange(1, 11)}
 
 
+def bruss1d_rhs(prm, y):
+    """The interior right-hand side of the Brusselator in the residual's operation order (include/ida_hip.h), 0 at the end points.
+    prm = [a, b, d, ub, vb]; y [2m] interleaved."""
+    a, b, d = (float(v) for v in prm[:3])
+    u, v = y[0::2], y[1::2]
+    f = np.zeros_like(y)
+    ui, vi = u[1:-1], v[1:-1]
+    w = (ui * ui) * vi
+    lu = (u[:-2] - 2.0 * ui) + u[2:]
+    lv = (v[:-2] - 2.0 * vi) + v[2:]
+    f[2:-2:2] = ((a - (b + 1.0) * ui) + w) + d * lu
+    f[3:-2:2] = (b * ui - w) + d * lv
+    return f
+
+
+def bruss1d(m=2048, batch=256, alpha=0.02):
+    """1-D Brusselator u_t = a - (b + 1) u + u^2 v + alpha u_xx, v_t = b u - u^2 v + alpha v_xx, method of lines on m nodes, two
+    species interleaved (n = 2m), Dirichlet ends (ub, vb) as algebraic equations. System s: a = 1 + s/64, b = 3 + s/32,
+    d = alpha (m-1)^2, ub = a, vb = b/a; u_i(0) = ub + 0.1 sin(pi x_i), v_i(0) = vb + 0.1 sin(pi x_i) with the end values exactly
+    ub, vb; y'(0) = the interior right-hand side. Nonlinear, stiff, bandwidths (2, 2)."""
+    n = 2 * m
+    x = np.arange(m) / (m - 1)
+    s = np.arange(batch)
+    a, b = 1.0 + s / 64.0, 3.0 + s / 32.0
+    d = np.full(batch, alpha * float(m - 1) ** 2)
+    ub, vb = a, b / a
+    params = np.stack([a, b, d, ub, vb], axis=1)
+    bump = 0.1 * np.sin(np.pi * x)
+    y0 = np.empty((batch, n))
+    y0[:, 0::2] = ub[:, None] + bump[None, :]
+    y0[:, 1::2] = vb[:, None] + bump[None, :]
+    y0[:, 0], y0[:, 1], y0[:, n - 2], y0[:, n - 1] = ub, vb, ub, vb
+    yp0 = np.stack([bruss1d_rhs(params[k], y0[k]) for k in range(batch)])
+    return {"kind": "bruss1d", "n": n, "yy0": y0, "yp0": yp0, "params": params, "rtol": 1.0e-6, "atol": np.array([1.0e-8]),
+            "touts": 0.25 * np.arange(1, 5)}
+
+
 def make_ctx(prob, device=0, stream=None, band=False, krylov=None):
     """Create a device context for a generated problem and load its data (import kept local: this module is also
-    used by CPU-only tests). band=True: a band ctx -- (1, 1) for heat1d, prob["band"] for a host-callback problem with a band
+    used by CPU-only tests). band=True: a band ctx -- (1, 1) for heat1d, (2, 2) for bruss1d, prob["band"] for a host-callback problem with a band
     Jacobian prob["bjac"]; a (ml, mu) pair is taken as given. krylov=maxl: a Krylov ctx (matrix-free SPGMR; 0 = the default maxl);
     a host-callback problem then registers its residual alone."""
     from . import Ctx
     batch = prob["yy0"].shape[0]
     if band is True:
-        band = (1, 1) if prob["kind"] == "heat1d" else tuple(prob["band"])
+        band = {"heat1d": (1, 1), "bruss1d": (2, 2)}.get(prob["kind"]) or tuple(prob["band"])
     ctx = Ctx(prob["kind"], prob["n"], batch, device=device, stream=stream, band=band or None, krylov=krylov)
     ctx.set_tolerances(prob["rtol"], prob["atol"])
     if prob["kind"] == "host_callback" and krylov is not None:
