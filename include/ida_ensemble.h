@@ -65,7 +65,9 @@ int idaens_set_max_ord(idaens* e, int maxord);          /* 1..5, default 5 */
  * identical either way; the switch exists for measurements. */
 int idaens_set_fused_newton(idaens* e, int on);
 /* on (default): the step-size and order controller runs on the device where a device stepper exists
- * (IDA_NORMAL, no root functions, no trace):
+ * (IDA_NORMAL, no trace, not a Krylov ctx; root functions only of idaens_set_roots' family and at most IDAHIP_MAX_ROOTS = 4 of
+ * them, and not in idaens_stream -- with more functions, or with a user callback (idaens_set_root_fn), the host stepper runs and
+ * idaens_device_controller_active reports 0; the results are the same):
  *   - small systems (n <= 8: Roberts, Lorenz63): a solve / solve_schedule / stream call is ONE launch in which every system
  *     runs its own time loop (idahip_tiny_solve);
  *   - linear dense, heat and Brusselator problems with 8 < n <= 4096: lock-step rounds as below, but enqueued without a host round trip

@@ -39,14 +39,13 @@ def oracle_cxxflags():
     raise RuntimeError("oracle/Makefile has no CXXFLAGS line")
 
 
-def lib():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    d = tempfile.mkdtemp(prefix="tstop_oracle_")
+def compile_lib(source, prefix):
+    """tests/native/<source> as a shared library in a temporary directory, with the oracle's flags; the entry points it has from
+    oracle/capi.cpp and tests/native/tstop_oracle.cpp declared."""
+    d = tempfile.mkdtemp(prefix=prefix + "_")
     atexit.register(shutil.rmtree, d, True)
-    so = os.path.join(d, "libtstop_oracle.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + oracle_cxxflags() + ["-shared", "-o", so, os.path.join(ROOT, "tests", "native", "tstop_oracle.cpp")])
+    so = os.path.join(d, "lib%s.so" % prefix)
+    subprocess.check_call([os.environ.get("CXX", "g++")] + oracle_cxxflags() + ["-shared", "-o", so, os.path.join(ROOT, "tests", "native", source)])
     L = C.CDLL(so)
     dp = O.dp
     L.oracle_ida_create.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, C.c_double, dp, C.c_int]
@@ -69,8 +68,14 @@ def lib():
     L.tstop_oracle_set_tstop.argtypes = [C.c_void_p, C.c_int, C.c_double]
     L.tstop_oracle_set_tstop.restype = None
     L.tstop_oracle_has_tstop.argtypes = [C.c_void_p, dp]
-    _LIB = L
     return L
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        _LIB = compile_lib("tstop_oracle.cpp", "tstop_oracle")
+    return _LIB
 
 
 class Harness(O.OracleIda):
@@ -79,17 +84,14 @@ class Harness(O.OracleIda):
     def __init__(self, prob, s, id=None, suppress=False, mxstep=None):
         kw = {k.lower() if k == "params" else k: prob[k][s] for k in ("params", "A", "B", "c") if k in prob}
         O.OracleIda.__init__(self, prob["kind"], prob["n"], prob["yy0"][s], prob["yp0"][s], prob["rtol"], prob["atol"], **kw)
-        real, mine = self.L, lib()  # the object was created by oracle_lib's library: make it anew in this one
+        real, mine = self.L, self._lib()  # the object was created by oracle_lib's library: make it anew in this one
         real.oracle_ida_destroy(self.h)
         self.L = mine
-        yy0_, yp0_, atol_, p_, A_, B_, c_ = self._keep
-        ptr = O._ptr
-        self.h = mine.oracle_ida_create(O.KIND[prob["kind"]], prob["n"], ptr(p_), ptr(A_), ptr(B_), ptr(c_), ptr(yy0_), ptr(yp0_),
-                                        float(prob["rtol"]), ptr(atol_), atol_.size)
+        self.h = self._create(prob)
         self.t0 = self.get("tn")
         if id is not None:
             a = O.f64(id)
-            assert mine.tstop_oracle_set_id(self.h, ptr(a), a.size) == 0
+            assert mine.tstop_oracle_set_id(self.h, O._ptr(a), a.size) == 0
         if suppress:
             self.set("suppressalg", 1.0)
         if mxstep is not None:
@@ -97,6 +99,15 @@ class Harness(O.OracleIda):
         mine.oracle_ida_record_steps(self.h, 1)
         self.dead = None      # (status, tret) once a status is sticky
         self.calls = []       # census: one dict per solve call
+
+    def _lib(self):
+        return lib()
+
+    def _create(self, prob):
+        yy0_, yp0_, atol_, p_, A_, B_, c_ = self._keep
+        ptr = O._ptr
+        return self.L.oracle_ida_create(O.KIND[prob["kind"]], prob["n"], ptr(p_), ptr(A_), ptr(B_), ptr(c_), ptr(yy0_), ptr(yp0_),
+                                        float(prob["rtol"]), ptr(atol_), atol_.size)
 
     def set_stop_time(self, t):
         if t is None or t != t:
@@ -163,11 +174,11 @@ BRANCHES = {"first_clip", "first_ill_input", "clip_stop_test1", "clip_stop_test2
             "tstop_stop_test1_one_step", "tstop_stop_test2_one_step", "tstop_eq_tout"}
 
 
-def run_ops(prob, ops, ids=None, **how):
-    """The ops on one Harness per system of ids (default: all). -> (records, harnesses): records[k] = per solve op a dict of
-    arrays over the systems (status, tret, yy, yp, the SCALARS and tstop)."""
+def run_ops(prob, ops, ids=None, harness=None, **how):
+    """The ops on one Harness (or the subclass `harness`) per system of ids (default: all). -> (records, harnesses): records[k] = per
+    solve op a dict of arrays over the systems (status, tret, yy, yp, the SCALARS, tstop and whatever else the harness' state() has)."""
     ids = list(range(prob["yy0"].shape[0])) if ids is None else list(ids)
-    hs = [Harness(prob, s, **how) for s in ids]
+    hs = [(harness or Harness)(prob, s, **how) for s in ids]
     rec = []
     for op in ops:
         if op[0] == "stop":
