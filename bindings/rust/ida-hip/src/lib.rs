@@ -250,6 +250,19 @@ impl Ctx {
         unsafe { sys::idahip_krylov_fused(self.raw) == 1 }
     }
 
+    /// Krylov context of a device kind: step on the device lock-step rounds instead of the host stepper (off by default).
+    pub fn set_krylov_rounds(&mut self, on: bool) -> Result<(), Error> {
+        let rc = unsafe { sys::idahip_set_krylov_rounds(self.raw, on as c_int) };
+        if rc != 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(())
+    }
+
+    pub fn krylov_rounds(&self) -> bool {
+        unsafe { sys::idahip_krylov_rounds(self.raw) == 1 }
+    }
+
     /// Krylov context: the band preconditioner of DESIGN.md section 4i with half-bandwidths (ml, mu); `None` turns it off.
     pub fn set_krylov_band_prec(&mut self, widths: Option<(usize, usize)>) -> Result<(), Error> {
         let (ml, mu) = widths.map_or((-1, -1), |(l, u)| (l as c_int, u as c_int));

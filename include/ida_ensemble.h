@@ -65,7 +65,7 @@ int idaens_set_max_ord(idaens* e, int maxord);          /* 1..5, default 5 */
  * identical either way; the switch exists for measurements. */
 int idaens_set_fused_newton(idaens* e, int on);
 /* on (default): the step-size and order controller runs on the device where a device stepper exists
- * (IDA_NORMAL, no trace, not a Krylov ctx; root functions only of idaens_set_roots' family and at most IDAHIP_MAX_ROOTS = 4 of
+ * (IDA_NORMAL, no trace, not a Krylov ctx unless idahip_set_krylov_rounds is on; root functions only of idaens_set_roots' family and at most IDAHIP_MAX_ROOTS = 4 of
  * them, and not in idaens_stream -- with more functions, or with a user callback (idaens_set_root_fn), the host stepper runs and
  * idaens_device_controller_active reports 0; the results are the same):
  *   - small systems (n <= 8: Roberts, Lorenz63): a solve / solve_schedule / stream call is ONE launch in which every system
@@ -124,12 +124,18 @@ int idaens_set_root_fn(idaens* e, int nroots, idaens_root_fn fn, void* user);
  *     any flag other than SUCCESS adds 1 to IDAENS_C_NCFL and is recoverable: the attempt takes Newton's ConvergenceRecover exit
  *     (a retry with a setup when the setup's data were stale, else a convergence failure of the step, counted in ncfn);
  *   - the fused first two Newton iterations are off (idaens_set_fused_newton changes nothing), idaens_device_controller_active reports 0:
- *     the host stepper runs; idaens_calc_ic is refused (negative return with a text);
+ *     the host stepper runs unless idahip_set_krylov_rounds is on (below); idaens_calc_ic is refused (negative return with a text);
  *   - solve, schedules, streams, groups, both tasks and root finding never touch the linear solver and work unchanged.
  * With the band preconditioner on (idahip_set_krylov_band_prec) the linear setup is real again: the systems that
  * ask for one get, after their residual, one idahip_krylov_psetup call with their tn, cj and hh. Per such system: the bookkeeping
  * above (nje stays), IDAENS_C_NPE += 1, IDAENS_C_NRE_DQ += min(ml+mu+1, n), and a zero pivot in P is a recoverable setup failure
- * exactly as on a dense ctx (IDAENS_C_NLUFAIL counts it there). Every Newton iteration adds 1 + nli to IDAENS_C_NPS. */
+ * exactly as on a dense ctx (IDAENS_C_NLUFAIL counts it there). Every Newton iteration adds 1 + nli to IDAENS_C_NPS.
+ * With idahip_set_krylov_rounds(ctx, 1) (off by default; read at the start of every solve call, so it may be changed between
+ * round-limited calls) a Krylov ctx of a device kind with 8 < n <= 4096 steps on the device lock-step rounds wherever a dense ctx would
+ * (idaens_device_controller_active reports 2; idaens_set_device_controller(e, 0) still forces the host stepper): one synchronisation
+ * per round, none in idaens_stream. Every system performs the operations above in the same order with the same arithmetic, so its
+ * results and all counters (IDAENS_C_NPE / _NPS / _NLI / _NCFL / _NRE_DQ included) are the host stepper's; a Newton solve that starts
+ * over with a setup does so in the next round, so a call may take more rounds. idaens_calc_ic and constraints stay refused. */
 
 /* Stop time: C IDA's IDASetStopTime. The reference's Ida::solve has every stop test (ida_tstop: Option<f64>, src/impl_solve.rs:137-150,
  * src/impl_stop_test.rs:36-211, src/lib.rs:640-644) and no setter; this is the setter. Every system is its own `Ida` object, so every

@@ -151,7 +151,7 @@ int idahip_ls_solve_band(idahip_ctx* ctx, int ml, int mu, const double* dAB, con
  * On a Krylov ctx idahip_ls_type is IDAHIP_LS_ITERATIVE, idahip_ls_num_iters the sum and idahip_ls_res_norm the maximum over the
  * listed systems of the last solve call. Refused with -2: idahip_ls_setup (no dense work matrices), idahip_nls_lsetup*, idahip_nls_sys_setup, idahip_newton_iter,
  * idahip_newton_iter2, idahip_download_lu*, idahip_set_jacobian_dq(1), idahip_set_constraints, idahip_set_host_problem,
- * idahip_ic_*, idahip_round_solve. */
+ * idahip_ic_*, idahip_round_solve (unless idahip_set_krylov_rounds is on, below). */
 int idahip_create_krylov(idahip_ctx** ctx, int device, int n, int batch, idahip_problem kind, void* hip_stream, int maxl);
 /* 1 for a Krylov ctx (*maxl set when non-null), 0 otherwise, -1 for a null ctx */
 int idahip_krylov(const idahip_ctx* ctx, int* maxl);
@@ -167,6 +167,24 @@ int idahip_krylov_solve(idahip_ctx* ctx, const double* hTn, const double* hCj, c
  * Returns 1 if some flag is not SUCCESS (recoverable: Newton's ConvergenceRecover exit). */
 int idahip_newton_iter_krylov(idahip_ctx* ctx, const double* hTn, const double* hCj, const double* hEpsNewt, double* hDelnrm,
                               int32_t* hNli, int32_t* hFlag, const int32_t* hIdx, int nsys);
+/* The device LOCK-STEP ROUNDS on a Krylov ctx (idahip_round_solve below; DESIGN.md section 4h/4i, addendum). Off by default: with the
+ * switch off idahip_round_solve refuses a Krylov ctx (-2) and libidaens steps it on the host stepper. With it on, idahip_round_solve
+ * takes IDAHIP_HEAT1D and IDAHIP_BRUSS1D (with or without the band preconditioner) and IDAHIP_LINEAR_DENSE (without), 8 < n <= 4096,
+ * whatever the LU variant: a round is the sequence of the dense and band contexts with the linear algebra replaced -- the residual for
+ * every system whose Newton solve starts, the preconditioner's band DQ Jacobian and factorisation for the listed systems that ask
+ * for a setup, and four passes of the one-launch solve (idahip_set_krylov_fused is ignored) with the tolerance
+ * (sqrt(n)*0.05)*eps_newt formed on the device from the system's record. Per system the operations, their order and the counters are
+ * the host stepper's; idahip_set_lu_period is treated as 1. idahip_ls_num_iters / idahip_ls_res_norm are left as they were.
+ * idahip_set_krylov_rounds returns -2 (and changes nothing) on a ctx that is not a Krylov ctx, on IDAHIP_HOST_CALLBACK (a host residual
+ * cannot run inside a round) and for on != 0 with n <= 8. May be changed between solve calls.
+ * idahip_krylov_rounds: 1 on, 0 off, -1 for a null ctx. */
+int idahip_set_krylov_rounds(idahip_ctx* ctx, int on);
+int idahip_krylov_rounds(const idahip_ctx* ctx);
+/* npe / nps (preconditioner setups and solves per system, C IDA's counters) are not part of the controller record that
+ * idahip_round_solve moves: the caller hands the systems' current values to the ctx before the call and reads them back after it,
+ * host arrays [batch]. A system that idaens_stream's restarts create anew inside the call starts again from 0. */
+int idahip_krylov_rounds_put_counters(idahip_ctx* ctx, const int64_t* hNpe, const int64_t* hNps);
+int idahip_krylov_rounds_get_counters(const idahip_ctx* ctx, int64_t* hNpe, int64_t* hNps);
 /* ---- The BAND PRECONDITIONER of a Krylov ctx: left-preconditioned SPGMR (C IDA's IDABBDPRE with one block and left preconditioning
  * in SPGMR; neither the reference nor a SUNDIALS copy is at hand: this text and DESIGN.md section 4i are the definition). Off by
  * default; with it off nothing of the ctx changes.
@@ -486,7 +504,8 @@ int idahip_pow_batch(idahip_ctx* ctx, const double* hX, const double* hY, double
  * Newton::solve, crates/nonlinear/src/newton.rs:51-167, and the batched kernels of this library inside), the controller
  * state of every system and the index lists live on the device, the host only enqueues each round's fixed launch sequence:
  * one synchronisation per round (to learn whether any system still steps), none at all when `recycle` is set (throughput
- * mode runs exactly max_rounds rounds). Arguments as idahip_tiny_solve; rounds_run: rounds executed by this call. */
+ * mode runs exactly max_rounds rounds). Arguments as idahip_tiny_solve; rounds_run: rounds executed by this call.
+ * A Krylov ctx is refused (-2) unless idahip_set_krylov_rounds is on (above). */
 int idahip_round_solve(idahip_ctx* ctx, void* hSys, size_t sys_bytes, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc,
                        double* hYout, double* hYPout, int64_t* rounds_run);
 

@@ -93,6 +93,12 @@ struct idahip_ctx {
     std::vector<uint8_t> kry_pready; // [batch] a psetup or an upload has given this system its factors
     int kry_last_nli = 0;            // sum of the iterations / maximum of the residual norms over the last solve call's list
     double kry_last_resnorm = 0.0;
+    // device lock-step rounds on a Krylov ctx (idahip_set_krylov_rounds, round_ida.hpp): off by default
+    int kry_rounds = 0;
+    int64_t* kry_rcnt = nullptr;     // [3][batch] npe, nps, ready flags of the running call (lazy)
+    int32_t* kry_rint = nullptr;     // [2][batch] nli, flag of the pass's solve (lazy)
+    double* kry_rres = nullptr;      // [batch] res_norm of the pass's solve (lazy)
+    std::vector<int64_t> kry_h_npe, kry_h_nps;  // [batch] the systems' npe / nps around idahip_round_solve (idahip_krylov_rounds_put/get_counters)
     double *ic_y = nullptr, *ic_yp = nullptr;  // [batch][n] initial conditions kept for idahip_restore_initial (lazy)
     double* dky = nullptr;                     // [batch][n] result buffer of idahip_get_dky (lazy)
     int lu_variant = 4;  // 4: one wave per matrix factors each 64-column super-panel (lu_wavepanel.hpp, default)

@@ -261,7 +261,7 @@ int idahip_destroy(idahip_ctx* c) {
     DevGuard dev_guard__(c);
     if (!c) return 0;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* ptrs[] = {c->kry_pab, c->kry_ppiv, c->kry_V, c->kry_st, c->kry_stage, c->kry_b, c->kry_x, c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
+    void* ptrs[] = {c->kry_rcnt, c->kry_rint, c->kry_rres, c->kry_pab, c->kry_ppiv, c->kry_V, c->kry_st, c->kry_stage, c->kry_b, c->kry_x, c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
                     c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->d_constr, c->ic_y,
                     c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d};
@@ -1410,6 +1410,35 @@ int idahip_set_krylov_fused(idahip_ctx* c, int on) {
 
 int idahip_krylov_fused(const idahip_ctx* c) { return c ? (c->krylov ? c->kry_fused : 0) : -1; }
 
+int idahip_set_krylov_rounds(idahip_ctx* c, int on) {
+    if (!c) return -1;
+    if (!c->krylov) return fail(c, -2, "idahip_set_krylov_rounds: not a Krylov ctx (idahip_create_krylov)");
+    if (c->kind == IDAHIP_HOST_CALLBACK) return fail(c, -2, "idahip_set_krylov_rounds: a host-callback residual cannot run inside a device round");
+    if (on && c->n <= TINY_N) return fail(c, -2, "idahip_set_krylov_rounds: n = %d outside %d < n <= %d", c->n, TINY_N, LU_BIG_MAX_N);
+    c->kry_rounds = on ? 1 : 0;
+    return 0;
+}
+
+int idahip_krylov_rounds(const idahip_ctx* c) { return c ? (c->krylov ? c->kry_rounds : 0) : -1; }
+
+int idahip_krylov_rounds_put_counters(idahip_ctx* c, const int64_t* hNpe, const int64_t* hNps) {
+    if (!c) return -1;
+    if (!c->krylov) return fail(c, -2, "idahip_krylov_rounds_put_counters: not a Krylov ctx (idahip_create_krylov)");
+    if (!hNpe || !hNps) return fail(c, -2, "null argument");
+    c->kry_h_npe.assign(hNpe, hNpe + c->batch);
+    c->kry_h_nps.assign(hNps, hNps + c->batch);
+    return 0;
+}
+
+int idahip_krylov_rounds_get_counters(const idahip_ctx* c, int64_t* hNpe, int64_t* hNps) {
+    if (!c || !hNpe || !hNps) return -1;
+    for (int b = 0; b < c->batch; ++b) {
+        hNpe[b] = (size_t)b < c->kry_h_npe.size() ? c->kry_h_npe[b] : 0;
+        hNps[b] = (size_t)b < c->kry_h_nps.size() ? c->kry_h_nps[b] : 0;
+    }
+    return 0;
+}
+
 namespace {
 
 // the solve of the listed systems, fused or split; a.idx / cj / tol / results point into `ap`'s slot, already uploaded
@@ -2509,16 +2538,85 @@ static int stepper_buffers(idahip_ctx* c, const idahip_tiny_call* call, bool out
     return 0;
 }
 
+// The Newton solve of one round on a Krylov ctx (round_ida.hpp, idahip_set_krylov_rounds): the residuals, the band preconditioner's
+// setup on the device-built list, and four passes of { SPGMR ; control ; residual }, booked under the classes of the host stepper's
+// calls. Always the one-launch solve (idahip_set_krylov_fused is ignored: the two paths are bit-identical).
+static int krylov_round_newton(idahip_ctx* c, const RoundArgs& a, const KryRoundArgs& kr, SysArgs& sa) {
+    const int batch = c->batch, n = c->n;
+    const dim3 per_sys((batch + 255) / 256), blk(256);
+    int rc;
+    {   // sys(y0), y <- y0 = 0: every system whose Newton solve starts in this round, those without a setup ...
+        KTimer kt(c, IDAHIP_K_SYS, 0);
+        sa.reset_ee = 1; sa.skip = a.skipP;
+        if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+    }
+    {   // ... and those with one (no Jacobian is formed: nje stays)
+        KTimer kt(c, IDAHIP_K_SYS, 0);
+        sa.skip = a.skipL;
+        if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+    }
+    if (c->kry_prec) {  // psetup of the listed systems at the residual sys has just left: P, then its factors
+        {
+            KTimer kt(c, IDAHIP_K_JAC, 0);
+            hipLaunchKernelGGL(dq_round_prep_kernel, per_sys, blk, 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh, batch,
+                               (long)std::min(c->kry_pml + c->kry_pmu + 1, n));
+            DqArgs d;
+            d.yy = c->yy; d.yp = c->yp; d.ewt = c->ewt; d.rr = c->savres;
+            d.idx = a.ident; d.cj = a.cj; d.hh = c->dq_hh; d.skip = a.skipL;
+            d.out = c->kry_pab; d.compact = 0; d.n = n;
+            d.ml = c->kry_pml; d.mu = c->kry_pmu; d.ld = c->kry_pldab;
+            launch_band_dq(c, d, batch);
+            if ((rc = post_launch(c, "band DQ jac (preconditioner)"))) return rc;
+        }
+        KTimer kt(c, IDAHIP_K_LU, 0);
+        if ((rc = band_factor(c, c->kry_pab, (long)c->kry_pldab * n, c->kry_ppiv, n, c->kry_pml, c->kry_pmu, a.lu_list, batch, a.lu_cnt))) return rc;
+    }
+    hipLaunchKernelGGL(round_krylov_ctl_kernel, per_sys, blk, 0, c->stream, a, kr, 0);
+    KryArgs ka{};
+    ka.yy = c->yy; ka.yp = c->yp; ka.ewt = c->ewt; ka.rr = c->savres;
+    ka.V = c->kry_V; ka.st = (idakry::Sys*)c->kry_st; ka.stage = c->kry_stage;
+    ka.idx = a.ident; ka.cj = a.cj; ka.tol = kr.tol; ka.skip = a.skipI;
+    ka.newton = 1; ka.delta = c->delta; ka.ee = c->ee;
+    ka.nli = c->kry_rint; ka.flag = c->kry_rint + batch; ka.resnorm = c->kry_rres; ka.nrm = a.nrm_out;
+    ka.n = n; ka.maxl = c->kry_maxl;
+    ka.params = c->params; ka.A = c->A; ka.Bm = c->B; ka.C = c->C;
+    ka.pab = c->kry_pab; ka.ppiv = (const long long*)c->kry_ppiv; ka.pml = c->kry_pml; ka.pmu = c->kry_pmu;
+    const bool prec = c->kry_prec != 0;
+    const size_t shm = kry_lds_bytes(n, 3);
+    for (int m = 1; m <= idactl::MAXNLSIT; ++m) {
+        {
+            KTimer kt(c, IDAHIP_K_NEWTON_ITER, 0);
+            const dim3 grid(batch), kblk(KRY_T);
+            if (c->kind == IDAHIP_HEAT1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, true, true>), grid, kblk, shm, c->stream, ka);
+            else if (c->kind == IDAHIP_HEAT1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, false, true>), grid, kblk, shm, c->stream, ka);
+            else if (c->kind == IDAHIP_BRUSS1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_BRUSS1D, true, true>), grid, kblk, shm, c->stream, ka);
+            else if (c->kind == IDAHIP_BRUSS1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_BRUSS1D, false, true>), grid, kblk, shm, c->stream, ka);
+            else hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_LINEAR_DENSE, false, true>), grid, kblk, shm, c->stream, ka);
+            if ((rc = post_launch(c, "krylov_fused (round)"))) return rc;
+        }
+        hipLaunchKernelGGL(round_krylov_ctl_kernel, per_sys, blk, 0, c->stream, a, kr, m);
+        if (m < idactl::MAXNLSIT) {
+            KTimer kt(c, IDAHIP_K_SYS, 0);
+            sa.reset_ee = 0; sa.skip = a.skipS;
+            if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+        }
+    }
+    return 0;
+}
+
 int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc,
                        double* hYout, double* hYPout, int64_t* rounds_run) {
-    if (c && c->krylov) return fail(c, -2, "idahip_round_solve on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
+    if (c && c->krylov && !c->kry_rounds) return fail(c, -2, "idahip_round_solve on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (!hSys || !call || !hRoundsDone || !hAcc || !rounds_run || !call->touts || call->ntout < 1) return fail(c, -2, "null argument");
     if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
     const bool lin = c->kind == IDAHIP_LINEAR_DENSE && c->n <= LU_BIG_MAX_N;
     const bool banded = (c->kind == IDAHIP_HEAT1D || c->kind == IDAHIP_BRUSS1D) && c->n <= LU_BIG_MAX_N;
-    if (c->n <= TINY_N || !(lin || banded) || c->lu_variant < 4)
+    const bool kry = c->krylov != 0;  // (idahip_set_krylov_rounds is on: no LU bounds n, the LU variant does not matter)
+    if (kry && (c->n <= TINY_N || !(lin || banded) || (c->kry_prec && c->kind == IDAHIP_LINEAR_DENSE)))
+        return fail(c, -2, "the device lock-step rounds of a Krylov ctx take linear dense (no preconditioner), heat and Brusselator problems with %d < n <= %d", TINY_N, LU_BIG_MAX_N);
+    if (!kry && (c->n <= TINY_N || !(lin || banded) || c->lu_variant < 4))
         return fail(c, -2, "the device-resident lock-step stepper takes linear dense, heat and Brusselator problems with %d < n <= %d (LU variant 4)", TINY_N, LU_BIG_MAX_N);
     if (!c->h_constr.empty()) return fail(c, -2, "the device lock-step stepper does not check constraints: the host stepper does (DESIGN.md section 4g)");
     if (const int rcm = missing_id(c, "idahip_round_solve")) return rcm;
@@ -2549,9 +2647,25 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     a.yout = hYout ? c->tiny_yout : nullptr;
     a.ypout = hYPout ? c->tiny_ypout : nullptr;
     a.round_base = call->round_base;
-    a.fused_jac = (c->kind == IDAHIP_LINEAR_DENSE && !c->jac_dq) ? 1 : 0;
-    if (c->jac_dq && !c->dq_hh && (rc = dalloc(c, &c->dq_hh, (size_t)batch))) return rc;
-    a.lu_period = c->lu_period;
+    a.fused_jac = (c->kind == IDAHIP_LINEAR_DENSE && !c->jac_dq && !kry) ? 1 : 0;
+    if ((c->jac_dq || (kry && c->kry_prec)) && !c->dq_hh && (rc = dalloc(c, &c->dq_hh, (size_t)batch))) return rc;
+    a.lu_period = kry ? 1 : c->lu_period;  // (a psetup is one band launch: nothing to amortise)
+    KryRoundArgs kr{};
+    if (kry) {
+        if (!c->kry_rcnt) rc |= dalloc(c, &c->kry_rcnt, (size_t)3 * batch);
+        if (!c->kry_rint) rc |= dalloc(c, &c->kry_rint, (size_t)2 * batch);
+        if (!c->kry_rres) rc |= dalloc(c, &c->kry_rres, (size_t)batch);
+        if (rc) return rc;
+        // npe / nps are not in the controller record: they travel in arrays of their own (idahip_krylov_rounds_put / get_counters)
+        c->kry_h_npe.resize((size_t)batch, 0);
+        c->kry_h_nps.resize((size_t)batch, 0);
+        IDAHIP_HIP(c, hipMemcpyAsync(c->kry_rcnt, c->kry_h_npe.data(), sizeof(int64_t) * batch, hipMemcpyHostToDevice, c->stream));
+        IDAHIP_HIP(c, hipMemcpyAsync(c->kry_rcnt + batch, c->kry_h_nps.data(), sizeof(int64_t) * batch, hipMemcpyHostToDevice, c->stream));
+        IDAHIP_HIP(c, hipMemsetAsync(c->kry_rcnt + 2 * (size_t)batch, 0, sizeof(int64_t) * batch, c->stream));
+        kr.prec = c->kry_prec;
+        kr.nli = c->kry_rint; kr.flag = c->kry_rint + batch;
+        kr.npe = (long long*)c->kry_rcnt; kr.nps = (long long*)c->kry_rcnt + batch; kr.ready = (long long*)c->kry_rcnt + 2 * (size_t)batch;
+    }
     a.roots = (idahip_root_state*)c->tiny_roots;
     int* ib = c->rnd_i;
     a.stepping = ib; a.in_newton = ib + batch; a.skipP = ib + 2 * batch; a.skipL = ib + 3 * batch; a.skipI = ib + 4 * batch;
@@ -2562,6 +2676,7 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     a.lu_info = c->lu_info;
     a.tn = c->rnd_d; a.cj = c->rnd_d + batch; a.scale = c->rnd_d + 2 * batch; a.nrm_out = c->rnd_d + 3 * batch;
     a.rounds_done = (long long*)c->tiny_rounds;
+    kr.tol = a.scale;  // (a Krylov ctx does not scale the correction: the slot carries the solver's tolerance)
     hipLaunchKernelGGL(round_init_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a);
     IDAHIP_HIP(c, hipMemsetAsync(a.summary, 0, 2 * sizeof(int), c->stream));
     const size_t shm_wg = sizeof(double) * (4 * (size_t)n + 8);
@@ -2579,64 +2694,69 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
             auto kern = call->nroots > 0 ? (tstop ? round_begin_kernel<true, true> : round_begin_kernel<true, false>)
                                          : (tstop ? round_begin_kernel<false, true> : round_begin_kernel<false, false>);
             hipLaunchKernelGGL(kern, dim3(batch), dim3(WG_NT), shm_wg, c->stream, a);
-            hipLaunchKernelGGL(round_lists_kernel, dim3(1), dim3(1024), 0, c->stream, a);
+            // (a Krylov ctx without the preconditioner factors nothing: no list)
+            if (!kry || c->kry_prec) hipLaunchKernelGGL(round_lists_kernel, dim3(1), dim3(1024), 0, c->stream, a);
         }
-        // n > 1024 (config 4): a factorisation is ~640 launches, most of them one workgroup per matrix, and a third of a small
-        // batch needs one in any round -- launches sized for the whole batch cost more than they do at n = 512 (11.4 against
-        // 12.3 k iters/s in round 4). The list's length comes back to the host (4 bytes, behind the residual kernels enqueued
-        // below: the copy's round trip is hidden) and the LU's launches are sized by it, as the host stepper's are.
-        const bool lu_cnt_on_host = n > LU_MAX_N && !c->band;  // (the band LU is one launch: its surplus lanes leave on reading the count)
-        if (lu_cnt_on_host) {
-            IDAHIP_HIP(c, hipMemcpyAsync(c->rnd_host + 2, a.lu_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            IDAHIP_HIP(c, hipEventRecord(c->ev_cnt, c->stream));
-        }
-        {   // sys(y0), y <- y0 = 0 (newton.rs:73): without and with the Jacobian (J = B + cj A falls out of the same sweep)
-            KTimer kt(c, IDAHIP_K_SYS, 0);
-            sa.reset_ee = 1; sa.skip = a.skipP;
-            if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
-        }
-        if (a.fused_jac) {
-            KTimer kt(c, IDAHIP_K_SYS_JAC, 0);
-            sa.skip = a.skipL;
-            if ((rc = launch_sys(c, sa, batch, c->jw))) return rc;
-        } else {  // no fused residual + Jacobian kernel for this problem: the residual, then the Jacobian of the same systems
-            {
-                KTimer kt(c, IDAHIP_K_SYS, 0);
-                sa.skip = a.skipL;
-                if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
-            }
-            KTimer kt(c, IDAHIP_K_JAC, 0);
-            if (c->jac_dq)  // the systems' hh from their records, and their nre_dq
-                hipLaunchKernelGGL(dq_round_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh,
-                                   batch, dq_evals(c));
-            if ((rc = launch_jac(c, c->jw, a.ident, a.cj, batch, nullptr, nullptr, nullptr, a.skipL, c->dq_hh))) return rc;
-        }
-        {
-            int nlu = batch;
-            const int* d_cnt = a.lu_cnt;
+        if (kry) {
+            if ((rc = krylov_round_newton(c, a, kr, sa))) return rc;
+        } else {
+            // n > 1024 (config 4): a factorisation is ~640 launches, most of them one workgroup per matrix, and a third of a small
+            // batch needs one in any round -- launches sized for the whole batch cost more than they do at n = 512 (11.4 against
+            // 12.3 k iters/s in round 4). The list's length comes back to the host (4 bytes, behind the residual kernels enqueued
+            // below: the copy's round trip is hidden) and the LU's launches are sized by it, as the host stepper's are.
+            const bool lu_cnt_on_host = n > LU_MAX_N && !c->band;  // (the band LU is one launch: its surplus lanes leave on reading the count)
             if (lu_cnt_on_host) {
-                IDAHIP_HIP(c, hipEventSynchronize(c->ev_cnt));
-                nlu = c->rnd_host[2];
-                d_cnt = nullptr;
-                if (nlu < 0 || nlu > batch) return fail(c, -4, "list length %d outside 0..%d", nlu, batch);
+                IDAHIP_HIP(c, hipMemcpyAsync(c->rnd_host + 2, a.lu_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                IDAHIP_HIP(c, hipEventRecord(c->ev_cnt, c->stream));
             }
-            KTimer kt(c, IDAHIP_K_LU, 0);
-            if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, a.lu_list, nlu, d_cnt);
-            else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt);
-            if (rc) return rc;
-            if ((rc = post_launch(c, "lu"))) return rc;
-        }
-        hipLaunchKernelGGL(round_newton_ctl_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a, 0);
-        for (int m = 1; m <= idactl::MAXNLSIT; ++m) {
-            {
-                KTimer kt(c, IDAHIP_K_NEWTON_ITER, 0);
-                if ((rc = launch_newton_iter(c, a.ident, a.scale, a.nrm_out, a.skipI, batch))) return rc;
-            }
-            hipLaunchKernelGGL(round_newton_ctl_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a, m);
-            if (m < idactl::MAXNLSIT) {
+            {   // sys(y0), y <- y0 = 0 (newton.rs:73): without and with the Jacobian (J = B + cj A falls out of the same sweep)
                 KTimer kt(c, IDAHIP_K_SYS, 0);
-                sa.reset_ee = 0; sa.skip = a.skipS;
+                sa.reset_ee = 1; sa.skip = a.skipP;
                 if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+            }
+            if (a.fused_jac) {
+                KTimer kt(c, IDAHIP_K_SYS_JAC, 0);
+                sa.skip = a.skipL;
+                if ((rc = launch_sys(c, sa, batch, c->jw))) return rc;
+            } else {  // no fused residual + Jacobian kernel for this problem: the residual, then the Jacobian of the same systems
+                {
+                    KTimer kt(c, IDAHIP_K_SYS, 0);
+                    sa.skip = a.skipL;
+                    if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+                }
+                KTimer kt(c, IDAHIP_K_JAC, 0);
+                if (c->jac_dq)  // the systems' hh from their records, and their nre_dq
+                    hipLaunchKernelGGL(dq_round_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh,
+                                       batch, dq_evals(c));
+                if ((rc = launch_jac(c, c->jw, a.ident, a.cj, batch, nullptr, nullptr, nullptr, a.skipL, c->dq_hh))) return rc;
+            }
+            {
+                int nlu = batch;
+                const int* d_cnt = a.lu_cnt;
+                if (lu_cnt_on_host) {
+                    IDAHIP_HIP(c, hipEventSynchronize(c->ev_cnt));
+                    nlu = c->rnd_host[2];
+                    d_cnt = nullptr;
+                    if (nlu < 0 || nlu > batch) return fail(c, -4, "list length %d outside 0..%d", nlu, batch);
+                }
+                KTimer kt(c, IDAHIP_K_LU, 0);
+                if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, a.lu_list, nlu, d_cnt);
+                else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt);
+                if (rc) return rc;
+                if ((rc = post_launch(c, "lu"))) return rc;
+            }
+            hipLaunchKernelGGL(round_newton_ctl_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a, 0);
+            for (int m = 1; m <= idactl::MAXNLSIT; ++m) {
+                {
+                    KTimer kt(c, IDAHIP_K_NEWTON_ITER, 0);
+                    if ((rc = launch_newton_iter(c, a.ident, a.scale, a.nrm_out, a.skipI, batch))) return rc;
+                }
+                hipLaunchKernelGGL(round_newton_ctl_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a, m);
+                if (m < idactl::MAXNLSIT) {
+                    KTimer kt(c, IDAHIP_K_SYS, 0);
+                    sa.reset_ee = 0; sa.skip = a.skipS;
+                    if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+                }
             }
         }
         IDAHIP_HIP(c, hipMemsetAsync(a.summary, 0, sizeof(int), c->stream));
@@ -2667,7 +2787,19 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     if (hYPout) IDAHIP_HIP(c, hipMemcpyAsync(hYPout, c->tiny_ypout, sizeof(double) * ysz, hipMemcpyDeviceToHost, c->stream));
     unsigned long long hstats[IDAHIP_K_COUNT];
     IDAHIP_HIP(c, hipMemcpyAsync(hstats, a.stats, sizeof hstats, hipMemcpyDeviceToHost, c->stream));
+    std::vector<int64_t> kcnt;
+    if (kry) {
+        kcnt.resize((size_t)3 * batch);
+        IDAHIP_HIP(c, hipMemcpyAsync(kcnt.data(), c->kry_rcnt, sizeof(int64_t) * kcnt.size(), hipMemcpyDeviceToHost, c->stream));
+    }
     IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    for (int b = 0; kry && b < batch; ++b) {
+        // (a system that idaens_stream created anew in the call's last round has not set up yet: its counters have restarted with it)
+        const bool fresh = static_cast<const idactl::SysCore*>(hSys)[b].nsetups == 0;
+        c->kry_h_npe[b] = fresh ? 0 : kcnt[b];
+        c->kry_h_nps[b] = fresh ? 0 : kcnt[(size_t)batch + b];
+        if (c->kry_prec && kcnt[2 * (size_t)batch + b] != 0) c->kry_pready[b] = 1;  // as after the host stepper's psetup calls
+    }
     for (int k = 0; k < IDAHIP_K_COUNT; ++k) c->k_systems[k] += (int64_t)hstats[k];  // systems actually served, per kernel class
     c->k_systems[IDAHIP_K_VECTOR] += 2 * r * (int64_t)batch;
     return 0;

@@ -349,7 +349,9 @@ __device__ __forceinline__ void kry_lds(double* sm, idakry::Sys** k, double** pa
 // ---------------------------------------------------------------------------------------------- fused path
 // The whole solve of one listed system in one launch (IDAHIP_HEAT1D, IDAHIP_BRUSS1D, IDAHIP_LINEAR_DENSE). Dynamic LDS: the state and the partials,
 // then 3 n doubles (products, y', yp'); the basis lives in a.V and stays in L2.
-template <int KIND, bool PREC>
+// ROUND: the instantiation of the device lock-step rounds (round_ida.hpp), launched over the whole batch with a.skip per system; a
+// skipped system's workgroup leaves at once. The host stepper's launches are the ROUND = false instantiations, which have no such test.
+template <int KIND, bool PREC, bool ROUND = false>
 __global__ __launch_bounds__(KRY_T) void krylov_fused_kernel(KryArgs a) {
     extern __shared__ __align__(16) double sm[];
     idakry::Sys* k;
@@ -359,6 +361,9 @@ __global__ __launch_bounds__(KRY_T) void krylov_fused_kernel(KryArgs a) {
     double* sy = sp + n;
     double* syp = sy + n;
     const int s = blockIdx.x;
+    if constexpr (ROUND) {
+        if (a.skip[s] != 0) return;  // (uniform over the workgroup, before the first barrier)
+    }
     const int b = a.idx[s];
     const long vb = (long)b * n;
     double* Vb = a.V + (long)b * (a.maxl + 1) * n;

@@ -15,8 +15,15 @@
 // (shared with the host stepper). A Newton solve that ends in ConvergenceRecover with a stale Jacobian (newton.rs:146-152:
 // set up again, iterate again) continues in the NEXT round's setup and iteration passes instead of extending this round: a
 // system's own sequence of operations -- hence its results -- is unchanged, only the round in which they happen is.
+//
+// A Krylov ctx with idahip_set_krylov_rounds on runs the same round with the linear algebra replaced:
+//   round_begin_kernel ; (preconditioner: round_lists_kernel) ; sys ; sys of the systems that set up
+//   preconditioner:      dq_round_prep_kernel ; band DQ Jacobian into kry_pab ; band getrf on the device-built list
+//   4 x { krylov_fused_kernel<.., ROUND> ; round_krylov_ctl_kernel ; sys }   (phase 0 of the control kernel before the first pass)
+//   round_end_kernel
 #pragma once
 #include "ida_flow.hpp"
+#include "../host/krylov_scalar.hpp"
 #include "solve_kernels.hpp"
 #include "vector_kernels.hpp"
 
@@ -275,6 +282,35 @@ __global__ __launch_bounds__(1024) void round_lists_kernel(RoundArgs a) {
     }
 }
 
+// ---- what follows a convergence test (newton.rs:109-153): converged / iterate again / ConvergenceRecover. true = sys(y), then the
+// next iteration pass
+__device__ __forceinline__ bool round_after_ctest(const RoundArgs& a, idactl::SysCore& s, int b, int ret, bool converged) {
+    if (ret == idactl::NLS_SUCCESS && converged) {
+        s.jcur = false;
+        s.nls_ret = idactl::NLS_SUCCESS;
+        a.skipI[b] = 1;
+        return false;
+    }
+    if (ret == idactl::NLS_SUCCESS) {
+        s.curiter += 1;
+        if (s.curiter >= idactl::MAXNLSIT) ret = idactl::NLS_CONV_RECVR;
+    }
+    if (ret == idactl::NLS_SUCCESS) {
+        a.skipS[b] = 0;  // sys(y), then iterate again
+        s.nre += 1;
+        return true;
+    }
+    s.nconvfails += 1;  // ConvergenceRecover
+    a.skipI[b] = 1;
+    if (!s.jcur) {
+        s.call_lsetup = true;
+        s.newton_retry = true;  // sys(y0) + setup + iterations again: in the next round
+    } else {
+        s.nls_ret = idactl::NLS_CONV_RECVR;
+    }
+    return false;
+}
+
 // ---- Newton's bookkeeping between the batched kernels (newton.rs:73-153, ida_nls.rs:168-179, 218-266); one thread per system.
 // phase 0: after the residual (and setup) kernels; phase 1..4: after the m-th newton_iter_kernel of the round
 __global__ void round_newton_ctl_kernel(RoundArgs a, int phase) {
@@ -307,31 +343,74 @@ __global__ void round_newton_ctl_kernel(RoundArgs a, int phase) {
             const double delnrm = sqrt(a.nrm_out[b] / (double)n);
             s.niters += 1;
             bool converged = false;
-            int ret = idactl::conv_test(s, delnrm, &converged);
-            if (ret == idactl::NLS_SUCCESS && converged) {
-                s.jcur = false;
-                s.nls_ret = idactl::NLS_SUCCESS;
-                a.skipI[b] = 1;
-            } else {
-                if (ret == idactl::NLS_SUCCESS) {
-                    s.curiter += 1;
-                    if (s.curiter >= idactl::MAXNLSIT) ret = idactl::NLS_CONV_RECVR;
+            const int ret = idactl::conv_test(s, delnrm, &converged);
+            again = round_after_ctest(a, s, b, ret, converged);
+        }
+    }
+    const unsigned long long m_sys = __ballot(again);
+    if (m_sys != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&a.stats[IDAHIP_K_SYS], (unsigned long long)__popcll(m_sys));
+}
+
+// ---- the same bookkeeping on a Krylov ctx (idahip_set_krylov_rounds; krylov_kernels.hpp): the linear setup forms
+// nothing (after_lsetup_nojac) or is the band preconditioner's psetup, whose Jacobian and factorisation the round has launched on
+// the list; the iteration is krylov_fused_kernel<.., ROUND>, whose tolerance is formed here from the record. The order per system
+// is the host stepper's (ensemble_ida.cpp, newton_solve_batched). npe / nps and the ready flags live in arrays of their own: the
+// record's size is the one-thread stepper's LDS footprint per system.
+struct KryRoundArgs {
+    int prec;            // the ctx has the band preconditioner on
+    const int* nli;      // [batch] linear iterations / flag of the pass's solve
+    const int* flag;
+    double* tol;         // [batch] idakry::tolerance(n, eps_newt) of the systems that iterate
+    long long* npe;      // [batch] preconditioner setups / solves of the system (absolute; they restart with the system)
+    long long* nps;
+    long long* ready;    // [batch] nonzero: the system had a psetup in this call
+};
+
+__global__ void round_krylov_ctl_kernel(RoundArgs a, KryRoundArgs k, int phase) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool mine = b < a.f.batch && a.in_newton[b] && (phase == 0 || a.skipI[b] == 0);
+    const unsigned long long m_iter = __ballot(mine && phase != 0);
+    if (m_iter != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&a.stats[IDAHIP_K_NEWTON_ITER], (unsigned long long)__popcll(m_iter));
+    // without the preconditioner no list is built: the residuals of the systems that set up are counted here (the others: round_begin_kernel)
+    bool again = mine && phase == 0 && !k.prec && a.skipL[b] == 0;
+    if (mine) {
+        idactl::SysCore& s = a.sys[b];
+        const int n = a.v.n;
+        if (phase == 0) {
+            s.nre += 1;  // sys(y0)
+            bool go = true;
+            if (a.skipL[b] == 0) {
+                if (s.nsetups == 0) {  // the system's first setup (a system idaens_stream has created anew included)
+                    k.npe[b] = 0;
+                    k.nps[b] = 0;
                 }
-                if (ret == idactl::NLS_SUCCESS) {
-                    a.skipS[b] = 0;  // sys(y), then iterate again
-                    s.nre += 1;
-                    again = true;
-                } else {
-                    s.nconvfails += 1;  // ConvergenceRecover
-                    a.skipI[b] = 1;
-                    if (!s.jcur) {
-                        s.call_lsetup = true;
-                        s.newton_retry = true;  // sys(y0) + setup + iterations again: in the next round
-                    } else {
-                        s.nls_ret = idactl::NLS_CONV_RECVR;
-                    }
+                idactl::after_lsetup_nojac(s);
+                if (k.prec) {  // (nre_dq: dq_round_prep_kernel)
+                    if (a.lu_info[b] != 0) s.nls_ret = idactl::NLS_LSETUP_RECVR;
+                    k.npe[b] += 1;
+                    k.ready[b] = 1;
+                }
+                if (s.nls_ret == idactl::NLS_LSETUP_RECVR) {
+                    s.nconvfails += 1;  // jcur is true: no retry
+                    go = false;
                 }
             }
+            if (go) {
+                s.curiter = 0;
+                a.skipI[b] = 0;
+                k.tol[b] = idakry::tolerance(n, s.eps_newt);
+            }
+        } else {
+            a.skipS[b] = 1;
+            const int nli = k.nli[b], flag = k.flag[b];
+            s.niters += 1;
+            (void)idactl::after_lsolve(s, IDAHIP_LS_ITERATIVE, nli, flag != 0);  // the correction is not scaled
+            s.nre_dq += nli;
+            if (k.prec) k.nps[b] += 1 + nli;
+            bool converged = false;
+            int ret = idactl::NLS_CONV_RECVR;  // every flag other than SUCCESS: ConvergenceRecover, no convergence test
+            if (flag == idakry::SUCCESS) ret = idactl::conv_test(s, sqrt(a.nrm_out[b] / (double)n), &converged);
+            again = round_after_ctest(a, s, b, ret, converged);
         }
     }
     const unsigned long long m_sys = __ballot(again);

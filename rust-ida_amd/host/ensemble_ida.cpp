@@ -768,9 +768,13 @@ int continue_schedule(idaens* e, SolveCall& C, int b) {
 int device_ctl_applies(const idaens* e, const SolveCall& C) {
     const int k = idahip_kind(e->ctx);
     if (!e->device_ctl || C.itask != IDAENS_NORMAL || e->trace_sys >= 0) return 0;
-    if (idahip_krylov(e->ctx, nullptr) == 1) return 0;  // the device steppers solve with factors: a Krylov ctx steps on the host
+    // a Krylov ctx steps on the host unless idahip_set_krylov_rounds is on (read anew by every solve call)
+    const bool kry = idahip_krylov(e->ctx, nullptr) == 1;
+    if (kry && idahip_krylov_rounds(e->ctx) != 1) return 0;
     // root finding on the device: the function family of idaens_set_roots (not a user callback), not in idaens_stream
     if (e->nrtfn != 0 && (e->rt_fn != nullptr || e->nrtfn > IDAHIP_MAX_ROOTS || C.recycle)) return 0;
+    if (kry)  // (constraints are refused on a Krylov ctx; no LU: the variant does not matter)
+        return (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D || k == IDAHIP_BRUSS1D)) ? 2 : 0;
     if (e->n <= 8 && (k == IDAHIP_ROBERTS || k == IDAHIP_LORENZ63)) return 1;
     if (idahip_constraints(e->ctx, nullptr) == 1) return 0;  // the lock-step device rounds have no constraint check
     if (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D || k == IDAHIP_BRUSS1D) && idahip_lu_variant(e->ctx) >= 4) return 2;
@@ -822,12 +826,25 @@ int solve_core_device(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, 
     if (C.hYout) yo.resize((size_t)C.ntout * batch * n);
     if (C.hYPout) ypo.resize((size_t)C.ntout * batch * n);
     int64_t rounds_run = -1;
+    // a Krylov ctx's npe / nps are not in the record (Sys above): they go to the ctx and come back from it around the call
+    const bool kry = mode == 2 && idahip_krylov(e->ctx, nullptr) == 1;
+    std::vector<int64_t> npe, nps;
+    if (kry) {
+        npe.resize(batch);
+        nps.resize(batch);
+        for (int b = 0; b < batch; ++b) { npe[b] = S[b].npe; nps[b] = S[b].nps; }
+        ENS_CALL(e, idahip_krylov_rounds_put_counters(e->ctx, npe.data(), nps.data()));
+    }
     if (mode == 1)
         ENS_CALL(e, idahip_tiny_solve(e->ctx, st.data(), sizeof(SysCore), &call, rounds.data(), acc, C.hYout ? yo.data() : nullptr,
                                       C.hYPout ? ypo.data() : nullptr));
     else
         ENS_CALL(e, idahip_round_solve(e->ctx, st.data(), sizeof(SysCore), &call, rounds.data(), acc, C.hYout ? yo.data() : nullptr,
                                        C.hYPout ? ypo.data() : nullptr, &rounds_run));
+    if (kry) {
+        ENS_CALL(e, idahip_krylov_rounds_get_counters(e->ctx, npe.data(), nps.data()));
+        for (int b = 0; b < batch; ++b) { S[b].npe = (long)npe[b]; S[b].nps = (long)nps[b]; }
+    }
     int64_t rmax = 0;
     bool unfinished = false;
     for (int b = 0; b < batch; ++b) {

@@ -50,6 +50,7 @@ HIP_SYMBOLS = [
     "idahip_newton_iter_krylov",
     "idahip_set_krylov_band_prec", "idahip_krylov_band_prec", "idahip_krylov_psetup", "idahip_krylov_psolve", "idahip_krylov_download_prec",
     "idahip_krylov_upload_prec",
+    "idahip_set_krylov_rounds", "idahip_krylov_rounds", "idahip_krylov_rounds_put_counters", "idahip_krylov_rounds_get_counters",
     "idahip_set_suppress_alg", "idahip_suppress_alg", "idahip_wrms_masked",
 ]
 ENS_SYMBOLS = [
@@ -182,6 +183,10 @@ def load():
     H.idahip_krylov_psolve.argtypes = [vp, dp, dp, i32p, ci]
     H.idahip_krylov_download_prec.argtypes = [vp, ci, dp, i64p]
     H.idahip_krylov_upload_prec.argtypes = [vp, ci, dp, i64p]
+    H.idahip_set_krylov_rounds.argtypes = [vp, ci]
+    H.idahip_krylov_rounds.argtypes = [vp]
+    H.idahip_krylov_rounds_put_counters.argtypes = [vp, i64p, i64p]
+    H.idahip_krylov_rounds_get_counters.argtypes = [vp, i64p, i64p]
     H.idahip_timing_enable.argtypes = [vp, ci]
     H.idahip_timing_get.argtypes = [vp, ci, dp, i64p, i64p]
     H.idahip_timing_reset.argtypes = [vp]
@@ -277,6 +282,14 @@ class Ctx:
 
     def krylov_fused(self):
         return bool(self._chk(self.H.idahip_krylov_fused(self.h), "krylov_fused"))
+
+    def set_krylov_rounds(self, on=True):
+        """Krylov ctx: step on the device lock-step rounds (idahip_round_solve) instead of the host stepper. Off by default; refused
+        for a ctx that is not a Krylov ctx and for host-callback residuals."""
+        self._chk(self.H.idahip_set_krylov_rounds(self.h, int(bool(on))), "set_krylov_rounds")
+
+    def krylov_rounds(self):
+        return bool(self._chk(self.H.idahip_krylov_rounds(self.h), "krylov_rounds"))
 
     def krylov_solve(self, tn, cj, tol, b, idx=None):
         """The SPGMR solve of the listed systems at the ctx-resident yy, yp, savres, ewt; b [nsys][n] by list position

@@ -11,6 +11,13 @@ One JSON object per line on stdout; --json also writes them to a file.
 
     python tools/krylov_ab.py [--json profiles/krylov_ab.json] [--cases heat linear] [--outputs 1] [--limit 300] [--small]
     python tools/krylov_ab.py --cases heat --json profiles/krylov_prec_ab.json     (the figures of section 4i)
+
+--rounds is another measurement, and this one is an A/B: the Krylov ctx of each case (heat: with the (1, 1) preconditioner) on the
+host stepper against the device lock-step rounds (idahip_set_krylov_rounds), in one process on one ctx, the two alternating over
+--reps repetitions after a warm-up pass of each. Per case one line with the medians, the host stepper's spread (max - min) next to
+the difference of the medians, and for heat a second line: idaens_stream over --stream-rounds rounds, Newton iterations per second.
+
+    python tools/krylov_ab.py --rounds --json profiles/krylov_rounds_ab.json
 """
 import argparse
 import json
@@ -62,6 +69,68 @@ def one(case, solver, outputs, small):
         print(json.dumps(r), flush=True)
 
 
+def rounds_ab(case, outputs, small, reps, stream_rounds):
+    """The Krylov ctx of the case (heat: with the (1, 1) band preconditioner) on the host stepper against the device lock-step rounds
+    (idahip_set_krylov_rounds): one process, one ctx, the two variants alternating over `reps` repetitions after a warm-up pass of
+    each; medians, and the spread of the host-stepper runs next to the difference. heat also: idaens_stream for a fixed number of
+    rounds, Newton iterations per second."""
+    import numpy as np
+    import idahip
+    from idahip import problems
+    kind, n, batch, _ = (SMALL if small else CASES)[case]
+    p = problems.heat1d(n=n, batch=batch) if kind == "heat1d" else problems.linear_dense(n=n, batch=batch, procs=8)
+    touts = p["touts"][:outputs]
+    ctx = problems.make_ctx(p, krylov=0)
+    if kind == "heat1d":
+        ctx.set_krylov_band_prec(1, 1)
+    base = {"case": case, "kind": kind, "n": n, "batch": batch, "solver": "krylov_prec" if kind == "heat1d" else "krylov", "host": socket.gethostname(),
+            "command": "python tools/krylov_ab.py --rounds --cases %s --outputs %d --reps %d%s" % (case, outputs, reps, " --small" if small else "")}
+
+    def timed(rounds, stream):
+        ctx.set_krylov_rounds(rounds)
+        ens = idahip.Ensemble(ctx, p["yy0"], p["yp0"])
+        assert ens.device_controller_active() == (2 if rounds else 0)
+        ctx.H.idahip_sync(ctx.h)
+        t0 = time.perf_counter()
+        if stream:  # "finished": integrations completed inside the stream
+            finished = ens.stream(touts, stream_rounds, stagger_rounds=stream_rounds // 3)
+        else:
+            finished = int((ens.solve_schedule(touts)[0] == 0).sum())
+        ctx.H.idahip_sync(ctx.h)
+        sec = time.perf_counter() - t0
+        c = ens.counters()
+        rec = {"seconds": sec, "nni": int(ens.total_newton_iters()), "rounds": int(ens.total_rounds()), "finished": int(finished),
+               **{k: int(c[k].sum()) for k in ("nst", "nli", "ncfl", "npe", "nps")}}
+        ens.close()
+        return rec
+
+    for mode in (("schedule", "stream") if kind == "heat1d" else ("schedule",)):
+        stream = mode == "stream"
+        runs = {False: [], True: []}
+        for rep in range(reps + 1):  # the first pass of each variant warms the code objects up and is dropped
+            for rounds in (False, True):
+                r = timed(rounds, stream)
+                if rep > 0:
+                    runs[rounds].append(r)
+        out = dict(base, mode=mode, reps=reps)
+        if stream:
+            out["stream_rounds"] = stream_rounds
+        else:
+            out["horizon"] = float(touts[-1])
+        for rounds, name in ((False, "host_stepper"), (True, "device_rounds")):
+            secs = sorted(r["seconds"] for r in runs[rounds])
+            last = runs[rounds][-1]
+            out[name] = {"seconds_median": round(float(np.median(secs)), 5), "seconds_min": round(secs[0], 5), "seconds_max": round(secs[-1], 5),
+                         "newton_iters_per_s_median": round(last["nni"] / float(np.median(secs)), 1),
+                         **{k: last[k] for k in ("nni", "rounds", "finished", "nst", "nli", "ncfl", "npe", "nps")}}
+        h, d = out["host_stepper"], out["device_rounds"]
+        out["device_minus_host_seconds"] = round(d["seconds_median"] - h["seconds_median"], 5)
+        out["host_spread_seconds"] = round(h["seconds_max"] - h["seconds_min"], 5)
+        out["host_over_device"] = round(h["seconds_median"] / d["seconds_median"], 3)
+        print(json.dumps(out), flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
@@ -69,16 +138,23 @@ def main():
     ap.add_argument("--outputs", type=int, default=1, help="outputs of the case's schedule to integrate to (1: heat 0.01, linear dense 0.1)")
     ap.add_argument("--limit", type=int, default=300, help="seconds granted to each (case, solver) child")
     ap.add_argument("--small", action="store_true", help="toy sizes: a rehearsal of the script, not a measurement")
+    ap.add_argument("--rounds", action="store_true", help="the Krylov ctx of each case on the host stepper against the device lock-step rounds, alternating")
+    ap.add_argument("--reps", type=int, default=7, help="--rounds: timed repetitions of each variant")
+    ap.add_argument("--stream-rounds", type=int, default=120, help="--rounds, heat: rounds of the idaens_stream figure")
     ap.add_argument("--one", nargs=2, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.one and a.rounds:
+        return rounds_ab(a.one[0], a.outputs, a.small, a.reps, a.stream_rounds)
     if a.one:
         return one(a.one[0], a.one[1], a.outputs, a.small)
     lines = []
     for case, (_, _, _, solvers) in (SMALL if a.small else CASES).items():
         if case not in a.cases:
             continue
-        for solver in solvers:
+        for solver in (("rounds_ab",) if a.rounds else solvers):
             cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--one", case, solver, "--outputs", str(a.outputs)]
+            if a.rounds:
+                cmd += ["--rounds", "--reps", str(a.reps), "--stream-rounds", str(a.stream_rounds)]
             if a.small:
                 cmd.append("--small")
             r = subprocess.run(cmd, capture_output=True, text=True)
