@@ -1,4 +1,4 @@
-// Batched band LU (getrf / getrs), the band form of the fused Newton-iteration body and the heat problem's band Jacobian, for gfx950.
+// Batched band LU (getrf / getrs), and the band form of the fused Newton-iteration body, for gfx950.
 //
 // Storage: LAPACK dgbtrf's, 0-based. A system with lower bandwidth ml and upper bandwidth mu has ldab = 2 ml + mu + 1 and
 // kv = ml + mu; element (i, j), j - mu <= i <= j + ml, is ab[j * ldab + kv + i - j]. The top ml rows of every column are fill
@@ -336,38 +336,6 @@ __global__ __launch_bounds__(64) void band_newton_iter_kernel(const double* __re
         sum = sum + p * p;
     }
     out[s] = sum;
-}
-
-// ------------------------------------------------------------------------------------------------ heat 1-D, band Jacobian
-// heat_jac_kernel's three entries per column into band storage; the rest of the column (band and fill rows) is written +0.0
-// (J <- 0 first, ida_ls.rs:254). Needs ml >= 1 and mu >= 1.
-__global__ __launch_bounds__(256) void heat_band_jac_kernel(double* __restrict__ ab, int n, int ml, int mu, const double* __restrict__ params,
-                                                            const int* __restrict__ idx, const double* __restrict__ cjs, int chunks,
-                                                            const int* __restrict__ skip) {
-    if (skip && skip[blockIdx.x] != 0) return;
-    const int b = idx[blockIdx.x];
-    const double cj = cjs[blockIdx.x];
-    const double coef = params[b];
-    const int kv = ml + mu, ld = 2 * ml + mu + 1;
-    double* __restrict__ J = ab + (long)b * ld * n;
-    const long total = (long)ld * n;
-    const long per = (total + chunks - 1) / chunks;
-    const long ebeg = blockIdx.y * per;
-    const long eend = (ebeg + per < total) ? ebeg + per : total;
-    for (long e = ebeg + threadIdx.x; e < eend; e += 256) {
-        const int j = (int)(e / ld);
-        const int i = j + (int)(e - (long)j * ld) - kv;
-        double v = 0.0;
-        if (i >= 0 && i < n && i >= j - 1 && i <= j + 1) {
-            if (i == 0 || i == n - 1) {
-                v = (j == i) ? 1.0 : 0.0;
-            } else {
-                if (j == i) v = cj + 2.0 * coef;
-                else v = -coef;
-            }
-        }
-        J[e] = v;
-    }
 }
 
 }  // namespace idahip

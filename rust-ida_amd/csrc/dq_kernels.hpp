@@ -233,112 +233,23 @@ __global__ __launch_bounds__(256) void linear_dq_jac_kernel(DqArgs d, const doub
     }
 }
 
-// ------------------------------------------------------------------------------------------------ heat 1-D
-// Row i of the heat residual (heat_sys_kernel's expression) at yy with entries perturbed where pert(k) holds
-template <class Pert>
-__device__ __forceinline__ double heat_row_perturbed(const double* __restrict__ y, const double* __restrict__ yp, int n, int i,
-                                                     double coef, Pert pert) {
-    double yi, ypi;
-    pert(i, y[i], yp[i], yi, ypi);
-    if (i == 0 || i == n - 1) return yi;
-    double ym, ypm, yq, ypq;
-    pert(i - 1, y[i - 1], yp[i - 1], ym, ypm);
-    pert(i + 1, y[i + 1], yp[i + 1], yq, ypq);
-    return ypi - coef * ((ym - 2.0 * yi) + yq);
-}
+// ------------------------------------------------------------------------------------------------ banded stencil problems
+// Heat1D and Bruss1D (stencil_problems.hpp), with P::row as the row: column j's perturbation reaches rows j-HALF_BW .. j+HALF_BW.
+// A row reads no y' but its own, so y' is perturbed only on the row that is itself perturbed.
 
-// dense ctx: column j's DQ changes rows j-1, j and j+1 only; they are computed from the perturbed inputs, every other entry is the
-// +0.0 the analytic heat_jac_kernel writes there. Same launch shape and the same contract with the factorisation: with `zeroed`
-// (LuWs::jwzero) set, the matrix is all +0.0 already and only those three rows are written.
-__global__ __launch_bounds__(256) void heat_dq_jac_kernel(DqArgs d, const double* __restrict__ params, int chunks,
-                                                          const int* __restrict__ zeroed) {
+// dense ctx: rows j-HALF_BW .. j+HALF_BW of column j from the perturbed inputs, every other entry the +0.0 the analytic
+// stencil_jac_kernel writes there. Same launch shape and the same contract with the factorisation: with `zeroed` (LuWs::jwzero) set,
+// the matrix is all +0.0 already and only those rows are written.
+template <class P>
+__global__ __launch_bounds__(256) void stencil_dq_jac_kernel(DqArgs d, const double* __restrict__ params, int chunks,
+                                                             const int* __restrict__ zeroed) {
     if (d.skip && d.skip[blockIdx.x] != 0) return;
     const int s = blockIdx.x;
     const int n = d.n;
     const int b = d.idx[s];
     const long vb = (long)b * n;
     const double cj = d.cj[s], hh = d.hh[s];
-    const double coef = params[b];
-    const double* __restrict__ y = d.yy + vb;
-    const double* __restrict__ yp = d.yp + vb;
-    const double* __restrict__ rr = d.rr + vb;
-    double* __restrict__ J = d.out + dq_slot(d, s, b) * n * n;
-    const int per = (n + chunks - 1) / chunks;
-    const int jbeg = blockIdx.y * per;
-    const int jend = (jbeg + per < n) ? jbeg + per : n;
-    auto entry = [&](int i, int j) {
-        const double inc = dq_inc(y[j], yp[j], d.ewt[vb + j], hh);
-        const double yj = y[j] + inc, ypj = yp[j] + cj * inc;
-        const double rt = heat_row_perturbed(y, yp, n, i, coef, [&](int k, double a, double ap, double& o, double& op) {
-            o = (k == j) ? yj : a;
-            op = (k == j) ? ypj : ap;
-        });
-        return dq_linsum(1.0 / inc, rt, rr[i]);
-    };
-    if (zeroed && zeroed[b] != 0) {
-        for (int j = jbeg + threadIdx.x; j < jend; j += 256)
-            for (int i = (j > 0 ? j - 1 : 0); i <= j + 1 && i < n; ++i) J[(long)j * n + i] = entry(i, j);
-        return;
-    }
-    for (int j = jbeg; j < jend; ++j)
-        for (int i = threadIdx.x; i < n; i += 256) J[(long)j * n + i] = (i >= j - 1 && i <= j + 1) ? entry(i, j) : 0.0;
-}
-
-// band ctx: every entry of the band storage (heat_band_jac_kernel's launch shape); entry (i, j) in column j's band is row i of
-// group (j mod width)'s residual, in which every column of the group is perturbed
-__global__ __launch_bounds__(256) void heat_band_dq_jac_kernel(DqArgs d, const double* __restrict__ params, int chunks) {
-    if (d.skip && d.skip[blockIdx.x] != 0) return;
-    const int s = blockIdx.x;
-    const int n = d.n, ml = d.ml, mu = d.mu, ld = d.ld, kv = ml + mu, width = ml + mu + 1;
-    const int b = d.idx[s];
-    const long vb = (long)b * n;
-    const double cj = d.cj[s], hh = d.hh[s];
-    const double coef = params[b];
-    const double* __restrict__ y = d.yy + vb;
-    const double* __restrict__ yp = d.yp + vb;
-    const double* __restrict__ w = d.ewt + vb;
-    double* __restrict__ J = d.out + dq_slot(d, s, b) * ld * n;
-    const long total = (long)ld * n;
-    const long per = (total + chunks - 1) / chunks;
-    const long ebeg = blockIdx.y * per;
-    const long eend = (ebeg + per < total) ? ebeg + per : total;
-    for (long e = ebeg + threadIdx.x; e < eend; e += 256) {
-        const int j = (int)(e / ld);
-        const int i = j + (int)(e - (long)j * ld) - kv;
-        double v = 0.0;
-        if (i >= 0 && i < n && i >= j - mu && i <= j + ml) {
-            const int g = j % width;
-            const double rt = heat_row_perturbed(y, yp, n, i, coef, [&](int k, double a, double ap, double& o, double& op) {
-                o = a;
-                op = ap;
-                if (k % width == g) {
-                    const double inc = dq_inc(a, ap, w[k], hh);
-                    o = a + inc;
-                    op = ap + cj * inc;
-                }
-            });
-            const double inc = dq_inc(y[j], yp[j], w[j], hh);
-            v = (1.0 / inc) * (rt - d.rr[vb + i]);
-        }
-        J[e] = v;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ Brusselator 1-D
-// The heat kernels' shapes and contracts with bruss_row_perturbed (problem_kernels.hpp) as the row: column j's perturbation reaches
-// rows j-2 .. j+2; the entries move with the state, so nothing here is a constant of the system.
-
-// dense ctx: rows j-2 .. j+2 of column j from the perturbed inputs, +0.0 everywhere else (what bruss_jac_kernel writes there); with
-// `zeroed` (LuWs::jwzero) set only those five rows are written
-__global__ __launch_bounds__(256) void bruss_dq_jac_kernel(DqArgs d, const double* __restrict__ params, int chunks,
-                                                           const int* __restrict__ zeroed) {
-    if (d.skip && d.skip[blockIdx.x] != 0) return;
-    const int s = blockIdx.x;
-    const int n = d.n;
-    const int b = d.idx[s];
-    const long vb = (long)b * n;
-    const double cj = d.cj[s], hh = d.hh[s];
-    const double* __restrict__ prm = params + (long)b * BRUSS_NPARAM;
+    const double* __restrict__ prm = params + (long)b * P::NPARAM;
     const double* __restrict__ y = d.yy + vb;
     const double* __restrict__ yp = d.yp + vb;
     const double* __restrict__ rr = d.rr + vb;
@@ -350,29 +261,30 @@ __global__ __launch_bounds__(256) void bruss_dq_jac_kernel(DqArgs d, const doubl
         const double inc = dq_inc(y[j], yp[j], d.ewt[vb + j], hh);
         const double yj = y[j] + inc;
         const double ypi = (i == j) ? yp[j] + cj * inc : yp[i];
-        const double rt = bruss_row_perturbed(n, i, ypi, prm, [&](int k) { return (k == j) ? yj : y[k]; });
+        const double rt = P::row(n, i, ypi, prm, [&](int k) { return (k == j) ? yj : y[k]; });
         return dq_linsum(1.0 / inc, rt, rr[i]);
     };
     if (zeroed && zeroed[b] != 0) {
         for (int j = jbeg + threadIdx.x; j < jend; j += 256)
-            for (int i = (j > 2 ? j - 2 : 0); i <= j + 2 && i < n; ++i) J[(long)j * n + i] = entry(i, j);
+            for (int i = (j > P::HALF_BW ? j - P::HALF_BW : 0); i <= j + P::HALF_BW && i < n; ++i) J[(long)j * n + i] = entry(i, j);
         return;
     }
     for (int j = jbeg; j < jend; ++j)
-        for (int i = threadIdx.x; i < n; i += 256) J[(long)j * n + i] = (i >= j - 2 && i <= j + 2) ? entry(i, j) : 0.0;
+        for (int i = threadIdx.x; i < n; i += 256) J[(long)j * n + i] = stencil_in_band<P>(i, j) ? entry(i, j) : 0.0;
 }
 
-// band ctx and the Krylov ctx's band preconditioner, any 0 <= ml, mu < n: entry (i, j) of column j's band is row i of group
-// (j mod width)'s residual, in which every column of the group is perturbed -- widths below (2, 2) fold columns that share a row
-// into one group, exactly as idaLsBandDQJac does
-__global__ __launch_bounds__(256) void bruss_band_dq_jac_kernel(DqArgs d, const double* __restrict__ params, int chunks) {
+// band ctx and the Krylov ctx's band preconditioner, any 0 <= ml, mu < n (stencil_band_jac_kernel's launch shape): entry (i, j) of
+// column j's band is row i of group (j mod width)'s residual, in which every column of the group is perturbed -- widths below
+// (HALF_BW, HALF_BW) fold columns that share a row into one group, exactly as idaLsBandDQJac does
+template <class P>
+__global__ __launch_bounds__(256) void stencil_band_dq_jac_kernel(DqArgs d, const double* __restrict__ params, int chunks) {
     if (d.skip && d.skip[blockIdx.x] != 0) return;
     const int s = blockIdx.x;
     const int n = d.n, ml = d.ml, mu = d.mu, ld = d.ld, kv = ml + mu, width = ml + mu + 1;
     const int b = d.idx[s];
     const long vb = (long)b * n;
     const double cj = d.cj[s], hh = d.hh[s];
-    const double* __restrict__ prm = params + (long)b * BRUSS_NPARAM;
+    const double* __restrict__ prm = params + (long)b * P::NPARAM;
     const double* __restrict__ y = d.yy + vb;
     const double* __restrict__ yp = d.yp + vb;
     const double* __restrict__ w = d.ewt + vb;
@@ -389,7 +301,7 @@ __global__ __launch_bounds__(256) void bruss_band_dq_jac_kernel(DqArgs d, const 
             const int g = j % width;
             double ypi = yp[i];
             if (i % width == g) ypi = ypi + cj * dq_inc(y[i], yp[i], w[i], hh);
-            const double rt = bruss_row_perturbed(n, i, ypi, prm, [&](int k) {
+            const double rt = P::row(n, i, ypi, prm, [&](int k) {
                 return (k % width == g) ? y[k] + dq_inc(y[k], yp[k], w[k], hh) : y[k];
             });
             const double inc = dq_inc(y[j], yp[j], w[j], hh);

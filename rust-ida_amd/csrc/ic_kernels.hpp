@@ -74,9 +74,8 @@ __global__ void ic_tiny_sys_kernel(SysArgsIC a, const double* __restrict__ param
     tiny_sys_body<KIND>(a, params, nparam, nsys);
 }
 // (linear dense: linear_sys_kernel<VEC, false, SysArgsIC> itself)
-template <int VEC>
-__global__ __launch_bounds__(256) void ic_heat_sys_kernel(SysArgsIC a, const double* __restrict__ params) { heat_sys_body<VEC>(a, params); }
-__global__ __launch_bounds__(256) void ic_bruss_sys_kernel(SysArgsIC a, const double* __restrict__ params) { bruss_sys_body(a, params); }
+template <class P, int VEC>
+__global__ __launch_bounds__(256) void ic_stencil_sys_kernel(SysArgsIC a, const double* __restrict__ params) { stencil_sys_body<P, VEC>(a, params); }
 __global__ __launch_bounds__(256) void ic_callback_pre_kernel(SysArgsIC a, double* __restrict__ stage) { callback_pre_body(a, stage); }
 
 // ------------------------------------------------------------------------------------------------ bookkeeping around it

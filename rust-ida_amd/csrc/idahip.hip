@@ -24,6 +24,61 @@ int dalloc(idahip_ctx* c, T** p, size_t count) {
     return 0;
 }
 
+// What the host side knows about a problem kind, by idahip_problem value. band_min: the least ml and mu of the kind's device band
+// form (0: it has none); banded: the Jacobian's content is banded by construction (the super-panel LU's default).
+// IDAHIP_HOST_CALLBACK runs the user's functions instead: its band form takes every width and is asked for by name where it matters.
+struct KindFacts {
+    int nparam, band_min;
+    bool krylov, rounds, banded;
+};
+const KindFacts KIND_FACTS[] = {
+    {0, 0, false, false, false},                               // IDAHIP_ROBERTS
+    {3, 0, false, false, false},                               // IDAHIP_LORENZ63
+    {0, 0, true, true, false},                                 // IDAHIP_LINEAR_DENSE
+    {Heat1D::NPARAM, Heat1D::HALF_BW, true, true, true},       // IDAHIP_HEAT1D
+    {0, 0, true, false, false},                                // IDAHIP_HOST_CALLBACK
+    {Bruss1D::NPARAM, Bruss1D::HALF_BW, true, true, true},     // IDAHIP_BRUSS1D
+};
+constexpr int KIND_COUNT = (int)(sizeof(KIND_FACTS) / sizeof(KIND_FACTS[0]));
+const KindFacts& kind_facts(idahip_problem kind) { return KIND_FACTS[(int)kind]; }
+
+// f(P{}) with the stencil description (stencil_problems.hpp) of the ctx's kind; false, and nothing called, for every other kind
+template <class F>
+bool with_stencil(const idahip_ctx* c, F f) {
+    switch (c->kind) {
+        case IDAHIP_HEAT1D: f(Heat1D{}); return true;
+        case IDAHIP_BRUSS1D: f(Bruss1D{}); return true;
+        default: return false;
+    }
+}
+
+// what a launch site returns where with_stencil found no description: a kind that has no kernel there
+int no_kernel(idahip_ctx* c, const char* what) { return fail(c, -2, "no %s kernel for problem kind %d", what, (int)c->kind); }
+
+// grid.y of the kernels that split one system's work into chunks: the launch reaches 2048 workgroups, or `cap` chunks per system
+int launch_chunks(int nsys, int cap) {
+    int chunks = 1;
+    while ((long)nsys * chunks < 2048 && chunks < cap) chunks *= 2;
+    return chunks;
+}
+
+// the one-launch Krylov solve of nsys listed systems (ROUND: inside a device lock-step round); false: the ctx's kind has no such kernel
+template <bool ROUND>
+bool launch_krylov_fused(idahip_ctx* c, const KryArgs& a, int nsys) {
+    const dim3 grid(nsys), blk(KRY_T);
+    const size_t shm = kry_lds_bytes(c->n, 3);
+    const bool prec = c->kry_prec != 0;
+    if (with_stencil(c, [&](auto p) {
+            constexpr int K = decltype(p)::KIND;
+            if (prec) hipLaunchKernelGGL((krylov_fused_kernel<K, true, ROUND>), grid, blk, shm, c->stream, a);
+            else hipLaunchKernelGGL((krylov_fused_kernel<K, false, ROUND>), grid, blk, shm, c->stream, a);
+        }))
+        return true;
+    if (c->kind != IDAHIP_LINEAR_DENSE) return false;
+    hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_LINEAR_DENSE, false, ROUND>), grid, blk, shm, c->stream, a);
+    return true;
+}
+
 int check_list(idahip_ctx* c, const int32_t* hIdx, int nsys) {
     if (!c) return -1;
     if (nsys < 0 || nsys > c->batch) return fail(c, -2, "nsys = %d out of range (batch = %d)", nsys, c->batch);
@@ -116,7 +171,8 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     if (!out) return -1;
     *out = nullptr;
     if (n < 1 || batch < 1) return -2;
-    if ((int)kind < 0 || (int)kind > (int)IDAHIP_BRUSS1D) return -2;
+    if ((int)kind < 0 || (int)kind >= KIND_COUNT) return -2;
+    const KindFacts& facts = kind_facts(kind);
     if ((kind == IDAHIP_ROBERTS || kind == IDAHIP_LORENZ63) && n != 3) return -2;
     if (kind == IDAHIP_BRUSS1D && (n % 2 != 0 || n < 10)) {
         std::fprintf(stderr, "IDAHIP_BRUSS1D: n = %d is not 2 m with m >= 5 grid points (two interleaved species)\n", n);
@@ -134,7 +190,7 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     const bool nomat = band || krylov_maxl > 0;  // no n x n storage
     c->npad16 = (n + 15) & ~15;
     c->list_seen.assign(((size_t)batch + 63) / 64, 0);
-    c->lu_superpanel = (kind == IDAHIP_HEAT1D || kind == IDAHIP_BRUSS1D) ? 1 : 0;  // banded content
+    c->lu_superpanel = facts.banded ? 1 : 0;
     if (const char* sp = std::getenv("IDAHIP_LU_SUPERPANEL")) c->lu_superpanel = std::strtol(sp, nullptr, 10) != 0 ? 1 : 0;
     if (const char* sp = std::getenv("IDAHIP_LU_PERIOD")) {
         const int v = (int)std::strtol(sp, nullptr, 10);
@@ -184,9 +240,8 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     if (kind == IDAHIP_LINEAR_DENSE) {
         rc |= dalloc(c, &c->A, bnn); rc |= dalloc(c, &c->B, bnn); rc |= dalloc(c, &c->C, bn);
     }
-    if (kind == IDAHIP_LORENZ63) { c->nparam = 3; rc |= dalloc(c, &c->params, (size_t)batch * 3); }
-    if (kind == IDAHIP_HEAT1D) { c->nparam = 1; rc |= dalloc(c, &c->params, (size_t)batch); }
-    if (kind == IDAHIP_BRUSS1D) { c->nparam = BRUSS_NPARAM; rc |= dalloc(c, &c->params, (size_t)batch * BRUSS_NPARAM); }
+    c->nparam = facts.nparam;
+    rc |= dalloc(c, &c->params, (size_t)batch * facts.nparam);
     if (kind == IDAHIP_HOST_CALLBACK) rc |= dalloc(c, &c->cb_stage, 3 * bn);
     c->slot_cap = (size_t)batch * 256 + 4096;  // per call: <= ~110 B of scalars per system (predict) + list ids + results
     for (int i = 0; i < NSLOT && !rc; ++i) {
@@ -233,7 +288,8 @@ int idahip_create(idahip_ctx** out, int device, int n, int batch, idahip_problem
 int idahip_create_band(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, int ml, int mu) {
     if (!out) return -1;
     *out = nullptr;
-    if (kind != IDAHIP_HEAT1D && kind != IDAHIP_BRUSS1D && kind != IDAHIP_HOST_CALLBACK) {
+    const int band_min = ((int)kind >= 0 && (int)kind < KIND_COUNT) ? kind_facts(kind).band_min : 0;
+    if (!band_min && kind != IDAHIP_HOST_CALLBACK) {
         std::fprintf(stderr, "idahip_create_band: problem kind %d has no band form (IDAHIP_HEAT1D, IDAHIP_BRUSS1D or IDAHIP_HOST_CALLBACK)\n", (int)kind);
         return -2;
     }
@@ -241,7 +297,7 @@ int idahip_create_band(idahip_ctx** out, int device, int n, int batch, idahip_pr
         std::fprintf(stderr, "idahip_create_band: n = %d outside %d < n <= %d\n", n, TINY_N, LU_BIG_MAX_N);
         return -2;
     }
-    if (ml < 0 || mu < 0 || ml >= n || mu >= n || (kind == IDAHIP_HEAT1D && (ml < 1 || mu < 1)) || (kind == IDAHIP_BRUSS1D && (ml < 2 || mu < 2))) {
+    if (ml < 0 || mu < 0 || ml >= n || mu >= n || ml < band_min || mu < band_min) {
         std::fprintf(stderr, "idahip_create_band: bandwidths ml = %d, mu = %d outside 0 <= ml, mu < n (>= 1 for IDAHIP_HEAT1D, >= 2 for IDAHIP_BRUSS1D)\n", ml, mu);
         return -2;
     }
@@ -905,11 +961,11 @@ int launch_sys(idahip_ctx* c, const SysArgs& a, int nsys, double* jac_out, const
             }
             break;
         }
-        case IDAHIP_HEAT1D:
-            hipLaunchKernelGGL(heat_sys_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, a, (const double*)c->params);
-            break;
-        case IDAHIP_BRUSS1D:
-            hipLaunchKernelGGL(bruss_sys_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, a, (const double*)c->params);
+        default:
+            if (!with_stencil(c, [&](auto p) {
+                    hipLaunchKernelGGL(stencil_sys_kernel<decltype(p)>, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, a, (const double*)c->params);
+                }))
+                return no_kernel(c, "residual");
             break;
     }
     return post_launch(c, "nls_sys");
@@ -979,11 +1035,19 @@ int callback_dq_jac(idahip_ctx* c, const DqArgs& d0, const double* hTn, const in
 }
 
 // the band DQ kernel of the ctx's device kind (a band ctx, or the band preconditioner of a Krylov ctx)
-void launch_band_dq(idahip_ctx* c, const DqArgs& d, int nsys) {
-    int chunks = 1;
-    while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
-    if (c->kind == IDAHIP_BRUSS1D) hipLaunchKernelGGL(bruss_band_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
-    else hipLaunchKernelGGL(heat_band_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
+int launch_band_dq(idahip_ctx* c, const DqArgs& d, int nsys, const char* what) {
+    const int chunks = launch_chunks(nsys, 64);
+    if (!with_stencil(c, [&](auto p) {
+            hipLaunchKernelGGL(stencil_band_dq_jac_kernel<decltype(p)>, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks);
+        }))
+        return no_kernel(c, what);
+    return post_launch(c, what);
+}
+
+// the ctx's fields a DQ Jacobian reads, and the storage it is formed in (ld = 0: dense); the caller adds the list and the output
+void fill_dq_args(const idahip_ctx* c, DqArgs& d, int ml, int mu, int ld) {
+    d.yy = c->yy; d.yp = c->yp; d.ewt = c->ewt; d.rr = c->savres;
+    d.n = c->n; d.ml = ml; d.mu = mu; d.ld = ld;
 }
 
 // DQ Jacobians of the listed systems at the ctx's yy, yp, ewt and savres: into `out` by system id (the work matrices or the band
@@ -993,14 +1057,12 @@ int launch_dq_jac(idahip_ctx* c, double* out, bool compact, const int* d_idx, co
     const int n = c->n;
     if (nsys == 0) return 0;
     DqArgs d;
-    d.yy = c->yy; d.yp = c->yp; d.ewt = c->ewt; d.rr = c->savres;
+    fill_dq_args(c, d, c->band ? c->ml : 0, c->band ? c->mu : 0, c->band ? c->ldab : 0);
     d.idx = d_idx; d.cj = d_cj; d.hh = d_hh; d.skip = d_skip;
-    d.out = out; d.compact = compact ? 1 : 0; d.n = n;
-    d.ml = c->band ? c->ml : 0; d.mu = c->band ? c->mu : 0; d.ld = c->band ? c->ldab : 0;
+    d.out = out; d.compact = compact ? 1 : 0;
     if (c->kind == IDAHIP_HOST_CALLBACK) return callback_dq_jac(c, d, hTn, hIdx, nsys);
-    if (c->band) {  // (idahip_create_band: IDAHIP_HEAT1D and IDAHIP_BRUSS1D are the band ctx's device kinds)
-        launch_band_dq(c, d, nsys);
-        return post_launch(c, "band DQ jac");
+    if (c->band) {  // (idahip_create_band: the stencil problems are the band ctx's device kinds)
+        return launch_band_dq(c, d, nsys, "band DQ jac");
     }
     switch (c->kind) {
         case IDAHIP_ROBERTS:
@@ -1023,21 +1085,15 @@ int launch_dq_jac(idahip_ctx* c, double* out, bool compact, const int* d_idx, co
             }
             break;
         }
-        case IDAHIP_HEAT1D: {
-            int chunks = 1;
-            while ((long)nsys * chunks < 2048 && chunks < n) chunks *= 2;
-            hipLaunchKernelGGL(heat_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks,
-                               (!compact && out == c->jw) ? (const int*)c->lu_jwzero : nullptr);
+        default: {
+            const int chunks = launch_chunks(nsys, n);
+            const bool stencil = with_stencil(c, [&](auto p) {
+                hipLaunchKernelGGL(stencil_dq_jac_kernel<decltype(p)>, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks,
+                                   (!compact && out == c->jw) ? (const int*)c->lu_jwzero : nullptr);
+            });
+            if (!stencil) return fail(c, -2, "no DQ Jacobian for problem kind %d", (int)c->kind);
             break;
         }
-        case IDAHIP_BRUSS1D: {
-            int chunks = 1;
-            while ((long)nsys * chunks < 2048 && chunks < n) chunks *= 2;
-            hipLaunchKernelGGL(bruss_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, d, (const double*)c->params, chunks,
-                               (!compact && out == c->jw) ? (const int*)c->lu_jwzero : nullptr);
-            break;
-        }
-        default: return fail(c, -2, "no DQ Jacobian for problem kind %d", (int)c->kind);
     }
     return post_launch(c, "DQ jac");
 }
@@ -1053,14 +1109,12 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
     }
     if (c->band) {  // the band storage is the work matrix: the factorisation runs in place
         if (c->kind == IDAHIP_HOST_CALLBACK) return callback_jac(c, c->bab, d_idx, hTn, hCj, hIdx, nsys);
-        int chunks = 1;
-        while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
-        if (c->kind == IDAHIP_BRUSS1D)
-            hipLaunchKernelGGL(bruss_band_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, c->bab, n, c->ml, c->mu, (const double*)c->yy,
-                               (const double*)c->params, d_idx, d_cj, chunks, d_skip);
-        else
-            hipLaunchKernelGGL(heat_band_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, c->bab, n, c->ml, c->mu, (const double*)c->params, d_idx,
-                               d_cj, chunks, d_skip);
+        const int chunks = launch_chunks(nsys, 64);
+        if (!with_stencil(c, [&](auto p) {
+                hipLaunchKernelGGL(stencil_band_jac_kernel<decltype(p)>, dim3(nsys, chunks), dim3(256), 0, c->stream, c->bab, n, c->ml, c->mu,
+                                   (const double*)c->yy, (const double*)c->params, d_idx, d_cj, chunks, d_skip);
+            }))
+            return no_kernel(c, "band jac");
         return post_launch(c, "band jac");
     }
     switch (c->kind) {
@@ -1075,24 +1129,18 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
                                (const double*)c->params, 3, d_idx, d_cj, nsys);
             break;
         case IDAHIP_LINEAR_DENSE: {
-            int chunks = 1;
-            while ((long)nsys * chunks < 2048 && chunks < 64) chunks *= 2;
+            const int chunks = launch_chunks(nsys, 64);
             hipLaunchKernelGGL(linear_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, work, (const double*)c->A,
                                (const double*)c->B, nn, d_idx, d_cj, chunks);
             break;
         }
-        case IDAHIP_HEAT1D: {
-            int chunks = 1;
-            while ((long)nsys * chunks < 2048 && chunks < n) chunks *= 2;
-            hipLaunchKernelGGL(heat_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->params, d_idx, d_cj, chunks, d_skip,
-                               (work == c->jw) ? (const int*)c->lu_jwzero : nullptr);
-            break;
-        }
-        case IDAHIP_BRUSS1D: {
-            int chunks = 1;
-            while ((long)nsys * chunks < 2048 && chunks < n) chunks *= 2;
-            hipLaunchKernelGGL(bruss_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->yy, (const double*)c->params, d_idx,
-                               d_cj, chunks, d_skip, (work == c->jw) ? (const int*)c->lu_jwzero : nullptr);
+        default: {
+            const int chunks = launch_chunks(nsys, n);
+            if (!with_stencil(c, [&](auto p) {
+                    hipLaunchKernelGGL(stencil_jac_kernel<decltype(p)>, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->yy,
+                                       (const double*)c->params, d_idx, d_cj, chunks, d_skip, (work == c->jw) ? (const int*)c->lu_jwzero : nullptr);
+                }))
+                return no_kernel(c, "jac");
             break;
         }
     }
@@ -1378,7 +1426,7 @@ int idahip_kind(const idahip_ctx* c) { return c ? (int)c->kind : -1; }
 int idahip_create_krylov(idahip_ctx** out, int device, int n, int batch, idahip_problem kind, void* hip_stream, int maxl) {
     if (!out) return -1;
     *out = nullptr;
-    if (kind != IDAHIP_HEAT1D && kind != IDAHIP_BRUSS1D && kind != IDAHIP_LINEAR_DENSE && kind != IDAHIP_HOST_CALLBACK) {
+    if ((int)kind < 0 || (int)kind >= KIND_COUNT || !kind_facts(kind).krylov) {
         std::fprintf(stderr, "idahip_create_krylov: problem kind %d (IDAHIP_HEAT1D, IDAHIP_BRUSS1D, IDAHIP_LINEAR_DENSE or IDAHIP_HOST_CALLBACK)\n", (int)kind);
         return -2;
     }
@@ -1441,26 +1489,25 @@ int idahip_krylov_rounds_get_counters(const idahip_ctx* c, int64_t* hNpe, int64_
 
 namespace {
 
-// the solve of the listed systems, fused or split; a.idx / cj / tol / results point into `ap`'s slot, already uploaded
-int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* hIdx, int nsys) {
-    const int n = c->n;
+// the ctx's part of a solve's arguments; the caller adds the list, the tolerances and where the results go
+void fill_kry_args(const idahip_ctx* c, KryArgs& a) {
     a.yy = c->yy; a.yp = c->yp; a.ewt = c->ewt; a.rr = c->savres;
     a.V = c->kry_V; a.st = (idakry::Sys*)c->kry_st; a.stage = c->kry_stage;
     a.delta = c->delta; a.ee = c->ee;
-    a.n = n; a.maxl = c->kry_maxl;
+    a.n = c->n; a.maxl = c->kry_maxl;
     a.params = c->params; a.A = c->A; a.Bm = c->B; a.C = c->C;
+    a.pab = c->kry_pab; a.ppiv = (const long long*)c->kry_ppiv; a.pml = c->kry_pml; a.pmu = c->kry_pmu;
+}
+
+// the solve of the listed systems, fused or split; a.idx / cj / tol / results point into `ap`'s slot, already uploaded
+int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* hIdx, int nsys) {
+    const int n = c->n;
+    fill_kry_args(c, a);
     a.skip = nullptr;
     const bool prec = c->kry_prec != 0;
-    a.pab = c->kry_pab; a.ppiv = (const long long*)c->kry_ppiv; a.pml = c->kry_pml; a.pmu = c->kry_pmu;
     const dim3 grid(nsys), blk(KRY_T);
     if (c->kry_fused) {
-        const size_t shm = kry_lds_bytes(n, 3);
-        if (c->kind == IDAHIP_HEAT1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, true>), grid, blk, shm, c->stream, a);
-        else if (c->kind == IDAHIP_HEAT1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, false>), grid, blk, shm, c->stream, a);
-        else if (c->kind == IDAHIP_BRUSS1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_BRUSS1D, true>), grid, blk, shm, c->stream, a);
-        else if (c->kind == IDAHIP_BRUSS1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_BRUSS1D, false>), grid, blk, shm, c->stream, a);
-        else if (c->kind == IDAHIP_LINEAR_DENSE) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_LINEAR_DENSE, false>), grid, blk, shm, c->stream, a);
-        else return fail(c, -2, "no fused Krylov kernel for problem kind %d", (int)c->kind);
+        if (!launch_krylov_fused<false>(c, a, nsys)) return fail(c, -2, "no fused Krylov kernel for problem kind %d", (int)c->kind);
         return post_launch(c, "krylov_fused");
     }
     if (c->kind == IDAHIP_HOST_CALLBACK && !c->cb_res) return fail(c, -2, "IDAHIP_HOST_CALLBACK: idahip_set_host_residual has not been called");
@@ -1495,11 +1542,9 @@ int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* h
                     return fail(c, -7, "the user's residual function failed for system %d", hIdx[s]);
             }
             IDAHIP_HIP(c, hipMemcpyAsync(c->kry_stage, h, sizeof(double) * cnt, hipMemcpyHostToDevice, c->stream));
-        } else if (c->kind == IDAHIP_HEAT1D) {
-            hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_HEAT1D>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
-        } else if (c->kind == IDAHIP_BRUSS1D) {
-            hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_BRUSS1D>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
-        } else {
+        } else if (!with_stencil(c, [&](auto p) {
+                       hipLaunchKernelGGL(krylov_res_kernel<decltype(p)::KIND>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
+                   })) {
             hipLaunchKernelGGL(krylov_res_kernel<IDAHIP_LINEAR_DENSE>, grid, blk, 2 * sizeof(double) * n, c->stream, a);
         }
         if (prec) hipLaunchKernelGGL(krylov_step_kernel<true>, grid, blk, shm1, c->stream, a, l);
@@ -1636,17 +1681,15 @@ int idahip_krylov_psetup(idahip_ctx* c, const double* hTn, const double* hCj, co
     const double* d_hh = ap.in(hHh, nsys);
     if ((rc = ap.upload())) return rc;
     DqArgs d;
-    d.yy = c->yy; d.yp = c->yp; d.ewt = c->ewt; d.rr = c->savres;
+    fill_dq_args(c, d, c->kry_pml, c->kry_pmu, c->kry_pldab);
     d.idx = d_idx; d.cj = d_cj; d.hh = d_hh; d.skip = nullptr;
-    d.out = c->kry_pab; d.compact = 0; d.n = n;
-    d.ml = c->kry_pml; d.mu = c->kry_pmu; d.ld = c->kry_pldab;
+    d.out = c->kry_pab; d.compact = 0;
     {
         KTimer kt(c, IDAHIP_K_JAC, nsys);
         if (c->kind == IDAHIP_HOST_CALLBACK) {
             if ((rc = callback_dq_jac(c, d, hTn, hIdx, nsys))) return rc;
-        } else {  // (idahip_set_krylov_band_prec: IDAHIP_HEAT1D and IDAHIP_BRUSS1D are the device kinds)
-            launch_band_dq(c, d, nsys);
-            if ((rc = post_launch(c, "band DQ jac (preconditioner)"))) return rc;
+        } else {  // (idahip_set_krylov_band_prec: the stencil problems are the device kinds)
+            if ((rc = launch_band_dq(c, d, nsys, "band DQ jac (preconditioner)"))) return rc;
         }
     }
     {
@@ -2129,15 +2172,14 @@ int launch_ic_sys(idahip_ctx* c, const SysArgsIC& a, int nsys, const double* hTn
             else hipLaunchKernelGGL((linear_sys_kernel<1, false, SysArgsIC>), dim3(nsys), dim3(256), shm, c->stream, a, A, B, C, (double*)nullptr);
             break;
         }
-        case IDAHIP_HEAT1D: {
+        default: {
             const size_t shm = (a.lu ? 2 : 1) * sizeof(double) * n;
-            if (n % 2 == 0) hipLaunchKernelGGL(ic_heat_sys_kernel<2>, dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
-            else hipLaunchKernelGGL(ic_heat_sys_kernel<1>, dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
-            break;
-        }
-        case IDAHIP_BRUSS1D: {  // (n is even)
-            const size_t shm = (a.lu ? 2 : 1) * sizeof(double) * n;
-            hipLaunchKernelGGL(ic_bruss_sys_kernel, dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
+            if (!with_stencil(c, [&](auto p) {
+                    using P = decltype(p);
+                    if (n % 2 == 0) hipLaunchKernelGGL((ic_stencil_sys_kernel<P, 2>), dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
+                    else hipLaunchKernelGGL((ic_stencil_sys_kernel<P, 1>), dim3(nsys), dim3(256), shm, c->stream, a, (const double*)c->params);
+                }))
+                return no_kernel(c, "IC residual");
             break;
         }
     }
@@ -2561,37 +2603,24 @@ static int krylov_round_newton(idahip_ctx* c, const RoundArgs& a, const KryRound
             hipLaunchKernelGGL(dq_round_prep_kernel, per_sys, blk, 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh, batch,
                                (long)std::min(c->kry_pml + c->kry_pmu + 1, n));
             DqArgs d;
-            d.yy = c->yy; d.yp = c->yp; d.ewt = c->ewt; d.rr = c->savres;
+            fill_dq_args(c, d, c->kry_pml, c->kry_pmu, c->kry_pldab);
             d.idx = a.ident; d.cj = a.cj; d.hh = c->dq_hh; d.skip = a.skipL;
-            d.out = c->kry_pab; d.compact = 0; d.n = n;
-            d.ml = c->kry_pml; d.mu = c->kry_pmu; d.ld = c->kry_pldab;
-            launch_band_dq(c, d, batch);
-            if ((rc = post_launch(c, "band DQ jac (preconditioner)"))) return rc;
+            d.out = c->kry_pab; d.compact = 0;
+            if ((rc = launch_band_dq(c, d, batch, "band DQ jac (preconditioner)"))) return rc;
         }
         KTimer kt(c, IDAHIP_K_LU, 0);
         if ((rc = band_factor(c, c->kry_pab, (long)c->kry_pldab * n, c->kry_ppiv, n, c->kry_pml, c->kry_pmu, a.lu_list, batch, a.lu_cnt))) return rc;
     }
     hipLaunchKernelGGL(round_krylov_ctl_kernel, per_sys, blk, 0, c->stream, a, kr, 0);
     KryArgs ka{};
-    ka.yy = c->yy; ka.yp = c->yp; ka.ewt = c->ewt; ka.rr = c->savres;
-    ka.V = c->kry_V; ka.st = (idakry::Sys*)c->kry_st; ka.stage = c->kry_stage;
+    fill_kry_args(c, ka);
     ka.idx = a.ident; ka.cj = a.cj; ka.tol = kr.tol; ka.skip = a.skipI;
-    ka.newton = 1; ka.delta = c->delta; ka.ee = c->ee;
+    ka.newton = 1;
     ka.nli = c->kry_rint; ka.flag = c->kry_rint + batch; ka.resnorm = c->kry_rres; ka.nrm = a.nrm_out;
-    ka.n = n; ka.maxl = c->kry_maxl;
-    ka.params = c->params; ka.A = c->A; ka.Bm = c->B; ka.C = c->C;
-    ka.pab = c->kry_pab; ka.ppiv = (const long long*)c->kry_ppiv; ka.pml = c->kry_pml; ka.pmu = c->kry_pmu;
-    const bool prec = c->kry_prec != 0;
-    const size_t shm = kry_lds_bytes(n, 3);
     for (int m = 1; m <= idactl::MAXNLSIT; ++m) {
         {
             KTimer kt(c, IDAHIP_K_NEWTON_ITER, 0);
-            const dim3 grid(batch), kblk(KRY_T);
-            if (c->kind == IDAHIP_HEAT1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, true, true>), grid, kblk, shm, c->stream, ka);
-            else if (c->kind == IDAHIP_HEAT1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_HEAT1D, false, true>), grid, kblk, shm, c->stream, ka);
-            else if (c->kind == IDAHIP_BRUSS1D && prec) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_BRUSS1D, true, true>), grid, kblk, shm, c->stream, ka);
-            else if (c->kind == IDAHIP_BRUSS1D) hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_BRUSS1D, false, true>), grid, kblk, shm, c->stream, ka);
-            else hipLaunchKernelGGL((krylov_fused_kernel<IDAHIP_LINEAR_DENSE, false, true>), grid, kblk, shm, c->stream, ka);
+            if (!launch_krylov_fused<true>(c, ka, batch)) return fail(c, -2, "no fused Krylov kernel for problem kind %d", (int)c->kind);
             if ((rc = post_launch(c, "krylov_fused (round)"))) return rc;
         }
         hipLaunchKernelGGL(round_krylov_ctl_kernel, per_sys, blk, 0, c->stream, a, kr, m);
@@ -2611,8 +2640,9 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     if (!c) return -1;
     if (!hSys || !call || !hRoundsDone || !hAcc || !rounds_run || !call->touts || call->ntout < 1) return fail(c, -2, "null argument");
     if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
-    const bool lin = c->kind == IDAHIP_LINEAR_DENSE && c->n <= LU_BIG_MAX_N;
-    const bool banded = (c->kind == IDAHIP_HEAT1D || c->kind == IDAHIP_BRUSS1D) && c->n <= LU_BIG_MAX_N;
+    const KindFacts& facts = kind_facts(c->kind);
+    const bool lin = c->kind == IDAHIP_LINEAR_DENSE && facts.rounds && c->n <= LU_BIG_MAX_N;
+    const bool banded = facts.rounds && facts.banded && c->n <= LU_BIG_MAX_N;
     const bool kry = c->krylov != 0;  // (idahip_set_krylov_rounds is on: no LU bounds n, the LU variant does not matter)
     if (kry && (c->n <= TINY_N || !(lin || banded) || (c->kry_prec && c->kind == IDAHIP_LINEAR_DENSE)))
         return fail(c, -2, "the device lock-step rounds of a Krylov ctx take linear dense (no preconditioner), heat and Brusselator problems with %d < n <= %d", TINY_N, LU_BIG_MAX_N);

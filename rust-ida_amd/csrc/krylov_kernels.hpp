@@ -66,7 +66,7 @@ struct KryArgs {
     double* nrm;        // [nsys] newton: sum_i (delta_i ewt_i)^2 left to right, 0 for a flag other than SUCCESS
     int* done;          // [nsys] split path: the loop of this system has ended
     int n, maxl;
-    const double* params;  // heat: [batch]; Brusselator: [batch][5]
+    const double* params;  // a stencil problem's [batch][NPARAM]
     const double *A, *Bm, *C;  // linear dense
     // band preconditioner (the kernels instantiated with PREC only): factors [batch][(2 pml + pmu + 1) * n], pivots [batch][n]
     const double* pab;
@@ -203,12 +203,8 @@ __device__ __forceinline__ void kry_point(const KryArgs& a, int b, const double*
     }
 }
 
-// row i of the residual at (y', yp'): heat_sys_kernel's expression / linear_sys_kernel's two chains over ascending columns (the
-// Brusselator's row is bruss_row_perturbed itself)
-__device__ __forceinline__ double kry_res_heat(const double* y, const double* ypv, int n, int i, double coef) {
-    if (i == 0 || i == n - 1) return y[i];
-    return ypv[i] - coef * ((y[i - 1] - 2.0 * y[i]) + y[i + 1]);
-}
+// row i of the linear dense residual at (y', yp'): linear_sys_kernel's two chains over ascending columns (a stencil problem's row
+// is its description's P::row itself, stencil_problems.hpp)
 __device__ __forceinline__ double kry_res_linear(const double* __restrict__ Ab, const double* __restrict__ Bb, double ci, const double* y,
                                                  const double* ypv, int n, int i) {
     double ra = 0.0, rb = 0.0;
@@ -237,12 +233,10 @@ __device__ __forceinline__ double kry_res_linear(const double* __restrict__ Ab, 
 template <int KIND, class Put>
 __device__ __forceinline__ void kry_residual(const KryArgs& a, int b, const double* y, const double* ypv, Put put) {
     const int n = a.n;
-    if constexpr (KIND == IDAHIP_HEAT1D) {
-        const double coef = a.params[b];
-        for (int i = threadIdx.x; i < n; i += KRY_T) put(i, kry_res_heat(y, ypv, n, i, coef));
-    } else if constexpr (KIND == IDAHIP_BRUSS1D) {
-        const double* __restrict__ prm = a.params + (long)b * BRUSS_NPARAM;
-        for (int i = threadIdx.x; i < n; i += KRY_T) put(i, bruss_row_perturbed(n, i, ypv[i], prm, [&](int k) { return y[k]; }));
+    using P = typename stencil_of<KIND>::type;
+    if constexpr (!std::is_void_v<P>) {
+        const double* __restrict__ prm = a.params + (long)b * P::NPARAM;
+        for (int i = threadIdx.x; i < n; i += KRY_T) put(i, P::row(n, i, ypv[i], prm, [&](int k) { return y[k]; }));
     } else {
         const double* __restrict__ Ab = a.A + (long)b * n * n;
         const double* __restrict__ Bb = a.Bm + (long)b * n * n;

@@ -50,7 +50,7 @@ struct LuWs {
     unsigned char* zmap;  // null, or [batch][64][64] (n >= 2048): zmap[K][I] = 1 when block (rows I, columns K) of the factors may be non-zero
     unsigned char* dirty; // null, or [batch][64][64] with zmap: dirty[K][I] = 1 once block (rows I, columns K) of `out` has held a value with non-zero bits; never reset
     int* jwzero;       // null, or [batch] (with dirty, work == the ctx's work matrix, every super-panel 64 columns wide): 1 = the factorisation has left the
-                       // work matrix all +0.0 (lu_finalize_kernel clears what it reads and the pivot rows' entries right of their super-panel); heat_jac_kernel
+                       // work matrix all +0.0 (lu_finalize_kernel clears what it reads and the pivot rows' entries right of their super-panel); stencil_jac_kernel
                        // then writes the band only. lu_init_kernel resets it, lu_finalize_kernel sets it.
     int* redo;         // [batch]   lu_wavepanel_kernel: 0 | 1 + first 8-column block of the super-panel left to its SLOW launch
     double* l11;       // [batch][L11_STRIDE] transposed L11: l11[kk*l11ld + k] = multiplier of the k-th pivot row for column kk

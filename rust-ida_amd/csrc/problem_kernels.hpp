@@ -8,10 +8,11 @@
 //   LinearDense  <- SURVEY.md 8(d) config 3: F = A y' + B y - c with the summation order fixed in
 //                   oracle/problems.hpp (two left-to-right chains over ascending column j) -- which is exactly
 //                   what a thread-per-row, column-sweeping GPU kernel computes, with coalesced 16-byte loads.
-//   Heat1D       <- SURVEY.md 8(d) config 4.
+//   Heat1D       <- SURVEY.md 8(d) config 4; Bruss1D <- include/ida_hip.h (both described in stencil_problems.hpp).
 #pragma once
 #include "common.hpp"
 #include "solve_kernels.hpp"
+#include "stencil_problems.hpp"
 
 namespace idahip {
 
@@ -278,9 +279,14 @@ __global__ __launch_bounds__(256) void linear_jac_kernel(double* __restrict__ ma
     }
 }
 
-// ------------------------------------------------------------------------------------------------ heat 1-D
-template <int VEC, class ARGS>
-__device__ __forceinline__ void heat_sys_body(ARGS a, const double* __restrict__ params) {
+// ------------------------------------------------------------------------------------------------ banded stencil problems
+// Heat1D and Bruss1D (stencil_problems.hpp): one set of kernels over the description P -- P::row is the residual's row, P::jac_entry
+// the Jacobian's entry, P::HALF_BW the band, P::NPARAM the parameters' stride.
+
+// One workgroup per listed system, y staged in LDS (row r reads y at r-HALF_BW .. r+HALF_BW and its own y'). VEC: the rows a lane
+// takes in the IC front end's in-launch solve (n % 2 == 0 ? 2 : 1).
+template <class P, int VEC, class ARGS>
+__device__ __forceinline__ void stencil_sys_body(ARGS a, const double* __restrict__ params) {
     extern __shared__ __align__(16) double sm[];
     const int n = a.n;
     double* syy = sm;
@@ -288,7 +294,7 @@ __device__ __forceinline__ void heat_sys_body(ARGS a, const double* __restrict__
     const int b = a.idx[blockIdx.x];
     const long vb = (long)b * n;
     const double cj = a.cj[blockIdx.x];
-    const double coef = params[b];
+    const double* __restrict__ prm = params + (long)b * P::NPARAM;
     for (int i = threadIdx.x; i < n; i += 256) {
         double y, yp;
         sys_point(a, (int)blockIdx.x, vb + i, i, cj, y, yp);
@@ -296,9 +302,7 @@ __device__ __forceinline__ void heat_sys_body(ARGS a, const double* __restrict__
     }
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += 256) {
-        double r;
-        if (i == 0 || i == n - 1) r = syy[i];
-        else r = a.yp[vb + i] - coef * ((syy[i - 1] - 2.0 * syy[i]) + syy[i + 1]);
+        const double r = P::row(n, i, a.yp[vb + i], prm, [&](int k) { return syy[k]; });
         a.delta[vb + i] = r;
         a.savres[vb + i] = r;
     }
@@ -309,159 +313,46 @@ __device__ __forceinline__ void heat_sys_body(ARGS a, const double* __restrict__
         }
     }
 }
-__global__ __launch_bounds__(256) void heat_sys_kernel(SysArgs a, const double* __restrict__ params) { heat_sys_body<1>(a, params); }
+template <class P>
+__global__ __launch_bounds__(256) void stencil_sys_kernel(SysArgs a, const double* __restrict__ params) { stencil_sys_body<P, 1>(a, params); }
 
-__global__ __launch_bounds__(256) void heat_jac_kernel(double* __restrict__ mats, int n, const double* __restrict__ params,
-                                                       const int* __restrict__ idx, const double* __restrict__ cjs, int chunks,
-                                                       const int* __restrict__ skip, const int* __restrict__ zeroed) {
-    if (skip && skip[blockIdx.x] != 0) return;  // (the device lock-step stepper's per-system flags)
+// The analytic Jacobian into the dense work matrix: (system, column chunk). skip: the device lock-step stepper's per-system flags.
+// The entries are taken at the system's current yy (heat's do not depend on it).
+template <class P>
+__global__ __launch_bounds__(256) void stencil_jac_kernel(double* __restrict__ mats, int n, const double* __restrict__ yy,
+                                                          const double* __restrict__ params, const int* __restrict__ idx,
+                                                          const double* __restrict__ cjs, int chunks, const int* __restrict__ skip,
+                                                          const int* __restrict__ zeroed) {
+    if (skip && skip[blockIdx.x] != 0) return;
     const int b = idx[blockIdx.x];
     const double cj = cjs[blockIdx.x];
-    const double coef = params[b];
+    const double* __restrict__ prm = params + (long)b * P::NPARAM;
+    const double* __restrict__ y = yy + (long)b * n;
     double* __restrict__ J = mats + (long)b * n * n;
     const int per = (n + chunks - 1) / chunks;  // columns per block
     const int jbeg = blockIdx.y * per;
     const int jend = (jbeg + per < n) ? jbeg + per : n;
     if (zeroed && zeroed[b] != 0) {
         // the last factorisation has left this system's matrix all +0.0 (LuWs::jwzero): J <- 0 (ida_ls.rs:254) is in place already, the
-        // band is all there is to write -- 3 entries of a column instead of n
-        for (int j = jbeg + threadIdx.x; j < jend; j += 256) {
-            for (int i = (j > 0 ? j - 1 : 0); i <= j + 1 && i < n; ++i) {
-                double v = 0.0;
-                if (i == 0 || i == n - 1) {
-                    v = (j == i) ? 1.0 : 0.0;
-                } else {
-                    if (j == i) v = cj + 2.0 * coef;
-                    else v = -coef;
-                }
-                J[(long)j * n + i] = v;
-            }
-        }
-        return;
-    }
-    for (int j = jbeg; j < jend; ++j) {
-        for (int i = threadIdx.x; i < n; i += 256) {
-            double v = 0.0;
-            if (i == 0 || i == n - 1) {
-                v = (j == i) ? 1.0 : 0.0;
-            } else {
-                if (j == i) v = cj + 2.0 * coef;
-                else if (j == i - 1 || j == i + 1) v = -coef;
-            }
-            J[(long)j * n + i] = v;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ Brusselator 1-D
-// n = 2m, y[2i] = u_i, y[2i+1] = v_i; prm = [a, b, d, ub, vb] of the system (include/ida_hip.h has the definition). Every line
-// below is one IEEE operation in the header's order (-ffp-contract=off).
-constexpr int BRUSS_NPARAM = 5;
-
-// Row r of the residual. py(k) is component k of the point -- the state itself, or a perturbed one (dq_kernels.hpp) -- and ypr
-// the point's y'_r. The residual kernel, the DQ Jacobians and the Krylov residual all evaluate this one expression.
-template <class PY>
-__device__ __forceinline__ double bruss_row_perturbed(int n, int r, double ypr, const double* __restrict__ prm, PY py) {
-    const int i = r >> 1, m = n >> 1;
-    if (i == 0 || i == m - 1) return py(r) - prm[3 + (r & 1)];
-    const double a = prm[0], b = prm[1], d = prm[2];
-    const double u = py(2 * i), v = py(2 * i + 1);
-    const double w = (u * u) * v;
-    if ((r & 1) == 0) {
-        const double lu = (py(r - 2) - 2.0 * u) + py(r + 2);
-        return ypr - (((a - (b + 1.0) * u) + w) + d * lu);
-    }
-    const double lv = (py(r - 2) - 2.0 * v) + py(r + 2);
-    return ypr - ((b * u - w) + d * lv);
-}
-
-// J(r, c) = dF_r/dy_c + cj dF_r/dy'_c at y, for |r - c| <= 2 (every other entry is +0.0, and so are the in-band ones no term reaches)
-__device__ __forceinline__ double bruss_jac_entry(const double* __restrict__ y, int n, int r, int c, double cj, const double* __restrict__ prm) {
-    const int i = r >> 1, m = n >> 1;
-    if (i == 0 || i == m - 1) return r == c ? 1.0 : 0.0;
-    const double b = prm[1], d = prm[2];
-    const int off = c - r;
-    if (off == -2 || off == 2) return -d;
-    const double u = y[2 * i], v = y[2 * i + 1];
-    if ((r & 1) == 0) {
-        if (off == 0) {
-            const double t2 = (2.0 * u) * v;
-            return cj - ((t2 - (b + 1.0)) - 2.0 * d);
-        }
-        if (off == 1) return -(u * u);
-        return 0.0;
-    }
-    if (off == -1) {
-        const double t2 = (2.0 * u) * v;
-        return -(b - t2);
-    }
-    if (off == 0) return cj + (u * u + 2.0 * d);
-    return 0.0;
-}
-
-// heat_sys_body's shape: one workgroup per listed system, y staged in LDS (row r reads y at r-2 .. r+2 and its own y')
-template <class ARGS>
-__device__ __forceinline__ void bruss_sys_body(ARGS a, const double* __restrict__ params) {
-    extern __shared__ __align__(16) double sm[];
-    const int n = a.n;
-    double* syy = sm;
-    if (a.skip && a.skip[blockIdx.x] != 0) return;
-    const int b = a.idx[blockIdx.x];
-    const long vb = (long)b * n;
-    const double cj = a.cj[blockIdx.x];
-    const double* __restrict__ prm = params + (long)b * BRUSS_NPARAM;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        double y, yp;
-        sys_point(a, (int)blockIdx.x, vb + i, i, cj, y, yp);
-        syy[i] = y;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const double r = bruss_row_perturbed(n, i, a.yp[vb + i], prm, [&](int k) { return syy[k]; });
-        a.delta[vb + i] = r;
-        a.savres[vb + i] = r;
-    }
-    if constexpr (ARGS::IC) {
-        if (a.lu) {  // (dynamic LDS: 2 n doubles; n is even, so the solve takes two rows per lane)
-            __syncthreads();
-            ic_solve_body<2>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out);
-        }
-    }
-}
-__global__ __launch_bounds__(256) void bruss_sys_kernel(SysArgs a, const double* __restrict__ params) { bruss_sys_body(a, params); }
-
-// heat_jac_kernel's launch shape and contracts (skip, zeroed); the entries depend on the system's current yy
-__global__ __launch_bounds__(256) void bruss_jac_kernel(double* __restrict__ mats, int n, const double* __restrict__ yy,
-                                                        const double* __restrict__ params, const int* __restrict__ idx,
-                                                        const double* __restrict__ cjs, int chunks, const int* __restrict__ skip,
-                                                        const int* __restrict__ zeroed) {
-    if (skip && skip[blockIdx.x] != 0) return;
-    const int b = idx[blockIdx.x];
-    const double cj = cjs[blockIdx.x];
-    const double* __restrict__ prm = params + (long)b * BRUSS_NPARAM;
-    const double* __restrict__ y = yy + (long)b * n;
-    double* __restrict__ J = mats + (long)b * n * n;
-    const int per = (n + chunks - 1) / chunks;  // columns per block
-    const int jbeg = blockIdx.y * per;
-    const int jend = (jbeg + per < n) ? jbeg + per : n;
-    if (zeroed && zeroed[b] != 0) {  // the matrix is all +0.0 already (LuWs::jwzero): the five in-band entries of a column
+        // band is all there is to write -- 2 HALF_BW + 1 entries of a column instead of n
         for (int j = jbeg + threadIdx.x; j < jend; j += 256)
-            for (int i = (j > 2 ? j - 2 : 0); i <= j + 2 && i < n; ++i) J[(long)j * n + i] = bruss_jac_entry(y, n, i, j, cj, prm);
+            for (int i = (j > P::HALF_BW ? j - P::HALF_BW : 0); i <= j + P::HALF_BW && i < n; ++i) J[(long)j * n + i] = P::jac_entry(y, n, i, j, cj, prm);
         return;
     }
     for (int j = jbeg; j < jend; ++j)
-        for (int i = threadIdx.x; i < n; i += 256) J[(long)j * n + i] = (i >= j - 2 && i <= j + 2) ? bruss_jac_entry(y, n, i, j, cj, prm) : 0.0;
+        for (int i = threadIdx.x; i < n; i += 256) J[(long)j * n + i] = stencil_in_band<P>(i, j) ? P::jac_entry(y, n, i, j, cj, prm) : 0.0;
 }
 
-// The same entries into LAPACK band storage (heat_band_jac_kernel's launch shape, band_kernels.hpp); the rest of the column (band
-// and fill rows) is written +0.0. Needs ml >= 2 and mu >= 2.
-__global__ __launch_bounds__(256) void bruss_band_jac_kernel(double* __restrict__ ab, int n, int ml, int mu, const double* __restrict__ yy,
-                                                             const double* __restrict__ params, const int* __restrict__ idx,
-                                                             const double* __restrict__ cjs, int chunks, const int* __restrict__ skip) {
+// The same entries into LAPACK band storage (band_kernels.hpp has the layout): (system, chunk of the ld x n entries); the rest of
+// the column (band and fill rows) is written +0.0 (J <- 0 first, ida_ls.rs:254). Needs ml >= HALF_BW and mu >= HALF_BW.
+template <class P>
+__global__ __launch_bounds__(256) void stencil_band_jac_kernel(double* __restrict__ ab, int n, int ml, int mu, const double* __restrict__ yy,
+                                                               const double* __restrict__ params, const int* __restrict__ idx,
+                                                               const double* __restrict__ cjs, int chunks, const int* __restrict__ skip) {
     if (skip && skip[blockIdx.x] != 0) return;
     const int b = idx[blockIdx.x];
     const double cj = cjs[blockIdx.x];
-    const double* __restrict__ prm = params + (long)b * BRUSS_NPARAM;
+    const double* __restrict__ prm = params + (long)b * P::NPARAM;
     const double* __restrict__ y = yy + (long)b * n;
     const int kv = ml + mu, ld = 2 * ml + mu + 1;
     double* __restrict__ J = ab + (long)b * ld * n;
@@ -472,7 +363,7 @@ __global__ __launch_bounds__(256) void bruss_band_jac_kernel(double* __restrict_
     for (long e = ebeg + threadIdx.x; e < eend; e += 256) {
         const int j = (int)(e / ld);
         const int i = j + (int)(e - (long)j * ld) - kv;
-        J[e] = (i >= 0 && i < n && i >= j - 2 && i <= j + 2) ? bruss_jac_entry(y, n, i, j, cj, prm) : 0.0;
+        J[e] = (i >= 0 && i < n && stencil_in_band<P>(i, j)) ? P::jac_entry(y, n, i, j, cj, prm) : 0.0;
     }
 }
 

@@ -75,7 +75,7 @@ def test_heat_through_band_host_callbacks(n):
     p = problems.heat1d(n=n, batch=B)
     coef = p["params"][:, 0]
 
-    def res(sys, t, y, yp):  # heat_sys_kernel's operation order
+    def res(sys, t, y, yp):  # Heat1D::row's operation order (stencil_sys_kernel)
         f = np.empty(n)
         f[0] = y[0]
         f[1:-1] = yp[1:-1] - coef[sys] * ((y[:-2] - 2.0 * y[1:-1]) + y[2:])

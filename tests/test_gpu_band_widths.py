@@ -297,7 +297,7 @@ def test_newton_iter_on_a_band_ctx(lin):
 # ------------------------------------------------------------------------------------------------ (b) the heat band Jacobian kernel
 @pytest.mark.parametrize("n,ml,mu", HEAT_WIDTHS, ids=lambda v: str(v))
 def test_heat_band_jacobian_at_every_width(n, ml, mu):
-    """heat_band_jac_kernel writes the whole ldab x n block of a listed system (three entries per column, +0.0 elsewhere, fill rows
+    """stencil_band_jac_kernel<Heat1D> writes the whole ldab x n block of a listed system (three entries per column, +0.0 elsewhere, fill rows
     included) over whatever the last factorisation left there: three setups in a row with different cj, list lengths B, 3 and 1."""
     case = HeatCase(n, ml, mu, B=4)
     for k, (idx, how) in enumerate((([2, 0, 3, 1], "lsetup"), ([3, 0, 2], "sys_setup"), ([1], "lsetup"), ([0, 1, 3], "lsetup"))):
@@ -323,7 +323,7 @@ def test_heat_band_jacobian_at_every_width(n, ml, mu):
 @pytest.mark.parametrize("ml,mu", [(1, 1), (2, 3), (16, 16)])
 def test_newton_iter2_on_a_heat_band_ctx(ml, mu):
     """The first two Newton iterations with their convergence tests on the device. Systems that end at m = 0 are skipped by the
-    second residual and the second pass (heat_sys_kernel's and band_newton_iter_kernel's `skip`): their delta and ee stay."""
+    second residual and the second pass (stencil_sys_kernel's and band_newton_iter_kernel's `skip`): their delta and ee stay."""
     n, B = 257, 16
     case = HeatCase(n, ml, mu, B=B)
     ids = np.arange(B, dtype=np.int32)[::-1].copy()
