@@ -1,5 +1,6 @@
 // libidahip.so -- implementation of include/ida_hip.h (single translation unit; gfx950; -ffp-contract=off).
 #include "common.hpp"
+#include "list_call.hpp"
 #include "lu_kernels.hpp"
 #include "lu_driver.hpp"
 #include "problem_kernels.hpp"
@@ -79,25 +80,6 @@ bool launch_krylov_fused(idahip_ctx* c, const KryArgs& a, int nsys) {
     return true;
 }
 
-int check_list(idahip_ctx* c, const int32_t* hIdx, int nsys) {
-    if (!c) return -1;
-    if (nsys < 0 || nsys > c->batch) return fail(c, -2, "nsys = %d out of range (batch = %d)", nsys, c->batch);
-    if (nsys > 0 && !hIdx) return fail(c, -2, "null system list");
-    for (int s = 0; s < nsys; ++s)
-        if (hIdx[s] < 0 || hIdx[s] >= c->batch) return fail(c, -2, "system id %d out of range at list position %d", hIdx[s], s);
-    // no id twice: two workgroups would factor one matrix in place, or update one system's vectors, at the same time
-    uint64_t* seen = c->list_seen.data();
-    int dup = -1;
-    for (int s = 0; s < nsys && dup < 0; ++s) {
-        const uint64_t bit = 1ull << (hIdx[s] & 63);
-        if (seen[hIdx[s] >> 6] & bit) dup = s;
-        seen[hIdx[s] >> 6] |= bit;
-    }
-    for (int s = 0; s < (dup < 0 ? nsys : dup); ++s) seen[hIdx[s] >> 6] = 0;  // leave the map clear for the next call
-    if (dup >= 0) return fail(c, -2, "system id %d listed twice (again at list position %d)", hIdx[dup], dup);
-    return 0;
-}
-
 double* field_ptr(idahip_ctx* c, idahip_field f) {
     switch (f) {
         case IDAHIP_F_YY: return c->yy;
@@ -129,12 +111,6 @@ VecState vec_state(idahip_ctx* c) {
 // C IDA's IDA_MISSING_ID: the masked norms (idahip_set_suppress_alg) need the id vector; nothing is launched without it
 int missing_id(idahip_ctx* c, const char* who) {
     if (c->suppress_alg && c->h_id.empty()) return fail(c, -2, "%s: suppress_alg is on and no id vector is set (idahip_set_id)", who);
-    return 0;
-}
-
-int post_launch(idahip_ctx* c, const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, -101, "launch of %s failed: %s", what, hipGetErrorString(e));
     return 0;
 }
 
@@ -522,7 +498,7 @@ int idahip_set_suppress_alg(idahip_ctx* c, int on) {
 int idahip_suppress_alg(const idahip_ctx* c) { return c ? (c->suppress_alg ? 1 : 0) : -1; }
 
 int idahip_set_constraints(idahip_ctx* c, const double* hC) {
-    if (c && c->krylov) return fail(c, -2, "idahip_set_constraints on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
+    if (int rc = refuse_krylov(c, "idahip_set_constraints")) return rc;
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (!hC) {
@@ -568,7 +544,7 @@ int idahip_set_linear_dense(idahip_ctx* c, int first, int count, const double* h
 }
 
 int idahip_set_host_problem(idahip_ctx* c, idahip_res_fn res, idahip_jac_fn jac, void* user) {
-    if (c && c->krylov) return fail(c, -2, "idahip_set_host_problem on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
+    if (int rc = refuse_krylov(c, "idahip_set_host_problem")) return rc;
     if (!c || !res || !jac) return -1;
     if (c->kind != IDAHIP_HOST_CALLBACK) return fail(c, -2, "not an IDAHIP_HOST_CALLBACK ctx");
     if (c->band) return fail(c, -2, "a band ctx takes a band Jacobian: idahip_set_host_band_problem");
@@ -594,7 +570,7 @@ int idahip_set_host_residual(idahip_ctx* c, idahip_res_fn res, void* user) {
 }
 
 int idahip_set_host_band_problem(idahip_ctx* c, idahip_res_fn res, idahip_band_jac_fn bjac, void* user) {
-    if (c && c->krylov) return fail(c, -2, "idahip_set_host_band_problem on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
+    if (int rc = refuse_krylov(c, "idahip_set_host_band_problem")) return rc;
     if (!c || !res || !bjac) return -1;
     if (c->kind != IDAHIP_HOST_CALLBACK) return fail(c, -2, "not an IDAHIP_HOST_CALLBACK ctx");
     if (!c->band) return fail(c, -2, "a dense ctx takes a dense Jacobian: idahip_set_host_problem");
@@ -629,7 +605,7 @@ int idahip_download(idahip_ctx* c, idahip_field f, int first, int count, double*
 }
 
 int idahip_download_lu(idahip_ctx* c, int sys, double* hLU, int64_t* hPiv) {
-    if (c && c->krylov) return fail(c, -2, "idahip_download_lu on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
+    if (int rc = refuse_krylov(c, "idahip_download_lu")) return rc;
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
@@ -642,7 +618,7 @@ int idahip_download_lu(idahip_ctx* c, int sys, double* hLU, int64_t* hPiv) {
 }
 
 int idahip_download_lu_band(idahip_ctx* c, int sys, double* hAB, int64_t* hPiv) {
-    if (c && c->krylov) return fail(c, -2, "idahip_download_lu_band on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
+    if (int rc = refuse_krylov(c, "idahip_download_lu_band")) return rc;
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
@@ -684,181 +660,108 @@ int idahip_memcpy_d2h(idahip_ctx* c, void* h, const void* d, size_t bytes) {
 
 // ------------------------------------------------------------------------------------------------ LSolver
 int idahip_ls_setup(idahip_ctx* c, double* dA, int64_t* dPiv, int32_t* hInfo, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!dA || !dPiv || !hInfo) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({dA, dPiv, hInfo})) return f.rc;
     if (c->band) return fail(c, -2, "idahip_ls_setup on a band ctx (no dense work matrices): idahip_ls_setup_band");
     if (c->krylov) return fail(c, -2, "idahip_ls_setup on a Krylov ctx (idahip_create_krylov): it holds no dense work matrices");
-    if (nsys == 0) return 0;
+    if (!f.stage()) return f.rc;
     const int n = c->n;
     const long nn = (long)n * n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_LU, nsys);
-        if (n <= TINY_N) {
-            rc = lu_factor_batched(c, dA, nn, dA, nn, (long long*)dPiv, n, nullptr, d_idx, nsys);
-        } else {
-            // factor in place in dA (physical row order), scatter rows into the ctx work matrix, copy back
-            rc = lu_factor_batched(c, dA, nn, c->jw, nn, (long long*)dPiv, n, nullptr, d_idx, nsys);
-            if (!rc) {
-                for (int s = 0; s < nsys; ++s)  // listed systems only; info != 0 systems keep their partial factors
-                    (void)hipMemcpyAsync(dA + hIdx[s] * nn, c->jw + hIdx[s] * nn, sizeof(double) * nn, hipMemcpyDeviceToDevice, c->stream);
-            }
-        }
-        if (rc) return rc;
-        if ((rc = post_launch(c, "lu"))) return rc;
-    }
-    std::vector<int32_t> info(c->batch);
-    IDAHIP_HIP(c, hipMemcpyAsync(info.data(), c->lu_info, sizeof(int32_t) * c->batch, hipMemcpyDeviceToHost, c->stream));
-    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
-    int any = 0;
-    for (int s = 0; s < nsys; ++s) {
-        hInfo[s] = info[hIdx[s]];
-        any |= hInfo[s] != 0;
-    }
-    return any ? 1 : 0;
+    f.launch(IDAHIP_K_LU, nsys, "lu", [&] {
+        if (n <= TINY_N) return lu_factor_batched(c, dA, nn, dA, nn, (long long*)dPiv, n, nullptr, f.idx, nsys);
+        // factor in place in dA (physical row order), scatter rows into the ctx work matrix, copy back
+        const int rc = lu_factor_batched(c, dA, nn, c->jw, nn, (long long*)dPiv, n, nullptr, f.idx, nsys);
+        for (int s = 0; s < nsys && !rc; ++s)  // listed systems only; info != 0 systems keep their partial factors
+            (void)hipMemcpyAsync(dA + hIdx[s] * nn, c->jw + hIdx[s] * nn, sizeof(double) * nn, hipMemcpyDeviceToDevice, c->stream);
+        return rc;
+    });
+    return f.rc ? f.rc : report_info(c, hIdx, nsys, hInfo);
 }
 
 int idahip_ls_solve(idahip_ctx* c, const double* dLU, const int64_t* dPiv, double* dX, const double* dB, double /*tol*/,
                     const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!dLU || !dPiv || !dX || !dB) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({dLU, dPiv, dX, dB})) return f.rc;
+    if (!f.stage()) return f.rc;
     const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
+    f.launch(IDAHIP_K_SOLVE, nsys, "ls_solve", [&] {
         if (n <= TINY_N) {
             hipLaunchKernelGGL(tiny_solve_kernel, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, dLU, (long)n * n, (const long long*)dPiv,
-                               (long)n, dX, dB, n, d_idx, nsys);
+                               (long)n, dX, dB, n, f.idx, nsys);
         } else {
             const size_t shm = sizeof(double) * n + sizeof(int) * n;
             if (n % 2 == 0)
                 hipLaunchKernelGGL(ls_solve_kernel<2>, dim3(nsys), dim3(256), shm, c->stream, dLU, (long)n * n, (const long long*)dPiv,
-                                   (long)n, (const int*)nullptr, dX, dB, n, d_idx);
+                                   (long)n, (const int*)nullptr, dX, dB, n, f.idx);
             else
                 hipLaunchKernelGGL(ls_solve_kernel<1>, dim3(nsys), dim3(256), shm, c->stream, dLU, (long)n * n, (const long long*)dPiv,
-                                   (long)n, (const int*)nullptr, dX, dB, n, d_idx);
+                                   (long)n, (const int*)nullptr, dX, dB, n, f.idx);
         }
-        if ((rc = post_launch(c, "ls_solve"))) return rc;
-    }
-    return ap.finish_async();
+    });
+    return f.done();
 }
 
 int idahip_ls_setup_band(idahip_ctx* c, int ml, int mu, double* dAB, int64_t* dPiv, int32_t* hInfo, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!dAB || !dPiv || !hInfo) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({dAB, dPiv, hInfo})) return f.rc;
     if (ml < 0 || mu < 0 || ml >= c->n || mu >= c->n) return fail(c, -2, "bandwidths ml = %d, mu = %d outside [0, n)", ml, mu);
-    if (nsys == 0) return 0;
+    if (!f.stage()) return f.rc;
     const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_LU, nsys);
-        if ((rc = band_factor(c, dAB, (long)(2 * ml + mu + 1) * n, dPiv, n, ml, mu, d_idx, nsys))) return rc;
-    }
-    std::vector<int32_t> info(c->batch);
-    IDAHIP_HIP(c, hipMemcpyAsync(info.data(), c->lu_info, sizeof(int32_t) * c->batch, hipMemcpyDeviceToHost, c->stream));
-    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
-    int any = 0;
-    for (int s = 0; s < nsys; ++s) {
-        hInfo[s] = info[hIdx[s]];
-        any |= hInfo[s] != 0;
-    }
-    return any ? 1 : 0;
+    f.launch(IDAHIP_K_LU, nsys, nullptr, [&] { return band_factor(c, dAB, (long)(2 * ml + mu + 1) * n, dPiv, n, ml, mu, f.idx, nsys); });
+    return f.rc ? f.rc : report_info(c, hIdx, nsys, hInfo);
 }
 
 int idahip_ls_solve_band(idahip_ctx* c, int ml, int mu, const double* dAB, const int64_t* dPiv, double* dX, const double* dB, double /*tol*/,
                          const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!dAB || !dPiv || !dX || !dB) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({dAB, dPiv, dX, dB})) return f.rc;
     if (ml < 0 || mu < 0 || ml >= c->n || mu >= c->n) return fail(c, -2, "bandwidths ml = %d, mu = %d outside [0, n)", ml, mu);
-    if (nsys == 0) return 0;
+    if (!f.stage()) return f.rc;
     const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
+    f.launch(IDAHIP_K_SOLVE, nsys, "ls_solve_band", [&] {
         const int spw = band_spw(c, nsys);
         const dim3 grid((nsys + spw - 1) / spw), blk(spw);
         const long ss = (long)(2 * ml + mu + 1) * n;
         if (ml == 1 && mu == 1)
-            hipLaunchKernelGGL((band_getrs_kernel<1, 1>), grid, blk, 0, c->stream, dAB, ss, (const long long*)dPiv, (long)n, dX, dB, n, ml, mu, d_idx, nsys);
+            hipLaunchKernelGGL((band_getrs_kernel<1, 1>), grid, blk, 0, c->stream, dAB, ss, (const long long*)dPiv, (long)n, dX, dB, n, ml, mu, f.idx, nsys);
         else
-            hipLaunchKernelGGL((band_getrs_kernel<-1, -1>), grid, blk, 0, c->stream, dAB, ss, (const long long*)dPiv, (long)n, dX, dB, n, ml, mu, d_idx, nsys);
-        if ((rc = post_launch(c, "ls_solve_band"))) return rc;
-    }
-    return ap.finish_async();
+            hipLaunchKernelGGL((band_getrs_kernel<-1, -1>), grid, blk, 0, c->stream, dAB, ss, (const long long*)dPiv, (long)n, dX, dB, n, ml, mu, f.idx, nsys);
+    });
+    return f.done();
 }
 
 int idahip_wrms(idahip_ctx* c, const double* dX, const double* dW, double* hOut, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!dX || !dW || !hOut) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({dX, dW, hOut})) return f.rc;
+    if (!f.stage()) return f.rc;
     const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    double* d_out = ap.out<double>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+    double* d_out = f.out<double>(nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "wrms", [&] {
         if (n <= TINY_N)
-            hipLaunchKernelGGL(tiny_wrms_kernel, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, dX, dW, d_out, n, d_idx, nsys);
+            hipLaunchKernelGGL(tiny_wrms_kernel, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, dX, dW, d_out, n, f.idx, nsys);
         else
-            hipLaunchKernelGGL(wrms_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, dX, dW, d_out, n, d_idx);
-        if ((rc = post_launch(c, "wrms"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    for (int s = 0; s < nsys; ++s) hOut[s] = sqrt(h[s] / (double)n);  // divide, then sqrt: host libm (norm_rms.rs:36-37)
+            hipLaunchKernelGGL(wrms_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, dX, dW, d_out, n, f.idx);
+    });
+    if (!f.fetch()) return f.rc;
+    f.rms(hOut, d_out, nsys);
     return 0;
 }
 
 int idahip_wrms_masked(idahip_ctx* c, const double* dX, const double* dW, double* hOut, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!dX || !dW || !hOut) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({dX, dW, hOut})) return f.rc;
     if (c->h_id.empty()) return fail(c, -2, "idahip_wrms_masked: no id vector is set (idahip_set_id)");
-    if (nsys == 0) return 0;
+    if (!f.stage()) return f.rc;
     const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    double* d_out = ap.out<double>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(wrms_masked_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, dX, dW, (const double*)c->d_id, d_out, n, d_idx);
-        if ((rc = post_launch(c, "wrms_masked"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    for (int s = 0; s < nsys; ++s) hOut[s] = sqrt(h[s] / (double)n);  // by the full n (norm_rms.rs:56)
+    double* d_out = f.out<double>(nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "wrms_masked", [&] {
+        hipLaunchKernelGGL(wrms_masked_kernel, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, dX, dW, (const double*)c->d_id, d_out, n, f.idx);
+    });
+    if (!f.fetch()) return f.rc;
+    f.rms(hOut, d_out, nsys);  // by the full n (norm_rms.rs:56)
     return 0;
 }
+
 
 // ------------------------------------------------------------------------------------------------ NLProblem
 namespace {
@@ -1148,26 +1051,15 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
 }
 
 // batched getrf of the work matrices into ctx->lu / piv / perm, then the per-system info of the listed systems
-int factor_and_report(idahip_ctx* c, double* work, const int* d_idx, const int32_t* hIdx, int nsys, int32_t* hInfo) {
-    const int n = c->n;
+int factor_and_report(ListCall& f, double* work, int32_t* hInfo) {
+    idahip_ctx* c = f.c;
+    const int n = c->n, nsys = f.nsys;
     const long nn = (long)n * n;
-    int rc;
-    {
-        KTimer kt(c, IDAHIP_K_LU, nsys);
-        if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, d_idx, nsys);
-        else rc = lu_factor_batched(c, work, nn, c->lu, nn, (long long*)c->piv, n, c->perm, d_idx, nsys);
-        if (rc) return rc;
-        if ((rc = post_launch(c, "lu"))) return rc;
-    }
-    std::vector<int32_t> info(c->batch);
-    IDAHIP_HIP(c, hipMemcpyAsync(info.data(), c->lu_info, sizeof(int32_t) * c->batch, hipMemcpyDeviceToHost, c->stream));
-    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
-    int any = 0;
-    for (int s = 0; s < nsys; ++s) {
-        hInfo[s] = info[hIdx[s]];
-        any |= hInfo[s] != 0;
-    }
-    return any ? 1 : 0;
+    f.launch(IDAHIP_K_LU, nsys, "lu", [&] {
+        if (c->band) return band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, f.idx, nsys);
+        return lu_factor_batched(c, work, nn, c->lu, nn, (long long*)c->piv, n, c->perm, f.idx, nsys);
+    });
+    return f.rc ? f.rc : report_info(c, f.hIdx, nsys, hInfo);
 }
 
 void fill_sys_args(idahip_ctx* c, SysArgs& a, int reset_ee) {
@@ -1178,130 +1070,82 @@ void fill_sys_args(idahip_ctx* c, SysArgs& a, int reset_ee) {
 }  // namespace
 
 int idahip_nls_sys(idahip_ctx* c, const double* hTn, const double* hCj, int reset_ee, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hTn, hCj})) return f.rc;
+    if (!f.stage()) return f.rc;
     SysArgs a;
-    a.idx = ap.in(hIdx, nsys);
-    a.tn = ap.in(hTn, nsys);
-    a.cj = ap.in(hCj, nsys);
-    if ((rc = ap.upload())) return rc;
+    a.idx = f.idx;
+    a.tn = f.in(hTn, nsys);
+    a.cj = f.in(hCj, nsys);
     fill_sys_args(c, a, reset_ee);
-    {
-        KTimer kt(c, IDAHIP_K_SYS, nsys);
-        if ((rc = launch_sys(c, a, nsys, nullptr, hTn, hIdx))) return rc;
-    }
-    return ap.finish_async();
+    f.launch(IDAHIP_K_SYS, nsys, nullptr, [&] { return launch_sys(c, a, nsys, nullptr, hTn, hIdx); });
+    return f.done();
 }
 
 int idahip_nls_lsetup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_nls_lsetup on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj || !hInfo) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys, "idahip_nls_lsetup");
+    if (!f.args({hTn, hCj, hInfo})) return f.rc;
     if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_nls_lsetup_dq");
-    if (nsys == 0) return 0;
-    const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_cj = ap.in(hCj, nsys);
-    if ((rc = ap.upload())) return rc;
-    double* work = (n <= TINY_N) ? c->lu : c->jw;
-    {
-        KTimer kt(c, IDAHIP_K_JAC, nsys);
-        if ((rc = launch_jac(c, work, d_idx, d_cj, nsys, hTn, hCj, hIdx))) return rc;
-    }
-    return factor_and_report(c, work, d_idx, hIdx, nsys, hInfo);
+    if (!f.stage()) return f.rc;
+    const double* d_cj = f.in(hCj, nsys);
+    double* work = (c->n <= TINY_N) ? c->lu : c->jw;
+    f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] { return launch_jac(c, work, f.idx, d_cj, nsys, hTn, hCj, hIdx); });
+    return factor_and_report(f, work, hInfo);
 }
 
 int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, int reset_ee, int32_t* hInfo, const int32_t* hIdx,
                          int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_nls_sys_setup on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj || !hInfo) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys, "idahip_nls_sys_setup");
+    if (!f.args({hTn, hCj, hInfo})) return f.rc;
     if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_nls_sys, then idahip_nls_lsetup_dq");
-    if (nsys == 0) return 0;
-    const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
+    if (!f.stage()) return f.rc;
     SysArgs a;
-    a.idx = ap.in(hIdx, nsys);
-    a.tn = ap.in(hTn, nsys);
-    a.cj = ap.in(hCj, nsys);
-    if ((rc = ap.upload())) return rc;
+    a.idx = f.idx;
+    a.tn = f.in(hTn, nsys);
+    a.cj = f.in(hCj, nsys);
     fill_sys_args(c, a, reset_ee);
-    double* work = (n <= TINY_N) ? c->lu : c->jw;
+    double* work = (c->n <= TINY_N) ? c->lu : c->jw;
     // the linear dense residual sweeps A and B anyway: J = B + cj*A falls out of the same pass
-    const bool fused = c->kind == IDAHIP_LINEAR_DENSE && n > TINY_N;
-    {
-        KTimer kt(c, fused ? IDAHIP_K_SYS_JAC : IDAHIP_K_SYS, nsys);
-        if ((rc = launch_sys(c, a, nsys, fused ? work : nullptr, hTn, hIdx))) return rc;
-    }
-    if (!fused) {
-        KTimer kt(c, IDAHIP_K_JAC, nsys);
-        if ((rc = launch_jac(c, work, a.idx, a.cj, nsys, hTn, hCj, hIdx))) return rc;
-    }
-    return factor_and_report(c, work, a.idx, hIdx, nsys, hInfo);
+    const bool fused = c->kind == IDAHIP_LINEAR_DENSE && c->n > TINY_N;
+    f.launch(fused ? IDAHIP_K_SYS_JAC : IDAHIP_K_SYS, nsys, nullptr, [&] { return launch_sys(c, a, nsys, fused ? work : nullptr, hTn, hIdx); });
+    if (!fused) f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] { return launch_jac(c, work, a.idx, a.cj, nsys, hTn, hCj, hIdx); });
+    return factor_and_report(f, work, hInfo);
 }
 
 int idahip_nls_lsetup_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx,
                          int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_nls_lsetup_dq on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj || !hHh || !hInfo) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys, "idahip_nls_lsetup_dq");
+    if (!f.args({hTn, hCj, hHh, hInfo})) return f.rc;
     if (!c->jac_dq) return fail(c, -2, "idahip_nls_lsetup_dq on a ctx with analytic Jacobians (idahip_set_jacobian_dq)");
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_cj = ap.in(hCj, nsys);
-    const double* d_hh = ap.in(hHh, nsys);
-    if ((rc = ap.upload())) return rc;
+    if (!f.stage()) return f.rc;
+    const double* d_cj = f.in(hCj, nsys);
+    const double* d_hh = f.in(hHh, nsys);
     double* work = (c->n <= TINY_N) ? c->lu : c->jw;
-    {
-        KTimer kt(c, IDAHIP_K_JAC, nsys);
-        if ((rc = launch_jac(c, work, d_idx, d_cj, nsys, hTn, hCj, hIdx, nullptr, d_hh))) return rc;
-    }
-    return factor_and_report(c, work, d_idx, hIdx, nsys, hInfo);
+    f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] { return launch_jac(c, work, f.idx, d_cj, nsys, hTn, hCj, hIdx, nullptr, d_hh); });
+    return factor_and_report(f, work, hInfo);
 }
 
 int idahip_jac_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, double* hJ, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj || !hHh || !hJ) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hTn, hCj, hHh, hJ})) return f.rc;
+    if (!f.stage()) return f.rc;
     const size_t mat = c->band ? (size_t)c->ldab * c->n : (size_t)c->n * c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_cj = ap.in(hCj, nsys);
-    const double* d_hh = ap.in(hHh, nsys);
-    if ((rc = ap.upload())) return rc;
+    const double* d_cj = f.in(hCj, nsys);
+    const double* d_hh = f.in(hHh, nsys);
+    if (!f.send()) return f.rc;
     // a chunk of systems at a time through a buffer of its own: the ctx's work matrices and factors are left as they are
     const int m = (int)std::max<size_t>(1, std::min<size_t>((size_t)nsys, ((size_t)256 << 20) / (mat * sizeof(double))));
-    if ((rc = dq_grow(c, &c->dq_out, &c->dq_out_cap, (size_t)m * mat))) return rc;
+    if (int rc = dq_grow(c, &c->dq_out, &c->dq_out_cap, (size_t)m * mat)) return rc;
     for (int s0 = 0; s0 < nsys; s0 += m) {
         const int k = std::min(m, nsys - s0);
-        {
-            KTimer kt(c, IDAHIP_K_JAC, k);
-            if ((rc = launch_dq_jac(c, c->dq_out, true, d_idx + s0, d_cj + s0, d_hh + s0, k, hTn + s0, hIdx + s0, nullptr))) return rc;
-        }
+        if (!f.launch(IDAHIP_K_JAC, k, nullptr, [&] { return launch_dq_jac(c, c->dq_out, true, f.idx + s0, d_cj + s0, d_hh + s0, k, hTn + s0, hIdx + s0, nullptr); }))
+            return f.rc;
         IDAHIP_HIP(c, hipMemcpyAsync(hJ + (size_t)s0 * mat, c->dq_out, sizeof(double) * k * mat, hipMemcpyDeviceToHost, c->stream));
         IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
     }
-    return ap.finish_async();
+    return f.done();
 }
+
 
 int idahip_set_jacobian_dq(idahip_ctx* c, int on) {
     if (!c) return -1;
@@ -1342,83 +1186,58 @@ static int launch_newton_iter(idahip_ctx* c, const int* d_idx, const double* d_s
 }
 
 int idahip_newton_iter(idahip_ctx* c, const double* hScale, double* hDelnrm, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_newton_iter on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hScale || !hDelnrm) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_scale = ap.in(hScale, nsys);
-    double* d_out = ap.out<double>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_NEWTON_ITER, nsys);
-        if ((rc = launch_newton_iter(c, d_idx, d_scale, d_out, nullptr, nsys))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    for (int s = 0; s < nsys; ++s) hDelnrm[s] = sqrt(h[s] / (double)n);
+    ListCall f(c, hIdx, nsys, "idahip_newton_iter");
+    if (!f.args({hScale, hDelnrm})) return f.rc;
+    if (!f.stage()) return f.rc;
+    const double* d_scale = f.in(hScale, nsys);
+    double* d_out = f.out<double>(nsys);
+    f.launch(IDAHIP_K_NEWTON_ITER, nsys, nullptr, [&] { return launch_newton_iter(c, f.idx, d_scale, d_out, nullptr, nsys); });
+    if (!f.fetch()) return f.rc;
+    f.rms(hDelnrm, d_out, nsys);
     return 0;
 }
 
 int idahip_newton_iter2(idahip_ctx* c, const double* hScale, const double* hTn, const double* hCj, const double* hToldel, const double* hSs,
                         const double* hEpsNewt, double* hDelnrm, int32_t* hConv, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_newton_iter2 on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hScale || !hTn || !hCj || !hToldel || !hSs || !hEpsNewt || !hDelnrm || !hConv) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys, "idahip_newton_iter2");
+    if (!f.args({hScale, hTn, hCj, hToldel, hSs, hEpsNewt, hDelnrm, hConv})) return f.rc;
     if (c->kind == IDAHIP_HOST_CALLBACK) return fail(c, -2, "idahip_newton_iter2 needs a device residual (not for IDAHIP_HOST_CALLBACK)");
-    if (nsys == 0) return 0;
+    if (!f.stage()) return f.rc;
     const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
     SysArgs a;
-    a.idx = ap.in(hIdx, nsys);
-    a.tn = ap.in(hTn, nsys);
-    a.cj = ap.in(hCj, nsys);
-    const double* d_scale = ap.in(hScale, nsys);
-    const double* d_toldel = ap.in(hToldel, nsys);
-    const double* d_ss = ap.in(hSs, nsys);
-    const double* d_eps = ap.in(hEpsNewt, nsys);
-    double* d_dn = ap.out<double>(2 * (size_t)nsys);
-    int* d_conv = ap.out<int>(nsys);
-    double* d_sum = ap.out<double>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
+    a.idx = f.idx;
+    a.tn = f.in(hTn, nsys);
+    a.cj = f.in(hCj, nsys);
+    const double* d_scale = f.in(hScale, nsys);
+    const double* d_toldel = f.in(hToldel, nsys);
+    const double* d_ss = f.in(hSs, nsys);
+    const double* d_eps = f.in(hEpsNewt, nsys);
+    double* d_dn = f.out<double>(2 * (size_t)nsys);
+    int* d_conv = f.out<int>(nsys);
+    double* d_sum = f.out<double>(nsys);
     fill_sys_args(c, a, 0);
     const dim3 tg((nsys + 255) / 256), tb(256);
-    {   // iteration m = 0 and its convergence test
-        KTimer kt(c, IDAHIP_K_NEWTON_ITER, nsys);
-        if ((rc = launch_newton_iter(c, a.idx, d_scale, d_sum, nullptr, nsys))) return rc;
-        hipLaunchKernelGGL(ctest_kernel, tg, tb, 0, c->stream, (const double*)d_sum, n, 0, d_toldel, d_ss, d_eps, d_dn, d_conv, nsys);
-    }
+    // iteration m = 0 and its convergence test
+    f.launch(IDAHIP_K_NEWTON_ITER, nsys, nullptr, [&] {
+        const int rc = launch_newton_iter(c, a.idx, d_scale, d_sum, nullptr, nsys);
+        if (!rc) hipLaunchKernelGGL(ctest_kernel, tg, tb, 0, c->stream, (const double*)d_sum, n, 0, d_toldel, d_ss, d_eps, d_dn, d_conv, nsys);
+        return rc;
+    });
     a.skip = d_conv;
-    {   // NLProblem::sys at the corrected y for the systems that go on (conv == 0)
-        KTimer kt(c, IDAHIP_K_SYS, 0);
-        if ((rc = launch_sys(c, a, nsys, nullptr, hTn, hIdx))) return rc;
-    }
-    {   // iteration m = 1 and its convergence test
-        KTimer kt(c, IDAHIP_K_NEWTON_ITER, 0);
-        if ((rc = launch_newton_iter(c, a.idx, d_scale, d_sum, d_conv, nsys))) return rc;
-        hipLaunchKernelGGL(ctest_kernel, tg, tb, 0, c->stream, (const double*)d_sum, n, 1, d_toldel, d_ss, d_eps, d_dn, d_conv, nsys);
-        if ((rc = post_launch(c, "ctest"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* hd = ap.host_of((const double*)d_dn);
-    const int* hc = ap.host_of((const int*)d_conv);
-    for (int s = 0; s < nsys; ++s) {
-        hDelnrm[2 * s] = hd[2 * s];
-        hDelnrm[2 * s + 1] = hd[2 * s + 1];
-        hConv[s] = hc[s];
-    }
+    // NLProblem::sys at the corrected y for the systems that go on (conv == 0)
+    f.launch(IDAHIP_K_SYS, 0, nullptr, [&] { return launch_sys(c, a, nsys, nullptr, hTn, hIdx); });
+    // iteration m = 1 and its convergence test
+    f.launch(IDAHIP_K_NEWTON_ITER, 0, "ctest", [&] {
+        const int rc = launch_newton_iter(c, a.idx, d_scale, d_sum, d_conv, nsys);
+        if (!rc) hipLaunchKernelGGL(ctest_kernel, tg, tb, 0, c->stream, (const double*)d_sum, n, 1, d_toldel, d_ss, d_eps, d_dn, d_conv, nsys);
+        return rc;
+    });
+    if (!f.fetch()) return f.rc;
+    f.copy(hDelnrm, d_dn, 2 * (size_t)nsys);
+    f.copy(hConv, d_conv, nsys);
     return 0;
 }
+
 
 int idahip_kind(const idahip_ctx* c) { return c ? (int)c->kind : -1; }
 
@@ -1472,7 +1291,7 @@ int idahip_krylov_rounds(const idahip_ctx* c) { return c ? (c->krylov ? c->kry_r
 int idahip_krylov_rounds_put_counters(idahip_ctx* c, const int64_t* hNpe, const int64_t* hNps) {
     if (!c) return -1;
     if (!c->krylov) return fail(c, -2, "idahip_krylov_rounds_put_counters: not a Krylov ctx (idahip_create_krylov)");
-    if (!hNpe || !hNps) return fail(c, -2, "null argument");
+    if (!hNpe || !hNps) return null_argument(c);
     c->kry_h_npe.assign(hNpe, hNpe + c->batch);
     c->kry_h_nps.assign(hNps, hNps + c->batch);
     return 0;
@@ -1557,40 +1376,36 @@ int krylov_launch(idahip_ctx* c, KryArgs& a, const double* hTn, const int32_t* h
     return post_launch(c, "krylov_finish");
 }
 
-int krylov_call(idahip_ctx* c, bool newton, const double* hTn, const double* hCj, const double* hTol, const double* hB, double* hX,
-                double* hDelnrm, int32_t* hNli, int32_t* hFlag, double* hResNorm, const int32_t* hIdx, int nsys) {
-    const int n = c->n;
-    ArgPack ap;
-    int rc;
-    if ((rc = ap.begin(c))) return rc;
+// the staged part of idahip_krylov_solve and idahip_newton_iter_krylov (newton): `f` has passed the refusals
+int krylov_call(ListCall& f, bool newton, const double* hTn, const double* hCj, const double* hTol, const double* hB, double* hX,
+                double* hDelnrm, int32_t* hNli, int32_t* hFlag, double* hResNorm) {
+    if (!f.stage()) return f.rc;
+    idahip_ctx* c = f.c;
+    const int n = c->n, nsys = f.nsys;
     KryArgs a{};
-    a.idx = ap.in(hIdx, nsys);
-    a.cj = ap.in(hCj, nsys);
-    a.tol = ap.in(hTol, nsys);
-    a.nli = ap.out<int>(nsys);
-    a.flag = ap.out<int>(nsys);
-    a.resnorm = ap.out<double>(nsys);
-    a.nrm = ap.out<double>(nsys);
-    a.done = ap.out<int>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
+    a.idx = f.idx;
+    a.cj = f.in(hCj, nsys);
+    a.tol = f.in(hTol, nsys);
+    a.nli = f.out<int>(nsys);
+    a.flag = f.out<int>(nsys);
+    a.resnorm = f.out<double>(nsys);
+    a.nrm = f.out<double>(nsys);
+    a.done = f.out<int>(nsys);
+    if (!f.send()) return f.rc;
     a.newton = newton ? 1 : 0;
     a.b = c->kry_b;
     a.x = c->kry_x;
     if (!newton) IDAHIP_HIP(c, hipMemcpyAsync(c->kry_b, hB, sizeof(double) * nsys * n, hipMemcpyHostToDevice, c->stream));
-    {
-        KTimer kt(c, newton ? IDAHIP_K_NEWTON_ITER : IDAHIP_K_SOLVE, nsys);
-        if ((rc = krylov_launch(c, a, hTn, hIdx, nsys))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
+    f.launch(newton ? IDAHIP_K_NEWTON_ITER : IDAHIP_K_SOLVE, nsys, nullptr, [&] { return krylov_launch(c, a, hTn, f.hIdx, nsys); });
+    if (!f.fetch()) return f.rc;
     if (!newton) {
         IDAHIP_HIP(c, hipMemcpyAsync(hX, c->kry_x, sizeof(double) * nsys * n, hipMemcpyDeviceToHost, c->stream));
         IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
     }
-    const int* hn = ap.host_of((const int*)a.nli);
-    const int* hf = ap.host_of((const int*)a.flag);
-    const double* hr = ap.host_of((const double*)a.resnorm);
-    const double* hs = ap.host_of((const double*)a.nrm);
+    const int* hn = f.host((const int*)a.nli);
+    const int* hf = f.host((const int*)a.flag);
+    const double* hr = f.host((const double*)a.resnorm);
+    const double* hs = f.host((const double*)a.nrm);
     int any = 0, sum = 0;
     double worst = 0.0;
     for (int s = 0; s < nsys; ++s) {
@@ -1606,6 +1421,7 @@ int krylov_call(idahip_ctx* c, bool newton, const double* hTn, const double* hCj
     c->kry_last_resnorm = worst;
     return any;
 }
+
 
 // a preconditioned ctx solves only systems that a psetup or an upload has given factors
 int krylov_prec_ready(idahip_ctx* c, const char* who, const int32_t* hIdx, int nsys) {
@@ -1667,71 +1483,46 @@ int idahip_krylov_band_prec(const idahip_ctx* c, int* ml, int* mu) {
 }
 
 int idahip_krylov_psetup(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if ((rc = krylov_prec_on(c, "idahip_krylov_psetup"))) return rc;
-    if (!hTn || !hCj || !hHh || !hInfo) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
+    ListCall f(c, hIdx, nsys);
+    if (f.rc) return f.rc;
+    if (int rc = krylov_prec_on(c, "idahip_krylov_psetup")) return rc;
+    if (!f.args({hTn, hCj, hHh, hInfo})) return f.rc;
+    if (!f.stage()) return f.rc;
     const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_cj = ap.in(hCj, nsys);
-    const double* d_hh = ap.in(hHh, nsys);
-    if ((rc = ap.upload())) return rc;
     DqArgs d;
     fill_dq_args(c, d, c->kry_pml, c->kry_pmu, c->kry_pldab);
-    d.idx = d_idx; d.cj = d_cj; d.hh = d_hh; d.skip = nullptr;
+    d.idx = f.idx; d.cj = f.in(hCj, nsys); d.hh = f.in(hHh, nsys); d.skip = nullptr;
     d.out = c->kry_pab; d.compact = 0;
-    {
-        KTimer kt(c, IDAHIP_K_JAC, nsys);
-        if (c->kind == IDAHIP_HOST_CALLBACK) {
-            if ((rc = callback_dq_jac(c, d, hTn, hIdx, nsys))) return rc;
-        } else {  // (idahip_set_krylov_band_prec: the stencil problems are the device kinds)
-            if ((rc = launch_band_dq(c, d, nsys, "band DQ jac (preconditioner)"))) return rc;
-        }
-    }
-    {
-        KTimer kt(c, IDAHIP_K_LU, nsys);
-        if ((rc = band_factor(c, c->kry_pab, (long)c->kry_pldab * n, c->kry_ppiv, n, c->kry_pml, c->kry_pmu, d_idx, nsys))) return rc;
-    }
-    std::vector<int32_t> info(c->batch);
-    IDAHIP_HIP(c, hipMemcpyAsync(info.data(), c->lu_info, sizeof(int32_t) * c->batch, hipMemcpyDeviceToHost, c->stream));
-    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
-    int any = 0;
-    for (int s = 0; s < nsys; ++s) {
-        hInfo[s] = info[hIdx[s]];
-        any |= hInfo[s] != 0;
-        c->kry_pready[hIdx[s]] = 1;
-    }
-    return any ? 1 : 0;
+    f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] {
+        if (c->kind == IDAHIP_HOST_CALLBACK) return callback_dq_jac(c, d, hTn, hIdx, nsys);
+        return launch_band_dq(c, d, nsys, "band DQ jac (preconditioner)");  // (idahip_set_krylov_band_prec: the stencil problems are the device kinds)
+    });
+    f.launch(IDAHIP_K_LU, nsys, nullptr, [&] { return band_factor(c, c->kry_pab, (long)c->kry_pldab * n, c->kry_ppiv, n, c->kry_pml, c->kry_pmu, f.idx, nsys); });
+    const int rc = f.rc ? f.rc : report_info(c, hIdx, nsys, hInfo);
+    for (int s = 0; s < nsys && rc >= 0; ++s) c->kry_pready[hIdx[s]] = 1;
+    return rc;
 }
 
 int idahip_krylov_psolve(idahip_ctx* c, const double* hR, double* hZ, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if ((rc = krylov_prec_on(c, "idahip_krylov_psolve"))) return rc;
-    if (!hR || !hZ) return fail(c, -2, "null argument");
-    if ((rc = krylov_prec_ready(c, "idahip_krylov_psolve", hIdx, nsys))) return rc;
-    if (nsys == 0) return 0;
+    ListCall f(c, hIdx, nsys);
+    if (f.rc) return f.rc;
+    if (int rc = krylov_prec_on(c, "idahip_krylov_psolve")) return rc;
+    if (!f.args({hR, hZ})) return f.rc;
+    if (int rc = krylov_prec_ready(c, "idahip_krylov_psolve", hIdx, nsys)) return rc;
+    if (!f.stage()) return f.rc;
+    if (!f.send()) return f.rc;
     const int n = c->n;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    if ((rc = ap.upload())) return rc;
     IDAHIP_HIP(c, hipMemcpyAsync(c->kry_b, hR, sizeof(double) * nsys * n, hipMemcpyHostToDevice, c->stream));
-    {
-        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
+    f.launch(IDAHIP_K_SOLVE, nsys, "krylov_psolve", [&] {
         hipLaunchKernelGGL(krylov_psolve_kernel, dim3(nsys), dim3(KRY_T), sizeof(double) * n, c->stream, (const double*)c->kry_pab,
-                           (const long long*)c->kry_ppiv, n, c->kry_pml, c->kry_pmu, (const double*)c->kry_b, c->kry_x, d_idx);
-        if ((rc = post_launch(c, "krylov_psolve"))) return rc;
-    }
+                           (const long long*)c->kry_ppiv, n, c->kry_pml, c->kry_pmu, (const double*)c->kry_b, c->kry_x, f.idx);
+    });
+    if (f.rc) return f.rc;
     IDAHIP_HIP(c, hipMemcpyAsync(hZ, c->kry_x, sizeof(double) * nsys * n, hipMemcpyDeviceToHost, c->stream));
     IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
-    return ap.finish_async();
+    return f.done();
 }
+
 
 int idahip_krylov_download_prec(idahip_ctx* c, int sys, double* hAB, int64_t* hPiv) {
     DevGuard dev_guard__(c);
@@ -1752,7 +1543,7 @@ int idahip_krylov_upload_prec(idahip_ctx* c, int sys, const double* hAB, const i
     int rc = krylov_prec_on(c, "idahip_krylov_upload_prec");
     if (rc) return rc;
     if (sys < 0 || sys >= c->batch) return fail(c, -2, "system out of range");
-    if (!hAB || !hPiv) return fail(c, -2, "null argument");
+    if (!hAB || !hPiv) return null_argument(c);
     const int n = c->n;
     for (int j = 0; j < n; ++j) {  // the solves index the vector by the pivots: dgbtrf's range, or nothing is uploaded
         const int64_t hi = std::min<int64_t>((int64_t)n - 1, (int64_t)j + c->kry_pml);
@@ -1768,303 +1559,196 @@ int idahip_krylov_upload_prec(idahip_ctx* c, int sys, const double* hAB, const i
 
 int idahip_krylov_solve(idahip_ctx* c, const double* hTn, const double* hCj, const double* hTol, const double* hB, double* hX, int32_t* hNli,
                         int32_t* hFlag, double* hResNorm, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
+    ListCall f(c, hIdx, nsys);
+    if (f.rc) return f.rc;
     if (!c->krylov) return fail(c, -2, "idahip_krylov_solve: not a Krylov ctx (idahip_create_krylov)");
-    if (!hTn || !hCj || !hTol || !hB || !hX || !hNli || !hFlag || !hResNorm) return fail(c, -2, "null argument");
-    if ((rc = krylov_prec_ready(c, "idahip_krylov_solve", hIdx, nsys))) return rc;
-    if (nsys == 0) return 0;
-    return krylov_call(c, false, hTn, hCj, hTol, hB, hX, nullptr, hNli, hFlag, hResNorm, hIdx, nsys);
+    if (!f.args({hTn, hCj, hTol, hB, hX, hNli, hFlag, hResNorm})) return f.rc;
+    if (int rc = krylov_prec_ready(c, "idahip_krylov_solve", hIdx, nsys)) return rc;
+    return krylov_call(f, false, hTn, hCj, hTol, hB, hX, nullptr, hNli, hFlag, hResNorm);
 }
 
 int idahip_newton_iter_krylov(idahip_ctx* c, const double* hTn, const double* hCj, const double* hEpsNewt, double* hDelnrm, int32_t* hNli,
                               int32_t* hFlag, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
+    ListCall f(c, hIdx, nsys);
+    if (f.rc) return f.rc;
     if (!c->krylov) return fail(c, -2, "idahip_newton_iter_krylov: not a Krylov ctx (idahip_create_krylov)");
-    if (!hTn || !hCj || !hEpsNewt || !hDelnrm || !hNli || !hFlag) return fail(c, -2, "null argument");
-    if ((rc = krylov_prec_ready(c, "idahip_newton_iter_krylov", hIdx, nsys))) return rc;
-    if (nsys == 0) return 0;
+    if (!f.args({hTn, hCj, hEpsNewt, hDelnrm, hNli, hFlag})) return f.rc;
+    if (int rc = krylov_prec_ready(c, "idahip_newton_iter_krylov", hIdx, nsys)) return rc;
     std::vector<double> tol((size_t)nsys);
     for (int s = 0; s < nsys; ++s) tol[s] = idakry::tolerance(c->n, hEpsNewt[s]);
-    return krylov_call(c, true, hTn, hCj, tol.data(), nullptr, nullptr, hDelnrm, hNli, hFlag, nullptr, hIdx, nsys);
+    return krylov_call(f, true, hTn, hCj, tol.data(), nullptr, nullptr, hDelnrm, hNli, hFlag, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ stepper vector ops
 int idahip_init_first(idahip_ctx* c, double* hYpnorm, double* hPhi0Nrm, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hYpnorm || !hPhi0Nrm) return fail(c, -2, "null argument");
-    if ((rc = missing_id(c, "idahip_init_first"))) return rc;
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    double* d_out = ap.out<double>(2 * (size_t)nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(init_first_kernel, dim3(nsys), dim3(256), 2 * sizeof(double) * c->n, c->stream, vec_state(c), d_idx, d_out);
-        if ((rc = post_launch(c, "init_first"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    for (int s = 0; s < nsys; ++s) {
-        hYpnorm[s] = sqrt(h[2 * s] / (double)c->n);
-        hPhi0Nrm[s] = sqrt(h[2 * s + 1] / (double)c->n);
-    }
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hYpnorm, hPhi0Nrm})) return f.rc;
+    if (int rc = missing_id(c, "idahip_init_first")) return rc;
+    if (!f.stage()) return f.rc;
+    double* d_out = f.out<double>(2 * (size_t)nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "init_first", [&] {
+        hipLaunchKernelGGL(init_first_kernel, dim3(nsys), dim3(256), 2 * sizeof(double) * c->n, c->stream, vec_state(c), f.idx, d_out);
+    });
+    if (!f.fetch()) return f.rc;
+    f.rms(hYpnorm, d_out, nsys, 2);
+    f.rms(hPhi0Nrm, d_out + 1, nsys, 2);
     return 0;
 }
 
 int idahip_scale_phi1(idahip_ctx* c, const double* hFac, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hFac) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_fac = ap.in(hFac, nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(scale_phi1_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), d_idx, d_fac);
-        if ((rc = post_launch(c, "scale_phi1"))) return rc;
-    }
-    return ap.finish_async();
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hFac})) return f.rc;
+    if (!f.stage()) return f.rc;
+    const double* d_fac = f.in(hFac, nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "scale_phi1", [&] {
+        hipLaunchKernelGGL(scale_phi1_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), f.idx, d_fac);
+    });
+    return f.done();
 }
 
 int idahip_predict(idahip_ctx* c, const int32_t* hKkNs, const double* hBeta, const double* hGamma, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hKkNs || !hBeta || !hGamma) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    for (int s = 0; s < nsys; ++s)
-        if (hKkNs[2 * s] < 1 || hKkNs[2 * s] >= MXORDP1 || hKkNs[2 * s + 1] < 0) return fail(c, -2, "bad kk/ns at list position %d", s);
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const int* d_kkns = ap.in(hKkNs, 2 * (size_t)nsys);
-    const double* d_beta = ap.in(hBeta, (size_t)MXORDP1 * nsys);
-    const double* d_gamma = ap.in(hGamma, (size_t)MXORDP1 * nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(predict_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), d_idx, d_kkns, d_beta, d_gamma);
-        if ((rc = post_launch(c, "predict"))) return rc;
-    }
-    return ap.finish_async();
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hKkNs, hBeta, hGamma})) return f.rc;
+    if (int rc = check_kk_ns(c, hKkNs, nsys)) return rc;
+    if (!f.stage()) return f.rc;
+    const int* d_kkns = f.in(hKkNs, 2 * (size_t)nsys);
+    const double* d_beta = f.in(hBeta, (size_t)MXORDP1 * nsys);
+    const double* d_gamma = f.in(hGamma, (size_t)MXORDP1 * nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "predict", [&] {
+        hipLaunchKernelGGL(predict_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), f.idx, d_kkns, d_beta, d_gamma);
+    });
+    return f.done();
 }
 
 int idahip_post_newton(idahip_ctx* c, const double* hCj, const int32_t* hKk, double* hNorms, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hCj || !hKk || !hNorms) return fail(c, -2, "null argument");
-    if ((rc = missing_id(c, "idahip_post_newton"))) return rc;
-    if (nsys == 0) return 0;
-    for (int s = 0; s < nsys; ++s)
-        if (hKk[s] < 1 || hKk[s] >= MXORDP1) return fail(c, -2, "bad kk at list position %d", s);
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_cj = ap.in(hCj, nsys);
-    const int* d_kk = ap.in(hKk, nsys);
-    double* d_out = ap.out<double>(4 * (size_t)nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(post_newton_kernel, dim3(nsys), dim3(256), 4 * sizeof(double) * c->n, c->stream, vec_state(c), d_idx, d_cj, d_kk, d_out);
-        if ((rc = post_launch(c, "post_newton"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    for (size_t e = 0; e < 4 * (size_t)nsys; ++e) hNorms[e] = sqrt(h[e] / (double)c->n);
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hCj, hKk, hNorms})) return f.rc;
+    if (int rc = missing_id(c, "idahip_post_newton")) return rc;
+    if (int rc = check_order(c, "kk", hKk, nsys)) return rc;
+    if (!f.stage()) return f.rc;
+    const double* d_cj = f.in(hCj, nsys);
+    const int* d_kk = f.in(hKk, nsys);
+    double* d_out = f.out<double>(4 * (size_t)nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "post_newton", [&] {
+        hipLaunchKernelGGL(post_newton_kernel, dim3(nsys), dim3(256), 4 * sizeof(double) * c->n, c->stream, vec_state(c), f.idx, d_cj, d_kk, d_out);
+    });
+    if (!f.fetch()) return f.rc;
+    f.rms(hNorms, d_out, 4 * (size_t)nsys);
     return 0;
 }
 
 int idahip_post_newton_constr(idahip_ctx* c, const double* hCj, const int32_t* hKk, const double* hEpsNewt, const int32_t* hCheck,
                               double* hNorms, int32_t* hFlag, double* hRr, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hCj || !hKk || !hEpsNewt || !hCheck || !hNorms || !hFlag || !hRr) return fail(c, -2, "null argument");
-    if ((rc = missing_id(c, "idahip_post_newton_constr"))) return rc;
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hCj, hKk, hEpsNewt, hCheck, hNorms, hFlag, hRr})) return f.rc;
+    if (int rc = missing_id(c, "idahip_post_newton_constr")) return rc;
     if (c->h_constr.empty()) return fail(c, -2, "idahip_post_newton_constr on a ctx without constraints (idahip_set_constraints)");
-    if (nsys == 0) return 0;
-    for (int s = 0; s < nsys; ++s)
-        if (hKk[s] < 1 || hKk[s] >= MXORDP1) return fail(c, -2, "bad kk at list position %d", s);
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_cj = ap.in(hCj, nsys);
-    const int* d_kk = ap.in(hKk, nsys);
-    const double* d_eps = ap.in(hEpsNewt, nsys);
-    const int* d_chk = ap.in(hCheck, nsys);
-    double* d_out = ap.out<double>(4 * (size_t)nsys);
-    double* d_rr = ap.out<double>((size_t)nsys);
-    int* d_flag = ap.out<int>((size_t)nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+    if (int rc = check_order(c, "kk", hKk, nsys)) return rc;
+    if (!f.stage()) return f.rc;
+    const double* d_cj = f.in(hCj, nsys);
+    const int* d_kk = f.in(hKk, nsys);
+    const double* d_eps = f.in(hEpsNewt, nsys);
+    const int* d_chk = f.in(hCheck, nsys);
+    double* d_out = f.out<double>(4 * (size_t)nsys);
+    double* d_rr = f.out<double>((size_t)nsys);
+    int* d_flag = f.out<int>((size_t)nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "post_newton_constr", [&] {
         hipLaunchKernelGGL(post_newton_constr_kernel, dim3(nsys), dim3(256), 4 * sizeof(double) * c->n, c->stream, vec_state(c),
-                           (const double*)c->d_constr, d_idx, d_cj, d_kk, d_eps, d_chk, d_out, d_flag, d_rr);
-        if ((rc = post_launch(c, "post_newton_constr"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    const double* hr = ap.host_of((const double*)d_rr);
-    const int* hf = ap.host_of((const int*)d_flag);
-    for (size_t e = 0; e < 4 * (size_t)nsys; ++e) hNorms[e] = sqrt(h[e] / (double)c->n);
-    for (int s = 0; s < nsys; ++s) {
-        hFlag[s] = hf[s];
-        hRr[s] = hr[s];
-    }
+                           (const double*)c->d_constr, f.idx, d_cj, d_kk, d_eps, d_chk, d_out, d_flag, d_rr);
+    });
+    if (!f.fetch()) return f.rc;
+    f.rms(hNorms, d_out, 4 * (size_t)nsys);
+    f.copy(hFlag, d_flag, nsys);
+    f.copy(hRr, d_rr, nsys);
     return 0;
 }
 
 int idahip_constr_check(idahip_ctx* c, idahip_field field, int32_t* hViolated, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hViolated) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hViolated})) return f.rc;
     if (c->h_constr.empty()) return fail(c, -2, "idahip_constr_check on a ctx without constraints (idahip_set_constraints)");
     const double* x = field_ptr(c, field);
     if (!x) return fail(c, -2, "unknown field %d", (int)field);
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    int* d_v = ap.out<int>((size_t)nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(constr_check_kernel, dim3(nsys), dim3(256), 0, c->stream, x, (const double*)c->d_constr, c->n, d_idx, d_v);
-        if ((rc = post_launch(c, "constr_check"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const int* hv = ap.host_of((const int*)d_v);
-    for (int s = 0; s < nsys; ++s) hViolated[s] = hv[s];
+    if (!f.stage()) return f.rc;
+    int* d_v = f.out<int>((size_t)nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "constr_check", [&] {
+        hipLaunchKernelGGL(constr_check_kernel, dim3(nsys), dim3(256), 0, c->stream, x, (const double*)c->d_constr, c->n, f.idx, d_v);
+    });
+    if (!f.fetch()) return f.rc;
+    f.copy(hViolated, d_v, nsys);
     return 0;
 }
 
 int idahip_restore(idahip_ctx* c, const int32_t* hKkNs, const double* hCvals, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hKkNs || !hCvals) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    for (int s = 0; s < nsys; ++s)
-        if (hKkNs[2 * s] < 1 || hKkNs[2 * s] >= MXORDP1 || hKkNs[2 * s + 1] < 0) return fail(c, -2, "bad kk/ns at list position %d", s);
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const int* d_kkns = ap.in(hKkNs, 2 * (size_t)nsys);
-    const double* d_cv = ap.in(hCvals, (size_t)MXORDP1 * nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(restore_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), d_idx, d_kkns, d_cv);
-        if ((rc = post_launch(c, "restore"))) return rc;
-    }
-    return ap.finish_async();
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hKkNs, hCvals})) return f.rc;
+    if (int rc = check_kk_ns(c, hKkNs, nsys)) return rc;
+    if (!f.stage()) return f.rc;
+    const int* d_kkns = f.in(hKkNs, 2 * (size_t)nsys);
+    const double* d_cv = f.in(hCvals, (size_t)MXORDP1 * nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "restore", [&] {
+        hipLaunchKernelGGL(restore_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), f.idx, d_kkns, d_cv);
+    });
+    return f.done();
 }
 
 int idahip_complete_step(idahip_ctx* c, const int32_t* hKused, const double* hCk, int maxord, double* hPhi0Nrm, int32_t* hEwtBad,
                          const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hKused || !hCk || !hPhi0Nrm || !hEwtBad) return fail(c, -2, "null argument");
-    if ((rc = missing_id(c, "idahip_complete_step"))) return rc;
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hKused, hCk, hPhi0Nrm, hEwtBad})) return f.rc;
+    if (int rc = missing_id(c, "idahip_complete_step")) return rc;
     if (maxord < 1 || maxord > 5) return fail(c, -2, "bad maxord");
-    if (nsys == 0) return 0;
-    for (int s = 0; s < nsys; ++s)
-        if (hKused[s] < 1 || hKused[s] > maxord) return fail(c, -2, "bad kused at list position %d", s);
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const int* d_ku = ap.in(hKused, nsys);
-    const double* d_ck = ap.in(hCk, nsys);
-    double* d_out = ap.out<double>(nsys);
-    int* d_bad = ap.out<int>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(complete_step_kernel, dim3(nsys), dim3(256), sizeof(double) * c->n, c->stream, vec_state(c), d_idx, d_ku, d_ck, maxord,
+    if (int rc = check_order(c, "kused", hKused, nsys, maxord)) return rc;
+    if (!f.stage()) return f.rc;
+    const int* d_ku = f.in(hKused, nsys);
+    const double* d_ck = f.in(hCk, nsys);
+    double* d_out = f.out<double>(nsys);
+    int* d_bad = f.out<int>(nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "complete_step", [&] {
+        hipLaunchKernelGGL(complete_step_kernel, dim3(nsys), dim3(256), sizeof(double) * c->n, c->stream, vec_state(c), f.idx, d_ku, d_ck, maxord,
                            d_out, d_bad);
-        if ((rc = post_launch(c, "complete_step"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    const int* hb = ap.host_of(d_bad);
-    for (int s = 0; s < nsys; ++s) {
-        hPhi0Nrm[s] = sqrt(h[s] / (double)c->n);
-        hEwtBad[s] = hb[s];
-    }
+    });
+    if (!f.fetch()) return f.rc;
+    f.rms(hPhi0Nrm, d_out, nsys);
+    f.copy(hEwtBad, d_bad, nsys);
     return 0;
 }
 
 int idahip_get_solution(idahip_ctx* c, const int32_t* hKord, const double* hCvals, const double* hDvals, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hKord || !hCvals || !hDvals) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    for (int s = 0; s < nsys; ++s)
-        if (hKord[s] < 1 || hKord[s] > 5) return fail(c, -2, "bad kord at list position %d", s);
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const int* d_ko = ap.in(hKord, nsys);
-    const double* d_cv = ap.in(hCvals, (size_t)MXORDP1 * nsys);
-    const double* d_dv = ap.in(hDvals, (size_t)5 * nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(get_solution_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), d_idx, d_ko, d_cv, d_dv);
-        if ((rc = post_launch(c, "get_solution"))) return rc;
-    }
-    return ap.finish_async();
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hKord, hCvals, hDvals})) return f.rc;
+    if (int rc = check_order(c, "kord", hKord, nsys)) return rc;
+    if (!f.stage()) return f.rc;
+    const int* d_ko = f.in(hKord, nsys);
+    const double* d_cv = f.in(hCvals, (size_t)MXORDP1 * nsys);
+    const double* d_dv = f.in(hDvals, (size_t)5 * nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "get_solution", [&] {
+        hipLaunchKernelGGL(get_solution_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), f.idx, d_ko, d_cv, d_dv);
+    });
+    return f.done();
 }
 
 int idahip_get_dky(idahip_ctx* c, const int32_t* hKfirst, const int32_t* hKlast, const double* hCjk, double* hOut, const int32_t* hIdx,
                    int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hKfirst || !hKlast || !hCjk || !hOut) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
+    ListCall f(c, hIdx, nsys);
+    if (!f.args({hKfirst, hKlast, hCjk, hOut})) return f.rc;
     for (int s = 0; s < nsys; ++s)
         if (hKfirst[s] < 0 || hKfirst[s] > hKlast[s] || hKlast[s] >= MXORDP1) return fail(c, -2, "bad derivative range at list position %d", s);
-    const size_t bn = (size_t)c->batch * c->n;
-    if (!c->dky && (rc = dalloc(c, &c->dky, bn))) return rc;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const int* d_k0 = ap.in(hKfirst, nsys);
-    const int* d_k1 = ap.in(hKlast, nsys);
-    const double* d_c = ap.in(hCjk, (size_t)MXORDP1 * nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(get_dky_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), d_idx, d_k0, d_k1, d_c, c->dky);
-        if ((rc = post_launch(c, "get_dky"))) return rc;
-    }
+    if (!f.stage()) return f.rc;
+    if (!c->dky)
+        if (int rc = dalloc(c, &c->dky, (size_t)c->batch * c->n)) return rc;
+    const int* d_k0 = f.in(hKfirst, nsys);
+    const int* d_k1 = f.in(hKlast, nsys);
+    const double* d_c = f.in(hCjk, (size_t)MXORDP1 * nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "get_dky", [&] {
+        hipLaunchKernelGGL(get_dky_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), f.idx, d_k0, d_k1, d_c, c->dky);
+    });
+    if (f.rc) return f.rc;  // the results come through ctx->dky, not the slot, and the copy below waits for the stream
     IDAHIP_HIP(c, hipMemcpyAsync(hOut, c->dky, sizeof(double) * (size_t)nsys * c->n, hipMemcpyDeviceToHost, c->stream));
     IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
+
 
 int idahip_snapshot_initial(idahip_ctx* c) {
     DevGuard dev_guard__(c);
@@ -2082,23 +1766,17 @@ int idahip_snapshot_initial(idahip_ctx* c) {
 }
 
 int idahip_restore_initial(idahip_ctx* c, const int32_t* hIdx, int nsys) {
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
+    ListCall f(c, hIdx, nsys);
+    if (f.rc) return f.rc;
     if (!c->ic_y) return fail(c, -2, "idahip_restore_initial before idahip_snapshot_initial");
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
+    if (!f.stage()) return f.rc;
+    f.launch(IDAHIP_K_VECTOR, nsys, "restore_initial", [&] {
         hipLaunchKernelGGL(restore_initial_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), (const double*)c->ic_y,
-                           (const double*)c->ic_yp, d_idx);
-        if ((rc = post_launch(c, "restore_initial"))) return rc;
-    }
-    return ap.finish_async();
+                           (const double*)c->ic_yp, f.idx);
+    });
+    return f.done();
 }
+
 
 // ------------------------------------------------------------------------------------------------ consistent initial conditions
 // (ic_kernels.hpp; driven by idaens_calc_ic)
@@ -2192,224 +1870,133 @@ int ic_check_opt(idahip_ctx* c, int icopt) {
     return 0;
 }
 
-// setup at the iterate: shared by idahip_ic_setup and idahip_ic_setup_dq (hHh != nullptr)
-int ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx, int nsys) {
-    ArgPack ap;
-    int rc;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    const double* d_cj = ap.in(hCj, nsys);
-    const double* d_hh = hHh ? ap.in(hHh, nsys) : nullptr;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(ic_point_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), d_idx);
-        if ((rc = post_launch(c, "ic_point"))) return rc;
-    }
+// setup at the iterate, the staged part of idahip_ic_setup and idahip_ic_setup_dq (hHh != nullptr): `f` has passed the refusals
+int ic_setup(ListCall& f, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo) {
+    if (!f.stage()) return f.rc;
+    idahip_ctx* c = f.c;
+    const int nsys = f.nsys;
+    const double* d_cj = f.in(hCj, nsys);
+    const double* d_hh = hHh ? f.in(hHh, nsys) : nullptr;
+    f.launch(IDAHIP_K_VECTOR, nsys, "ic_point", [&] {
+        hipLaunchKernelGGL(ic_point_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), f.idx);
+    });
     double* work = (c->n <= TINY_N) ? c->lu : c->jw;
-    {
-        KTimer kt(c, IDAHIP_K_JAC, nsys);
-        if ((rc = launch_jac(c, work, d_idx, d_cj, nsys, hTn, hCj, hIdx, nullptr, d_hh))) return rc;
-    }
-    return factor_and_report(c, work, d_idx, hIdx, nsys, hInfo);
+    f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] { return launch_jac(c, work, f.idx, d_cj, nsys, hTn, hCj, f.hIdx, nullptr, d_hh); });
+    return factor_and_report(f, work, hInfo);
 }
 
 }  // namespace
 
 int idahip_ic_begin(idahip_ctx* c, double* hYpnorm, int32_t* hEwtBad, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_begin on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hYpnorm || !hEwtBad) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    double* d_out = ap.out<double>(nsys);
-    int* d_bad = ap.out<int>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(ic_begin_kernel, dim3(nsys), dim3(256), sizeof(double) * c->n, c->stream, vec_state(c), ic_vecs(c), d_idx, d_out, d_bad);
-        if ((rc = post_launch(c, "ic_begin"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    const int* hb = ap.host_of(d_bad);
-    for (int s = 0; s < nsys; ++s) {
-        hYpnorm[s] = sqrt(h[s] / (double)c->n);
-        hEwtBad[s] = hb[s];
-    }
+    ListCall f(c, hIdx, nsys, "idahip_ic_begin");
+    if (!f.args({hYpnorm, hEwtBad})) return f.rc;
+    if (!f.stage()) return f.rc;
+    double* d_out = f.out<double>(nsys);
+    int* d_bad = f.out<int>(nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "ic_begin", [&] {
+        hipLaunchKernelGGL(ic_begin_kernel, dim3(nsys), dim3(256), sizeof(double) * c->n, c->stream, vec_state(c), ic_vecs(c), f.idx, d_out, d_bad);
+    });
+    if (!f.fetch()) return f.rc;
+    f.rms(hYpnorm, d_out, nsys);
+    f.copy(hEwtBad, d_bad, nsys);
     return 0;
 }
 
 int idahip_ic_reset(idahip_ctx* c, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_reset on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(ic_reset_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), d_idx);
-        if ((rc = post_launch(c, "ic_reset"))) return rc;
-    }
-    return ap.finish_async();
+    ListCall f(c, hIdx, nsys, "idahip_ic_reset");
+    if (!f.stage()) return f.rc;
+    f.launch(IDAHIP_K_VECTOR, nsys, "ic_reset", [&] {
+        hipLaunchKernelGGL(ic_reset_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), f.idx);
+    });
+    return f.done();
 }
 
 int idahip_ic_res(idahip_ctx* c, const double* hTn, const double* hCj, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_res on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
+    ListCall f(c, hIdx, nsys, "idahip_ic_res");
+    if (!f.args({hTn, hCj})) return f.rc;
+    if (!f.stage()) return f.rc;
     SysArgsIC a;
-    a.idx = ap.in(hIdx, nsys);
-    a.tn = ap.in(hTn, nsys);
-    a.cj = ap.in(hCj, nsys);
-    if ((rc = ap.upload())) return rc;
+    a.idx = f.idx;
+    a.tn = f.in(hTn, nsys);
+    a.cj = f.in(hCj, nsys);
     fill_ic_args(c, a, nullptr, IDAHIP_IC_Y);
-    {
-        KTimer kt(c, IDAHIP_K_SYS, nsys);
-        if ((rc = launch_ic_sys(c, a, nsys, hTn, hIdx))) return rc;
-    }
-    return ap.finish_async();
+    f.launch(IDAHIP_K_SYS, nsys, nullptr, [&] { return launch_ic_sys(c, a, nsys, hTn, hIdx); });
+    return f.done();
 }
 
 int idahip_ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_setup on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj || !hInfo) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys, "idahip_ic_setup");
+    if (!f.args({hTn, hCj, hInfo})) return f.rc;
     if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_ic_setup_dq");
-    if (nsys == 0) return 0;
-    return ic_setup(c, hTn, hCj, nullptr, hInfo, hIdx, nsys);
+    return ic_setup(f, hTn, hCj, nullptr, hInfo);
 }
 
 int idahip_ic_setup_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_setup_dq on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj || !hHh || !hInfo) return fail(c, -2, "null argument");
+    ListCall f(c, hIdx, nsys, "idahip_ic_setup_dq");
+    if (!f.args({hTn, hCj, hHh, hInfo})) return f.rc;
     if (!c->jac_dq) return fail(c, -2, "idahip_ic_setup_dq on a ctx with analytic Jacobians (idahip_set_jacobian_dq)");
-    if (nsys == 0) return 0;
-    return ic_setup(c, hTn, hCj, hHh, hInfo, hIdx, nsys);
+    return ic_setup(f, hTn, hCj, hHh, hInfo);
 }
 
 int idahip_ic_solve(idahip_ctx* c, double* hFnorm, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_solve on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hFnorm) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    double* d_out = ap.out<double>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
-        if ((rc = launch_ic_solve(c, c->delta, d_idx, d_out, nsys))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    for (int s = 0; s < nsys; ++s) hFnorm[s] = sqrt(h[s] / (double)c->n);
+    ListCall f(c, hIdx, nsys, "idahip_ic_solve");
+    if (!f.args({hFnorm})) return f.rc;
+    if (!f.stage()) return f.rc;
+    double* d_out = f.out<double>(nsys);
+    f.launch(IDAHIP_K_SOLVE, nsys, nullptr, [&] { return launch_ic_solve(c, c->delta, f.idx, d_out, nsys); });
+    if (!f.fetch()) return f.rc;
+    f.rms(hFnorm, d_out, nsys);
     return 0;
 }
 
 int idahip_ic_trial(idahip_ctx* c, int icopt, const double* hTn, const double* hCj, const double* hLambda, double* hFnormp,
                     const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_trial on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hTn || !hCj || !hLambda || !hFnormp) return fail(c, -2, "null argument");
-    if ((rc = ic_check_opt(c, icopt))) return rc;
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
+    ListCall f(c, hIdx, nsys, "idahip_ic_trial");
+    if (!f.args({hTn, hCj, hLambda, hFnormp})) return f.rc;
+    if (int rc = ic_check_opt(c, icopt)) return rc;
+    if (!f.stage()) return f.rc;
     SysArgsIC a;
-    a.idx = ap.in(hIdx, nsys);
-    a.tn = ap.in(hTn, nsys);
-    a.cj = ap.in(hCj, nsys);
-    const double* d_lambda = ap.in(hLambda, nsys);
-    double* d_out = ap.out<double>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
+    a.idx = f.idx;
+    a.tn = f.in(hTn, nsys);
+    a.cj = f.in(hCj, nsys);
+    const double* d_lambda = f.in(hLambda, nsys);
+    double* d_out = f.out<double>(nsys);
     fill_ic_args(c, a, d_lambda, icopt);
     const bool fused = ic_fusable(c);
     if (fused) {
         a.lu = c->lu; a.perm = c->perm; a.piv = (const long long*)c->piv; a.ewt = c->ewt; a.out = d_out;
     }
-    {
-        KTimer kt(c, IDAHIP_K_SYS, nsys);
-        if ((rc = launch_ic_sys(c, a, nsys, hTn, hIdx))) return rc;
-    }
-    if (!fused) {
-        KTimer kt(c, IDAHIP_K_SOLVE, nsys);
-        if ((rc = launch_ic_solve(c, a.delta, a.idx, d_out, nsys))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const double* h = ap.host_of(d_out);
-    for (int s = 0; s < nsys; ++s) hFnormp[s] = sqrt(h[s] / (double)c->n);
+    f.launch(IDAHIP_K_SYS, nsys, nullptr, [&] { return launch_ic_sys(c, a, nsys, hTn, hIdx); });
+    if (!fused) f.launch(IDAHIP_K_SOLVE, nsys, nullptr, [&] { return launch_ic_solve(c, a.delta, a.idx, d_out, nsys); });
+    if (!f.fetch()) return f.rc;
+    f.rms(hFnormp, d_out, nsys);
     return 0;
 }
 
 int idahip_ic_accept(idahip_ctx* c, int icopt, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_accept on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
+    ListCall f(c, hIdx, nsys, "idahip_ic_accept");
+    if (f.rc) return f.rc;
     if (icopt != IDAHIP_IC_YA_YDP && icopt != IDAHIP_IC_Y) return fail(c, -2, "unknown icopt %d", icopt);
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(ic_accept_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), icopt == IDAHIP_IC_YA_YDP ? 1 : 0, d_idx);
-        if ((rc = post_launch(c, "ic_accept"))) return rc;
-    }
-    return ap.finish_async();
+    if (!f.stage()) return f.rc;
+    f.launch(IDAHIP_K_VECTOR, nsys, "ic_accept", [&] {
+        hipLaunchKernelGGL(ic_accept_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), icopt == IDAHIP_IC_YA_YDP ? 1 : 0, f.idx);
+    });
+    return f.done();
 }
 
 int idahip_ic_commit(idahip_ctx* c, int32_t* hEwtBad, const int32_t* hIdx, int nsys) {
-    if (c && c->krylov) return fail(c, -2, "idahip_ic_commit on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
-    DevGuard dev_guard__(c);
-    int rc = check_list(c, hIdx, nsys);
-    if (rc) return rc;
-    if (!hEwtBad) return fail(c, -2, "null argument");
-    if (nsys == 0) return 0;
-    ArgPack ap;
-    if ((rc = ap.begin(c))) return rc;
-    const int* d_idx = ap.in(hIdx, nsys);
-    int* d_bad = ap.out<int>(nsys);
-    if ((rc = ap.ok())) return rc;
-    if ((rc = ap.upload())) return rc;
-    {
-        KTimer kt(c, IDAHIP_K_VECTOR, nsys);
-        hipLaunchKernelGGL(ic_commit_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), d_idx, d_bad);
-        if ((rc = post_launch(c, "ic_commit"))) return rc;
-    }
-    if ((rc = ap.fetch())) return rc;
-    const int* hb = ap.host_of(d_bad);
-    for (int s = 0; s < nsys; ++s) hEwtBad[s] = hb[s];
+    ListCall f(c, hIdx, nsys, "idahip_ic_commit");
+    if (!f.args({hEwtBad})) return f.rc;
+    if (!f.stage()) return f.rc;
+    int* d_bad = f.out<int>(nsys);
+    f.launch(IDAHIP_K_VECTOR, nsys, "ic_commit", [&] {
+        hipLaunchKernelGGL(ic_commit_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), ic_vecs(c), f.idx, d_bad);
+    });
+    if (!f.fetch()) return f.rc;
+    f.copy(hEwtBad, d_bad, nsys);
     return 0;
 }
+
 
 // ---------------------------------------------------------------------------------------------- device-resident stepper (n <= 8)
 __global__ void pow_batch_kernel(const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ out, size_t count) {
@@ -2420,7 +2007,7 @@ __global__ void pow_batch_kernel(const double* __restrict__ x, const double* __r
 int idahip_pow_batch(idahip_ctx* c, const double* hX, const double* hY, double* hOut, size_t count) {
     DevGuard dev_guard__(c);
     if (!c) return -1;
-    if (!hX || !hY || !hOut) return fail(c, -2, "null argument");
+    if (!hX || !hY || !hOut) return null_argument(c);
     if (count == 0) return 0;
     double *dx = nullptr, *dy = nullptr, *dout = nullptr;
     int rc = dalloc(c, &dx, count);
@@ -2467,7 +2054,7 @@ int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_
                       double* hYout, double* hYPout) {
     DevGuard dev_guard__(c);
     if (!c) return -1;
-    if (!hSys || !call || !hRoundsDone || !hAcc || !call->touts || call->ntout < 1) return fail(c, -2, "null argument");
+    if (!hSys || !call || !hRoundsDone || !hAcc || !call->touts || call->ntout < 1) return null_argument(c);
     if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
     if (c->n != 3 || (c->kind != IDAHIP_ROBERTS && c->kind != IDAHIP_LORENZ63))
         return fail(c, -2, "the device-resident stepper takes the Roberts and Lorenz63 problems (n = 3)");
@@ -2635,10 +2222,11 @@ static int krylov_round_newton(idahip_ctx* c, const RoundArgs& a, const KryRound
 
 int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc,
                        double* hYout, double* hYPout, int64_t* rounds_run) {
-    if (c && c->krylov && !c->kry_rounds) return fail(c, -2, "idahip_round_solve on a Krylov ctx (idahip_create_krylov): it forms, factors and solves with no matrix");
+    if (c && !c->kry_rounds)
+        if (int rc = refuse_krylov(c, "idahip_round_solve")) return rc;
     DevGuard dev_guard__(c);
     if (!c) return -1;
-    if (!hSys || !call || !hRoundsDone || !hAcc || !rounds_run || !call->touts || call->ntout < 1) return fail(c, -2, "null argument");
+    if (!hSys || !call || !hRoundsDone || !hAcc || !rounds_run || !call->touts || call->ntout < 1) return null_argument(c);
     if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
     const KindFacts& facts = kind_facts(c->kind);
     const bool lin = c->kind == IDAHIP_LINEAR_DENSE && facts.rounds && c->n <= LU_BIG_MAX_N;
