@@ -69,6 +69,9 @@ pub enum Problem {
     /// 1-D Brusselator (reaction-diffusion) by the method of lines, two interleaved species (n = 2m, m >= 5); parameters
     /// [a, b, d, ub, vb] per system; nonlinear, bandwidths (2, 2)
     Bruss1D,
+    /// a mass-action reaction network given as tables (`Ctx::set_mass_action`; `problem::MassAction` builds them), 2 <= n <= 4096;
+    /// parameters: one rate constant per reaction and system. Dense contexts only.
+    MassAction,
 }
 
 impl Problem {
@@ -80,6 +83,7 @@ impl Problem {
             Problem::Heat1D => sys::IDAHIP_HEAT1D,
             Problem::HostCallback => sys::IDAHIP_HOST_CALLBACK,
             Problem::Bruss1D => sys::IDAHIP_BRUSS1D,
+            Problem::MassAction => sys::IDAHIP_MASS_ACTION,
         }
     }
 }
@@ -339,6 +343,34 @@ impl Ctx {
         let count = a.len() / nn;
         let rc = unsafe { sys::idahip_set_linear_dense(self.raw, first as c_int, count as c_int, a.as_ptr(), b.as_ptr(), c.as_ptr()) };
         self.check(rc).map(|_| ())
+    }
+
+    /// The network of a [`Problem::MassAction`] context, once, before anything evaluates the problem (include/ida_hip.h has the
+    /// definition): `reactants` [nreac][3] with -1 in the unused trailing slots; stoichiometry entries `(rows[e], reacs[e], nu[e])`,
+    /// which keep their order within a row; `d` [n] the coefficients of y'. The library validates everything and refuses a bad
+    /// network, a context of another kind and a second call.
+    pub fn set_mass_action(&mut self, reactants: &[i32], rows: &[i32], reacs: &[i32], nu: &[f64], d: &[f64]) -> Result<(), Error> {
+        assert!(reactants.len() % 3 == 0 && rows.len() == reacs.len() && rows.len() == nu.len() && d.len() == self.n());
+        let rc = unsafe {
+            sys::idahip_set_mass_action(
+                self.raw,
+                (reactants.len() / 3) as c_int,
+                reactants.as_ptr(),
+                rows.len() as c_int,
+                rows.as_ptr(),
+                reacs.as_ptr(),
+                nu.as_ptr(),
+                d.as_ptr(),
+            )
+        };
+        self.check(rc).map(|_| ())
+    }
+
+    /// (positions, ml, mu) of the network's Jacobian pattern, every diagonal position included.
+    pub fn mass_action_pattern(&mut self) -> Result<(usize, usize, usize), Error> {
+        let (mut nnz, mut ml, mut mu): (c_int, c_int, c_int) = (0, 0, 0);
+        let rc = unsafe { sys::idahip_mass_action_pattern(self.raw, &mut nnz, &mut ml, &mut mu) };
+        self.check(rc).map(|_| (nnz as usize, ml as usize, mu as usize))
     }
 
     pub fn set_problem_params(&mut self, first: usize, params: &[f64], nparam: usize) -> Result<(), Error> {

@@ -7,7 +7,7 @@
 use ida::traits::{Jacobian, Residual};
 use ndarray::{ArrayView1, ArrayViewMut1, ArrayViewMut2, ShapeBuilder};
 
-use crate::HostProblem;
+use crate::{Ctx, Error, HostProblem};
 
 /// Wraps one problem instance shared by every system of the batch (the reference integrates one `Ida` per problem; an
 /// ensemble of different parameter sets uses one adapter per system through `Vec<P>` below).
@@ -48,5 +48,52 @@ where
         let n = yy.len();
         let j = ArrayViewMut2::from_shape((n, n).f(), jac_colmajor).expect("n x n Jacobian");
         self.of(sys).jac(tt, cj, ArrayView1::from(yy), ArrayView1::from(yp), ArrayView1::from(resvec), j);
+    }
+}
+
+/// A mass-action reaction network (`Problem::MassAction`, include/ida_hip.h): the tables `Ctx::set_mass_action` takes, built one
+/// reaction at a time. Entries are numbered in the order they are added, so within a row they keep that order.
+pub struct MassAction {
+    n: usize,
+    reactants: Vec<i32>,
+    rows: Vec<i32>,
+    reacs: Vec<i32>,
+    nu: Vec<f64>,
+    d: Vec<f64>,
+}
+
+impl MassAction {
+    /// `n` unknowns, every row differential (d = 1.0) and no reaction yet.
+    pub fn new(n: usize) -> Self {
+        MassAction { n, reactants: Vec::new(), rows: Vec::new(), reacs: Vec::new(), nu: Vec::new(), d: vec![1.0; n] }
+    }
+    /// Reaction of order `reactants.len()` <= 3 (a species may repeat: y1^2 is `&[1, 1]`) with the stoichiometric coefficient `nu`
+    /// in each `(row, nu)` of `stoich`. Returns the reaction's index: the position of its rate constant in a system's parameters.
+    pub fn reaction(&mut self, reactants: &[usize], stoich: &[(usize, f64)]) -> usize {
+        assert!(reactants.len() <= 3 && reactants.iter().all(|&s| s < self.n));
+        let r = self.reactants.len() / 3;
+        for p in 0..3 {
+            self.reactants.push(if p < reactants.len() { reactants[p] as i32 } else { -1 });
+        }
+        for &(row, nu) in stoich {
+            assert!(row < self.n && nu.is_finite());
+            self.rows.push(row as i32);
+            self.reacs.push(r as i32);
+            self.nu.push(nu);
+        }
+        r
+    }
+    /// Row `row` is algebraic: d = 0.0 (a conservation law written as entries that sum to zero).
+    pub fn algebraic(&mut self, row: usize) -> &mut Self {
+        self.d[row] = 0.0;
+        self
+    }
+    /// Reactions added so far: the number of rate constants per system.
+    pub fn nreac(&self) -> usize {
+        self.reactants.len() / 3
+    }
+    /// Uploads the network to a `Problem::MassAction` context.
+    pub fn apply(&self, ctx: &mut Ctx) -> Result<(), Error> {
+        ctx.set_mass_action(&self.reactants, &self.rows, &self.reacs, &self.nu, &self.d)
     }
 }

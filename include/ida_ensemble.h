@@ -70,7 +70,7 @@ int idaens_set_fused_newton(idaens* e, int on);
  * idaens_device_controller_active reports 0; the results are the same):
  *   - small systems (n <= 8: Roberts, Lorenz63): a solve / solve_schedule / stream call is ONE launch in which every system
  *     runs its own time loop (idahip_tiny_solve);
- *   - linear dense, heat and Brusselator problems with 8 < n <= 4096: lock-step rounds as below, but enqueued without a host round trip
+ *   - linear dense, heat, Brusselator and mass-action problems with 8 < n <= 4096: lock-step rounds as below, but enqueued without a host round trip
  *     inside a round -- one synchronisation per round, none in idaens_stream (idahip_round_solve); for n > 1024 one more,
  *     hidden behind the residual kernels: the length of the round's LU list comes back to size the factorisation's launches.
  *     A Newton solve that has to start over with a fresh Jacobian does so in the next round, so a system may need one round

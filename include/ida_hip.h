@@ -30,16 +30,44 @@ extern "C" {
 
 typedef struct idahip_ctx idahip_ctx; /* opaque; owns all device state of one ensemble on one device */
 
-/* User problems shipped as device code (src/traits.rs:12-70 `Residual`/`Jacobian`; H5 in SURVEY.md: a generic Rust
- * closure cannot cross an FFI into device code, so the set is closed and selected by enum). */
+/* User problems on the device (src/traits.rs:12-70 `Residual`/`Jacobian`; H5 in SURVEY.md: a generic Rust closure cannot cross an
+ * FFI into device code). The kinds compiled into the library are selected by enum; a problem of the user's own runs on the device
+ * when it is DATA -- IDAHIP_MASS_ACTION, a polynomial reaction network interpreted by table-driven kernels -- and through host
+ * functions otherwise (IDAHIP_HOST_CALLBACK). */
 typedef enum {
     IDAHIP_ROBERTS = 0,      /* src/sample_problems/roberts.rs:47-91                                  (n = 3) */
     IDAHIP_LORENZ63 = 1,     /* tests/lorenz63.rs:17-25,47-53; params [p, r, b] per system            (n = 3) */
     IDAHIP_LINEAR_DENSE = 2, /* F = A y' + B y - c, A/B dense column-major per system */
     IDAHIP_HEAT1D = 3,       /* 1-D heat, method of lines; params [kappa/dx^2] per system (config 4)           */
     IDAHIP_HOST_CALLBACK = 4, /* any IdaProblem: res / jac are host functions (idahip_set_host_problem); slow path  */
-    IDAHIP_BRUSS1D = 5       /* 1-D Brusselator (reaction-diffusion), method of lines; params [a, b, d, ub, vb] per system: below */
+    IDAHIP_BRUSS1D = 5,      /* 1-D Brusselator (reaction-diffusion), method of lines; params [a, b, d, ub, vb] per system: below */
+    IDAHIP_MASS_ACTION = 6   /* a mass-action reaction network given as tables (idahip_set_mass_action); params k[R] per system: below */
 } idahip_problem;
+
+/* IDAHIP_MASS_ACTION: polynomial kinetics as data. The network is shared by the ensemble: n unknowns (2 <= n <= 4096); R >= 1
+ * reactions, reaction r of order o_r in {0,1,2,3} with reactant slots s_r[0..o_r), a slot holding a species index (repeats allowed:
+ * y1^2 is the slots (1, 1)), passed as int32 [R][3] with -1 in the unused trailing slots; E >= 0 stoichiometry entries
+ * (row i, reaction r, nu) with nu a finite double, which keep, within a row, the order in which the caller listed them; and d[n],
+ * finite, the coefficient of y'_i (1.0: a differential row, 0.0: an algebraic one). Per system the rate constants k[R]
+ * (idahip_set_problem_params, nparam = R). The operation order is the definition; every line is one IEEE operation, nothing is
+ * contracted.
+ *   rate:      q_r = k_r, then q_r = q_r * y[s_r[p]] for p = 0, 1, 2 in slot order
+ *   residual:  acc = nu_e * q_{r(e)} of the row's first entry, then acc = acc + nu_e * q_{r(e)} for the following entries in order
+ *              (acc = +0.0 for a row without entries);   F_i = d_i * y'_i - acc
+ *   derivative factor of slot p of reaction r:  g = k_r, then g = g * y[s_r[t]] for every slot t != p, in slot order
+ *   J = dF/dy + cj dF/dy':  for a position (i, j), acc = the sum of nu_e * g over the row's entries in row order and, within an
+ *              entry, over the slots p in slot order with s_r[p] == j, the first term starting the sum;
+ *              base = cj * d_i if i == j, else +0.0;   J(i, j) = base - acc;   a position without a term holds base.
+ * The Jacobian's PATTERN is the set of positions with a term, and every diagonal position; idahip_mass_action_pattern reports its
+ * size and half-bandwidths. With d = (1, 1, 0), three first-order entries (nu = -1, k = 1) and one zero-order entry (nu = +1, k = 1)
+ * in the last row, the form states IDAHIP_ROBERTS by value.
+ * The difference-quotient Jacobian is idaLsDenseDQJac below with this residual as the row function, every entry by the definition
+ * (a row that does not depend on y_j holds (1/inc)*(+0.0), with the sign of the increment).
+ * It runs wherever a dense ctx runs: the host stepper at every n, the fused first two Newton iterations, idahip_ic_*, constraints,
+ * and the device lock-step rounds for 8 < n <= 4096; idahip_create_band and idahip_create_krylov refuse the kind (-2), and the
+ * one-thread device stepper (n <= 8) does not take it. Until idahip_set_mass_action has been called, every call that would evaluate
+ * the problem -- idahip_nls_sys*, idahip_nls_lsetup*, idahip_jac_dq, idahip_newton_iter2, idahip_ic_res / _setup* / _trial,
+ * idahip_round_solve, idahip_set_problem_params, idaens_create -- returns -2 with a text, and nothing is launched. */
 
 /* IDAHIP_BRUSS1D: the nonlinear, stiff, banded device problem. m grid points, two species interleaved: n = 2m (even, n >= 10),
  * y[2i] = u_i, y[2i+1] = v_i; parameters [a, b, d, ub, vb] per system (idahip_set_problem_params, nparam = 5), d = the diffusion
@@ -276,8 +304,23 @@ int idahip_suppress_alg(const idahip_ctx* ctx);
 int idahip_set_constraints(idahip_ctx* ctx, const double* hC /* [n] or NULL = clear */);
 /* 1 if constraints are set (hC, when non-null, receives them), 0 if not, -1 for a null ctx */
 int idahip_constraints(const idahip_ctx* ctx, double* hC);
-/* per-system problem parameters, systems [first, first+count): LORENZ63 [count][3], HEAT1D [count][1], BRUSS1D [count][5] */
+/* per-system problem parameters, systems [first, first+count): LORENZ63 [count][3], HEAT1D [count][1], BRUSS1D [count][5],
+ * MASS_ACTION [count][nreac] */
 int idahip_set_problem_params(idahip_ctx* ctx, int first, int count, const double* hParams, int nparam);
+/* IDAHIP_MASS_ACTION: the network, once per ctx, after idahip_create and before anything evaluates the problem. reactants
+ * [nreac][3], rows / reacs / nu [nentries], d [n] as defined above. Everything is validated -- index ranges, -1 only in trailing
+ * slots, finite nu and d, nreac >= 1 --: a bad input is refused with -2 and a text that names the first offending item, and
+ * nothing is changed; so is a ctx of another kind, and a second call. Builds and uploads the row-CSR of the residual and the CSR
+ * of the Jacobian's pattern, and allocates the rate constants [batch][nreac] (all 0.0 until idahip_set_problem_params). */
+int idahip_set_mass_action(idahip_ctx* ctx, int nreac, const int32_t* reactants /*[nreac][3]*/, int nentries, const int32_t* rows,
+                           const int32_t* reacs, const double* nu, const double* d /*[n]*/);
+/* the pattern of the network's Jacobian: its positions (*nnz) and half-bandwidths (*ml = max i - j, *mu = max j - i); any pointer
+ * may be null. -2 on a ctx of another kind and before idahip_set_mass_action. */
+int idahip_mass_action_pattern(idahip_ctx* ctx, int* nnz, int* ml, int* mu);
+/* The analytic Jacobian of one system at the ctx-resident yy, to host memory -- for tests/inspection, as idahip_download_lu: hJ [n*n]
+ * column-major, every position outside the pattern +0.0. The kernel of idahip_nls_lsetup launched for one system into a buffer of its
+ * own: the ctx's work matrices and factors are left alone. */
+int idahip_mass_action_jac(idahip_ctx* ctx, int sys, double cj, double* hJ);
 /* LINEAR_DENSE data, systems [first, first+count): hA, hB [count][n*n] column-major, hC [count][n] */
 int idahip_set_linear_dense(idahip_ctx* ctx, int first, int count, const double* hA, const double* hB, const double* hC);
 /* IDAHIP_HOST_CALLBACK: the problem's callbacks (both required) and the pointer handed back to them */
@@ -499,7 +542,7 @@ typedef struct idahip_tiny_call {
 int idahip_tiny_solve(idahip_ctx* ctx, void* hSys, size_t sys_bytes, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc,
                       double* hYout, double* hYPout);
 int idahip_pow_batch(idahip_ctx* ctx, const double* hX, const double* hY, double* hOut, size_t count);
-/* The same call for larger systems (8 < n <= 4096, IDAHIP_LINEAR_DENSE, IDAHIP_HEAT1D or IDAHIP_BRUSS1D, LU variant 4) as LOCK-STEP ROUNDS driven from the
+/* The same call for larger systems (8 < n <= 4096, IDAHIP_LINEAR_DENSE, IDAHIP_HEAT1D, IDAHIP_BRUSS1D or IDAHIP_MASS_ACTION, LU variant 4) as LOCK-STEP ROUNDS driven from the
  * device side: a round = one step attempt of every stepping system (Ida::step's attempt loop body, src/lib.rs:613-711, with
  * Newton::solve, crates/nonlinear/src/newton.rs:51-167, and the batched kernels of this library inside), the controller
  * state of every system and the index lists live on the device, the host only enqueues each round's fixed launch sequence:

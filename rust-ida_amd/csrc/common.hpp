@@ -33,6 +33,8 @@ struct Slot {
     bool pending = false;
 };
 
+struct MaNet;  // mass_action.hpp
+
 }  // namespace idahip
 
 struct idahip_ctx {
@@ -133,6 +135,12 @@ struct idahip_ctx {
     double* params = nullptr;  // [batch][nparam]
     int nparam = 0;
     double *A = nullptr, *B = nullptr, *C = nullptr;  // LINEAR_DENSE
+    // MASS_ACTION (idahip_set_mass_action, mass_action.hpp): the network's tables in one device allocation, the pointers into it,
+    // and what idahip_mass_action_pattern reports; ma == nullptr: the network is not set yet
+    void* ma_blob = nullptr;
+    idahip::MaNet* ma = nullptr;
+    int ma_nnz = 0, ma_ml = 0, ma_mu = 0;
+    int ma_force_wg = 0;  // measurements: the workgroup-per-system residual at every n (IDAHIP_MA_WG, read at idahip_create)
     idahip_res_fn cb_res = nullptr;                   // HOST_CALLBACK
     idahip_jac_fn cb_jac = nullptr;
     idahip_band_jac_fn cb_bjac = nullptr;             // HOST_CALLBACK on a band ctx

@@ -1,4 +1,8 @@
 // libidahip.so -- implementation of include/ida_hip.h (single translation unit; gfx950; -ffp-contract=off).
+#include <algorithm>
+#include <cmath>
+#include <map>
+
 #include "common.hpp"
 #include "list_call.hpp"
 #include "lu_kernels.hpp"
@@ -7,6 +11,7 @@
 #include "solve_kernels.hpp"
 #include "band_kernels.hpp"
 #include "dq_kernels.hpp"
+#include "mass_action.hpp"
 #include "vector_kernels.hpp"
 #include "ic_kernels.hpp"
 #include "krylov_kernels.hpp"
@@ -39,6 +44,7 @@ const KindFacts KIND_FACTS[] = {
     {Heat1D::NPARAM, Heat1D::HALF_BW, true, true, true},       // IDAHIP_HEAT1D
     {0, 0, true, false, false},                                // IDAHIP_HOST_CALLBACK
     {Bruss1D::NPARAM, Bruss1D::HALF_BW, true, true, true},     // IDAHIP_BRUSS1D
+    {0, 0, false, true, false},                                // IDAHIP_MASS_ACTION (nparam = R: known when the network is set)
 };
 constexpr int KIND_COUNT = (int)(sizeof(KIND_FACTS) / sizeof(KIND_FACTS[0]));
 const KindFacts& kind_facts(idahip_problem kind) { return KIND_FACTS[(int)kind]; }
@@ -55,6 +61,27 @@ bool with_stencil(const idahip_ctx* c, F f) {
 
 // what a launch site returns where with_stencil found no description: a kind that has no kernel there
 int no_kernel(idahip_ctx* c, const char* what) { return fail(c, -2, "no %s kernel for problem kind %d", what, (int)c->kind); }
+
+// IDAHIP_MASS_ACTION before idahip_set_mass_action: every call that would evaluate the problem ends here, nothing launched
+int ma_unset(idahip_ctx* c, const char* who) {
+    if (c && c->kind == IDAHIP_MASS_ACTION && !c->ma) return fail(c, -2, "%s: the reaction network is not set (idahip_set_mass_action)", who);
+    return 0;
+}
+
+// the residual of a mass-action ctx (mass_action.hpp): n <= 64 one wavefront per system, above one workgroup per system
+template <class ARGS>
+void launch_ma_sys(idahip_ctx* c, const ARGS& a, int nsys) {
+    const int n = c->n;
+    if (n <= MA_WAVE_MAX_N && !c->ma_force_wg) {
+        hipLaunchKernelGGL(ma_sys_wave_kernel<ARGS>, dim3((nsys + MA_SPW - 1) / MA_SPW), dim3(256), 0, c->stream, a, *c->ma, (const double*)c->params, nsys);
+        return;
+    }
+    bool solve = false;
+    if constexpr (ARGS::IC) solve = a.lu != nullptr;
+    const size_t shm = (solve ? 2 : 1) * sizeof(double) * n;
+    if (n % 2 == 0) hipLaunchKernelGGL((ma_sys_kernel<2, ARGS>), dim3(nsys), dim3(256), shm, c->stream, a, *c->ma, (const double*)c->params);
+    else hipLaunchKernelGGL((ma_sys_kernel<1, ARGS>), dim3(nsys), dim3(256), shm, c->stream, a, *c->ma, (const double*)c->params);
+}
 
 // grid.y of the kernels that split one system's work into chunks: the launch reaches 2048 workgroups, or `cap` chunks per system
 int launch_chunks(int nsys, int cap) {
@@ -154,8 +181,13 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
         std::fprintf(stderr, "IDAHIP_BRUSS1D: n = %d is not 2 m with m >= 5 grid points (two interleaved species)\n", n);
         return -2;
     }
+    if (kind == IDAHIP_MASS_ACTION && (n < 2 || n > LU_BIG_MAX_N)) {
+        std::fprintf(stderr, "IDAHIP_MASS_ACTION: n = %d outside 2 <= n <= %d\n", n, LU_BIG_MAX_N);
+        return -2;
+    }
     idahip_ctx* c = new idahip_ctx();
     c->device = device; c->n = n; c->batch = batch; c->kind = kind;
+    if (const char* e = std::getenv("IDAHIP_MA_WG")) c->ma_force_wg = std::strtol(e, nullptr, 10) != 0 ? 1 : 0;
     if (band) {
         c->band = 1; c->ml = ml; c->mu = mu; c->ldab = 2 * ml + mu + 1;
     }
@@ -296,9 +328,10 @@ int idahip_destroy(idahip_ctx* c) {
     void* ptrs[] = {c->kry_rcnt, c->kry_rint, c->kry_rres, c->kry_pab, c->kry_ppiv, c->kry_V, c->kry_st, c->kry_stage, c->kry_b, c->kry_x, c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
                     c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->d_constr, c->ic_y,
                     c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
-                    c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d};
+                    c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d, c->ma_blob};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    delete c->ma;
     if (c->rnd_host) (void)hipHostFree(c->rnd_host);
     if (c->cb_jpin) (void)hipHostFree(c->cb_jpin);
     if (c->cb_jdev) (void)hipFree(c->cb_jdev);
@@ -524,6 +557,7 @@ int idahip_constraints(const idahip_ctx* c, double* hC) {
 int idahip_set_problem_params(idahip_ctx* c, int first, int count, const double* hParams, int nparam) {
     DevGuard dev_guard__(c);
     if (!c || !hParams) return -1;
+    if (int rc = ma_unset(c, "idahip_set_problem_params")) return rc;
     if (!c->params || nparam != c->nparam) return fail(c, -2, "problem kind takes %d parameters per system", c->nparam);
     if (first < 0 || count < 0 || first + count > c->batch) return fail(c, -2, "system range out of bounds");
     IDAHIP_HIP(c, hipMemcpy(c->params + (size_t)first * nparam, hParams, sizeof(double) * count * nparam, hipMemcpyHostToDevice));
@@ -540,6 +574,130 @@ int idahip_set_linear_dense(idahip_ctx* c, int first, int count, const double* h
     IDAHIP_HIP(c, hipMemcpy(c->A + first * nn, hA, sizeof(double) * count * nn, hipMemcpyHostToDevice));
     IDAHIP_HIP(c, hipMemcpy(c->B + first * nn, hB, sizeof(double) * count * nn, hipMemcpyHostToDevice));
     IDAHIP_HIP(c, hipMemcpy(c->C + (size_t)first * c->n, hC, sizeof(double) * count * c->n, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// IDAHIP_MASS_ACTION: validate the network, build the residual's row-CSR and the Jacobian pattern's CSR (mass_action.hpp) on the host,
+// upload both in one allocation, and allocate the rate constants [batch][nreac]
+int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, int nentries, const int32_t* rows, const int32_t* reacs,
+                           const double* nu, const double* d) {
+    DevGuard dev_guard__(c);
+    if (!c) return -1;
+    if (c->kind != IDAHIP_MASS_ACTION) return fail(c, -2, "idahip_set_mass_action: not an IDAHIP_MASS_ACTION ctx (kind %d)", (int)c->kind);
+    if (c->ma) return fail(c, -2, "idahip_set_mass_action: the reaction network is already set (once per ctx)");
+    if (nreac < 1) return fail(c, -2, "idahip_set_mass_action: nreac = %d, at least one reaction", nreac);
+    if (nentries < 0) return fail(c, -2, "idahip_set_mass_action: nentries = %d is negative", nentries);
+    if (!reactants || !d || (nentries > 0 && (!rows || !reacs || !nu))) return null_argument(c);
+    const int n = c->n;
+    for (int r = 0; r < nreac; ++r) {
+        bool ended = false;
+        for (int p = 0; p < 3; ++p) {
+            const int sp = reactants[3 * r + p];
+            if (sp < -1 || sp >= n) return fail(c, -2, "idahip_set_mass_action: reaction %d, slot %d: species %d outside [0, %d)", r, p, sp, n);
+            if (sp == -1) ended = true;
+            else if (ended) return fail(c, -2, "idahip_set_mass_action: reaction %d, slot %d: a species after an unused slot (-1 only in trailing slots)", r, p);
+        }
+    }
+    for (int e = 0; e < nentries; ++e) {
+        if (rows[e] < 0 || rows[e] >= n) return fail(c, -2, "idahip_set_mass_action: entry %d: row %d outside [0, %d)", e, rows[e], n);
+        if (reacs[e] < 0 || reacs[e] >= nreac) return fail(c, -2, "idahip_set_mass_action: entry %d: reaction %d outside [0, %d)", e, reacs[e], nreac);
+        if (!std::isfinite(nu[e])) return fail(c, -2, "idahip_set_mass_action: entry %d: nu = %g is not finite", e, nu[e]);
+    }
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(d[i])) return fail(c, -2, "idahip_set_mass_action: d[%d] = %g is not finite", i, d[i]);
+    // the residual's rows: a stable counting sort of the entries by row keeps the caller's order within a row
+    std::vector<int> row_ptr(n + 1, 0);
+    for (int e = 0; e < nentries; ++e) row_ptr[rows[e] + 1] += 1;
+    for (int i = 0; i < n; ++i) row_ptr[i + 1] += row_ptr[i];
+    std::vector<MaTerm> rterms((size_t)nentries);
+    {
+        std::vector<int> fill(row_ptr.begin(), row_ptr.end() - 1);
+        for (int e = 0; e < nentries; ++e) {
+            const int32_t* s = reactants + 3 * reacs[e];
+            rterms[(size_t)fill[rows[e]]++] = MaTerm{nu[e], reacs[e], s[0], s[1], s[2]};
+        }
+    }
+    // the Jacobian's pattern, column-major: every diagonal position, and (i, j) for every slot of an entry of row i that holds j;
+    // a position's terms in the header's order (the row's entries in order, within an entry the slots in order)
+    std::map<long, std::vector<MaTerm>> pat;
+    for (int i = 0; i < n; ++i) {
+        pat[(long)i * n + i];
+        for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+            const MaTerm& t = rterms[(size_t)e];
+            const int s[3] = {t.a, t.b, t.c};
+            for (int p = 0; p < 3 && s[p] >= 0; ++p) {
+                int o[2] = {-1, -1}, k = 0;
+                for (int q = 0; q < 3; ++q)
+                    if (q != p && s[q] >= 0) o[k++] = s[q];
+                pat[(long)s[p] * n + i].push_back(MaTerm{t.nu, t.r, o[0], o[1], -1});
+            }
+        }
+    }
+    const int nnz = (int)pat.size();
+    std::vector<int> col_ptr(n + 1, 0), pos_row, pos_ptr;
+    std::vector<MaTerm> jterms;
+    pos_row.reserve(nnz);
+    pos_ptr.reserve(nnz + 1);
+    int ml = 0, mu = 0;
+    for (const auto& kv : pat) {
+        const int j = (int)(kv.first / n), i = (int)(kv.first % n);
+        col_ptr[j + 1] += 1;
+        pos_row.push_back(i);
+        pos_ptr.push_back((int)jterms.size());
+        jterms.insert(jterms.end(), kv.second.begin(), kv.second.end());
+        ml = std::max(ml, i - j);
+        mu = std::max(mu, j - i);
+    }
+    pos_ptr.push_back((int)jterms.size());
+    for (int j = 0; j < n; ++j) col_ptr[j + 1] += col_ptr[j];
+    // one allocation: the int tables, then (8-byte aligned) d and the two term tables
+    const size_t ints = 2 * (size_t)(n + 1) + (size_t)nnz + (size_t)(nnz + 1);
+    const size_t off_d = (ints * sizeof(int) + 7) & ~(size_t)7;
+    const size_t off_rt = off_d + sizeof(double) * n;
+    const size_t off_jt = off_rt + sizeof(MaTerm) * rterms.size();
+    const size_t total = off_jt + sizeof(MaTerm) * jterms.size();
+    std::vector<char> blob(total, 0);
+    int* hi = reinterpret_cast<int*>(blob.data());
+    std::memcpy(hi, row_ptr.data(), sizeof(int) * (n + 1));
+    std::memcpy(hi + (n + 1), col_ptr.data(), sizeof(int) * (n + 1));
+    std::memcpy(hi + 2 * (n + 1), pos_row.data(), sizeof(int) * nnz);
+    std::memcpy(hi + 2 * (n + 1) + nnz, pos_ptr.data(), sizeof(int) * (nnz + 1));
+    std::memcpy(blob.data() + off_d, d, sizeof(double) * n);
+    if (!rterms.empty()) std::memcpy(blob.data() + off_rt, rterms.data(), sizeof(MaTerm) * rterms.size());
+    if (!jterms.empty()) std::memcpy(blob.data() + off_jt, jterms.data(), sizeof(MaTerm) * jterms.size());
+    char* dev = nullptr;
+    double* params = nullptr;
+    if (hipMalloc((void**)&dev, total) != hipSuccess) return fail(c, -100, "idahip_set_mass_action: %zu bytes of network tables", total);
+    if (hipMalloc((void**)&params, sizeof(double) * (size_t)c->batch * nreac) != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(c, -100, "idahip_set_mass_action: rate constants of %d systems x %d reactions", c->batch, nreac);
+    }
+    hipError_t e = hipMemcpy(dev, blob.data(), total, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(params, 0, sizeof(double) * (size_t)c->batch * nreac);
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        (void)hipFree(params);
+        return fail(c, -100, "idahip_set_mass_action: upload failed: %s", hipGetErrorString(e));
+    }
+    MaNet* m = new MaNet();
+    const int* di = reinterpret_cast<const int*>(dev);
+    m->row_ptr = di; m->col_ptr = di + (n + 1); m->pos_row = di + 2 * (n + 1); m->pos_ptr = di + 2 * (n + 1) + nnz;
+    m->d = reinterpret_cast<const double*>(dev + off_d);
+    m->rterms = reinterpret_cast<const MaTerm*>(dev + off_rt);
+    m->jterms = reinterpret_cast<const MaTerm*>(dev + off_jt);
+    m->nreac = nreac;
+    c->ma_blob = dev; c->ma = m; c->ma_nnz = nnz; c->ma_ml = ml; c->ma_mu = mu;
+    c->params = params; c->nparam = nreac;
+    return 0;
+}
+
+int idahip_mass_action_pattern(idahip_ctx* c, int* nnz, int* ml, int* mu) {
+    if (!c) return -1;
+    if (c->kind != IDAHIP_MASS_ACTION) return fail(c, -2, "idahip_mass_action_pattern: not an IDAHIP_MASS_ACTION ctx (kind %d)", (int)c->kind);
+    if (int rc = ma_unset(c, "idahip_mass_action_pattern")) return rc;
+    if (nnz) *nnz = c->ma_nnz;
+    if (ml) *ml = c->ma_ml;
+    if (mu) *mu = c->ma_mu;
     return 0;
 }
 
@@ -864,6 +1022,10 @@ int launch_sys(idahip_ctx* c, const SysArgs& a, int nsys, double* jac_out, const
             }
             break;
         }
+        case IDAHIP_MASS_ACTION:
+            if (int rc = ma_unset(c, "nls_sys")) return rc;
+            launch_ma_sys(c, a, nsys);
+            break;
         default:
             if (!with_stencil(c, [&](auto p) {
                     hipLaunchKernelGGL(stencil_sys_kernel<decltype(p)>, dim3(nsys), dim3(256), sizeof(double) * n, c->stream, a, (const double*)c->params);
@@ -988,6 +1150,12 @@ int launch_dq_jac(idahip_ctx* c, double* out, bool compact, const int* d_idx, co
             }
             break;
         }
+        case IDAHIP_MASS_ACTION: {
+            if (int rc = ma_unset(c, "DQ jac")) return rc;
+            const int chunks = launch_chunks(nsys, n);
+            hipLaunchKernelGGL(ma_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 2 * sizeof(double) * n, c->stream, d, *c->ma, (const double*)c->params, chunks);
+            break;
+        }
         default: {
             const int chunks = launch_chunks(nsys, n);
             const bool stencil = with_stencil(c, [&](auto p) {
@@ -1037,6 +1205,13 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
                                (const double*)c->B, nn, d_idx, d_cj, chunks);
             break;
         }
+        case IDAHIP_MASS_ACTION: {
+            if (int rc = ma_unset(c, "jac")) return rc;
+            const int chunks = launch_chunks(nsys, n);
+            hipLaunchKernelGGL(ma_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->yy, *c->ma, (const double*)c->params,
+                               d_idx, d_cj, chunks, d_skip, 0);
+            break;
+        }
         default: {
             const int chunks = launch_chunks(nsys, n);
             if (!with_stencil(c, [&](auto p) {
@@ -1072,6 +1247,7 @@ void fill_sys_args(idahip_ctx* c, SysArgs& a, int reset_ee) {
 int idahip_nls_sys(idahip_ctx* c, const double* hTn, const double* hCj, int reset_ee, const int32_t* hIdx, int nsys) {
     ListCall f(c, hIdx, nsys);
     if (!f.args({hTn, hCj})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_nls_sys")) return rcu;
     if (!f.stage()) return f.rc;
     SysArgs a;
     a.idx = f.idx;
@@ -1085,6 +1261,7 @@ int idahip_nls_sys(idahip_ctx* c, const double* hTn, const double* hCj, int rese
 int idahip_nls_lsetup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys) {
     ListCall f(c, hIdx, nsys, "idahip_nls_lsetup");
     if (!f.args({hTn, hCj, hInfo})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_nls_lsetup")) return rcu;
     if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_nls_lsetup_dq");
     if (!f.stage()) return f.rc;
     const double* d_cj = f.in(hCj, nsys);
@@ -1097,6 +1274,7 @@ int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, in
                          int nsys) {
     ListCall f(c, hIdx, nsys, "idahip_nls_sys_setup");
     if (!f.args({hTn, hCj, hInfo})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_nls_sys_setup")) return rcu;
     if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_nls_sys, then idahip_nls_lsetup_dq");
     if (!f.stage()) return f.rc;
     SysArgs a;
@@ -1116,6 +1294,7 @@ int idahip_nls_lsetup_dq(idahip_ctx* c, const double* hTn, const double* hCj, co
                          int nsys) {
     ListCall f(c, hIdx, nsys, "idahip_nls_lsetup_dq");
     if (!f.args({hTn, hCj, hHh, hInfo})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_nls_lsetup_dq")) return rcu;
     if (!c->jac_dq) return fail(c, -2, "idahip_nls_lsetup_dq on a ctx with analytic Jacobians (idahip_set_jacobian_dq)");
     if (!f.stage()) return f.rc;
     const double* d_cj = f.in(hCj, nsys);
@@ -1128,6 +1307,7 @@ int idahip_nls_lsetup_dq(idahip_ctx* c, const double* hTn, const double* hCj, co
 int idahip_jac_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, double* hJ, const int32_t* hIdx, int nsys) {
     ListCall f(c, hIdx, nsys);
     if (!f.args({hTn, hCj, hHh, hJ})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_jac_dq")) return rcu;
     if (!f.stage()) return f.rc;
     const size_t mat = c->band ? (size_t)c->ldab * c->n : (size_t)c->n * c->n;
     const double* d_cj = f.in(hCj, nsys);
@@ -1146,6 +1326,30 @@ int idahip_jac_dq(idahip_ctx* c, const double* hTn, const double* hCj, const dou
     return f.done();
 }
 
+
+int idahip_mass_action_jac(idahip_ctx* c, int sys, double cj, double* hJ) {
+    const int32_t one = sys;
+    ListCall f(c, &one, 1);  // (a list of one system: the staging slot carries its id and cj to the kernel)
+    if (!f.args({hJ})) return f.rc;
+    if (c->kind != IDAHIP_MASS_ACTION) return fail(c, -2, "idahip_mass_action_jac: not an IDAHIP_MASS_ACTION ctx (kind %d)", (int)c->kind);
+    if (int rcu = ma_unset(c, "idahip_mass_action_jac")) return rcu;
+    if (!f.stage()) return f.rc;
+    const int n = c->n;
+    const size_t mat = (size_t)n * n;
+    const double* d_cj = f.in(&cj, 1);
+    if (!f.send()) return f.rc;
+    // through idahip_jac_dq's buffer: the ctx's work matrices and factors are left as they are
+    if (int rc = dq_grow(c, &c->dq_out, &c->dq_out_cap, mat)) return rc;
+    const int chunks = launch_chunks(1, n);
+    if (!f.launch(IDAHIP_K_JAC, 1, "ma_jac", [&] {
+            hipLaunchKernelGGL(ma_jac_kernel, dim3(1, chunks), dim3(256), 0, c->stream, c->dq_out, n, (const double*)c->yy, *c->ma,
+                               (const double*)c->params, f.idx, d_cj, chunks, (const int*)nullptr, 1);
+        }))
+        return f.rc;
+    IDAHIP_HIP(c, hipMemcpyAsync(hJ, c->dq_out, sizeof(double) * mat, hipMemcpyDeviceToHost, c->stream));
+    IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
+    return f.done();
+}
 
 int idahip_set_jacobian_dq(idahip_ctx* c, int on) {
     if (!c) return -1;
@@ -1201,6 +1405,7 @@ int idahip_newton_iter2(idahip_ctx* c, const double* hScale, const double* hTn, 
                         const double* hEpsNewt, double* hDelnrm, int32_t* hConv, const int32_t* hIdx, int nsys) {
     ListCall f(c, hIdx, nsys, "idahip_newton_iter2");
     if (!f.args({hScale, hTn, hCj, hToldel, hSs, hEpsNewt, hDelnrm, hConv})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_newton_iter2")) return rcu;
     if (c->kind == IDAHIP_HOST_CALLBACK) return fail(c, -2, "idahip_newton_iter2 needs a device residual (not for IDAHIP_HOST_CALLBACK)");
     if (!f.stage()) return f.rc;
     const int n = c->n;
@@ -1828,6 +2033,8 @@ int launch_ic_solve(idahip_ctx* c, double* x, const int* d_idx, double* d_out, i
 // can the residual kernel of this ctx also solve (SysArgsIC::lu)? The built-in problems on a dense ctx
 bool ic_fusable(const idahip_ctx* c) {
     if (c->band || c->kind == IDAHIP_HOST_CALLBACK) return false;
+    // (a mass-action ctx in the wave-per-system layout has no workgroup of its own to solve with: residual and solve are two launches)
+    if (c->kind == IDAHIP_MASS_ACTION) return c->n > MA_WAVE_MAX_N || (c->ma_force_wg && c->n > TINY_N);
     return c->n > TINY_N || c->kind == IDAHIP_ROBERTS || c->kind == IDAHIP_LORENZ63;
 }
 
@@ -1850,6 +2057,10 @@ int launch_ic_sys(idahip_ctx* c, const SysArgsIC& a, int nsys, const double* hTn
             else hipLaunchKernelGGL((linear_sys_kernel<1, false, SysArgsIC>), dim3(nsys), dim3(256), shm, c->stream, a, A, B, C, (double*)nullptr);
             break;
         }
+        case IDAHIP_MASS_ACTION:
+            if (int rc = ma_unset(c, "ic_res")) return rc;
+            launch_ma_sys(c, a, nsys);
+            break;
         default: {
             const size_t shm = (a.lu ? 2 : 1) * sizeof(double) * n;
             if (!with_stencil(c, [&](auto p) {
@@ -1914,6 +2125,7 @@ int idahip_ic_reset(idahip_ctx* c, const int32_t* hIdx, int nsys) {
 int idahip_ic_res(idahip_ctx* c, const double* hTn, const double* hCj, const int32_t* hIdx, int nsys) {
     ListCall f(c, hIdx, nsys, "idahip_ic_res");
     if (!f.args({hTn, hCj})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_ic_res")) return rcu;
     if (!f.stage()) return f.rc;
     SysArgsIC a;
     a.idx = f.idx;
@@ -1927,6 +2139,7 @@ int idahip_ic_res(idahip_ctx* c, const double* hTn, const double* hCj, const int
 int idahip_ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t* hInfo, const int32_t* hIdx, int nsys) {
     ListCall f(c, hIdx, nsys, "idahip_ic_setup");
     if (!f.args({hTn, hCj, hInfo})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_ic_setup")) return rcu;
     if (c->jac_dq) return fail(c, -2, "a DQ ctx forms its Jacobians with the step sizes: idahip_ic_setup_dq");
     return ic_setup(f, hTn, hCj, nullptr, hInfo);
 }
@@ -1934,6 +2147,7 @@ int idahip_ic_setup(idahip_ctx* c, const double* hTn, const double* hCj, int32_t
 int idahip_ic_setup_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx, int nsys) {
     ListCall f(c, hIdx, nsys, "idahip_ic_setup_dq");
     if (!f.args({hTn, hCj, hHh, hInfo})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_ic_setup_dq")) return rcu;
     if (!c->jac_dq) return fail(c, -2, "idahip_ic_setup_dq on a ctx with analytic Jacobians (idahip_set_jacobian_dq)");
     return ic_setup(f, hTn, hCj, hHh, hInfo);
 }
@@ -1953,6 +2167,7 @@ int idahip_ic_trial(idahip_ctx* c, int icopt, const double* hTn, const double* h
                     const int32_t* hIdx, int nsys) {
     ListCall f(c, hIdx, nsys, "idahip_ic_trial");
     if (!f.args({hTn, hCj, hLambda, hFnormp})) return f.rc;
+    if (int rcu = ma_unset(c, "idahip_ic_trial")) return rcu;
     if (int rc = ic_check_opt(c, icopt)) return rc;
     if (!f.stage()) return f.rc;
     SysArgsIC a;
@@ -2228,14 +2443,16 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     if (!c) return -1;
     if (!hSys || !call || !hRoundsDone || !hAcc || !rounds_run || !call->touts || call->ntout < 1) return null_argument(c);
     if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
+    if (int rcu = ma_unset(c, "idahip_round_solve")) return rcu;
     const KindFacts& facts = kind_facts(c->kind);
     const bool lin = c->kind == IDAHIP_LINEAR_DENSE && facts.rounds && c->n <= LU_BIG_MAX_N;
     const bool banded = facts.rounds && facts.banded && c->n <= LU_BIG_MAX_N;
+    const bool network = c->kind == IDAHIP_MASS_ACTION && facts.rounds && c->n <= LU_BIG_MAX_N;
     const bool kry = c->krylov != 0;  // (idahip_set_krylov_rounds is on: no LU bounds n, the LU variant does not matter)
     if (kry && (c->n <= TINY_N || !(lin || banded) || (c->kry_prec && c->kind == IDAHIP_LINEAR_DENSE)))
         return fail(c, -2, "the device lock-step rounds of a Krylov ctx take linear dense (no preconditioner), heat and Brusselator problems with %d < n <= %d", TINY_N, LU_BIG_MAX_N);
-    if (!kry && (c->n <= TINY_N || !(lin || banded) || c->lu_variant < 4))
-        return fail(c, -2, "the device-resident lock-step stepper takes linear dense, heat and Brusselator problems with %d < n <= %d (LU variant 4)", TINY_N, LU_BIG_MAX_N);
+    if (!kry && (c->n <= TINY_N || !(lin || banded || network) || c->lu_variant < 4))
+        return fail(c, -2, "the device-resident lock-step stepper takes linear dense, heat, Brusselator and mass-action problems with %d < n <= %d (LU variant 4)", TINY_N, LU_BIG_MAX_N);
     if (!c->h_constr.empty()) return fail(c, -2, "the device lock-step stepper does not check constraints: the host stepper does (DESIGN.md section 4g)");
     if (const int rcm = missing_id(c, "idahip_round_solve")) return rcm;
     if (call->recycle && (!c->ic_y || !c->ic_yp)) return fail(c, -2, "recycle needs idahip_snapshot_initial");

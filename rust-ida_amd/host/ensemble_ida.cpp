@@ -601,6 +601,8 @@ extern "C" {
 
 int idaens_create(idaens** out, idahip_ctx* ctx, const double* hYY0, const double* hYP0) {
     if (!out || !ctx || !hYY0 || !hYP0) return -1;
+    // a mass-action ctx without its network has no problem to step (the text is in idahip_last_error)
+    if (idahip_kind(ctx) == IDAHIP_MASS_ACTION && idahip_mass_action_pattern(ctx, nullptr, nullptr, nullptr) != 0) return -2;
     idaens* e = new idaens();
     if (g_prof && g_prof_t0 < 0.0) g_prof_t0 = prof_now();
     e->ctx = ctx;
@@ -777,7 +779,7 @@ int device_ctl_applies(const idaens* e, const SolveCall& C) {
         return (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D || k == IDAHIP_BRUSS1D)) ? 2 : 0;
     if (e->n <= 8 && (k == IDAHIP_ROBERTS || k == IDAHIP_LORENZ63)) return 1;
     if (idahip_constraints(e->ctx, nullptr) == 1) return 0;  // the lock-step device rounds have no constraint check
-    if (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D || k == IDAHIP_BRUSS1D) && idahip_lu_variant(e->ctx) >= 4) return 2;
+    if (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D || k == IDAHIP_BRUSS1D || k == IDAHIP_MASS_ACTION) && idahip_lu_variant(e->ctx) >= 4) return 2;
     return 0;
 }
 

@@ -18,9 +18,9 @@ dp = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
 i64p = C.POINTER(C.c_int64)
 
-ROBERTS, LORENZ63, LINEAR_DENSE, HEAT1D, HOST_CALLBACK, BRUSS1D = 0, 1, 2, 3, 4, 5
+ROBERTS, LORENZ63, LINEAR_DENSE, HEAT1D, HOST_CALLBACK, BRUSS1D, MASS_ACTION = 0, 1, 2, 3, 4, 5, 6
 KIND = {"roberts": ROBERTS, "lorenz63": LORENZ63, "linear_dense": LINEAR_DENSE, "heat1d": HEAT1D, "host_callback": HOST_CALLBACK,
-        "bruss1d": BRUSS1D}
+        "bruss1d": BRUSS1D, "mass_action": MASS_ACTION}
 RES_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
 JAC_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                      C.POINTER(C.c_double), C.c_void_p)
@@ -52,6 +52,7 @@ HIP_SYMBOLS = [
     "idahip_krylov_upload_prec",
     "idahip_set_krylov_rounds", "idahip_krylov_rounds", "idahip_krylov_rounds_put_counters", "idahip_krylov_rounds_get_counters",
     "idahip_set_suppress_alg", "idahip_suppress_alg", "idahip_wrms_masked",
+    "idahip_set_mass_action", "idahip_mass_action_pattern", "idahip_mass_action_jac",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
@@ -60,6 +61,8 @@ ENS_SYMBOLS = [
     "idaens_total_rounds", "idaens_trace_system", "idaens_trace_len", "idaens_trace_get", "idaens_calc_ic",
     "idaens_set_stop_time", "idaens_get_stop_time",
 ]
+
+from . import mass_action  # noqa: E402,F401  (IDAHIP_MASS_ACTION: a network checked and flattened, numpy only)
 
 _libs = None
 
@@ -115,6 +118,9 @@ def load():
     H.idahip_set_tolerances.argtypes = [vp, cd, dp, ci]
     H.idahip_set_problem_params.argtypes = [vp, ci, ci, dp, ci]
     H.idahip_set_linear_dense.argtypes = [vp, ci, ci, dp, dp, dp]
+    H.idahip_set_mass_action.argtypes = [vp, ci, i32p, ci, i32p, i32p, dp, dp]
+    H.idahip_mass_action_pattern.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    H.idahip_mass_action_jac.argtypes = [vp, ci, cd, dp]
     H.idahip_upload.argtypes = [vp, ci, ci, ci, dp]
     H.idahip_download.argtypes = [vp, ci, ci, ci, dp]
     H.idahip_download_lu.argtypes = [vp, ci, dp, i64p]
@@ -444,6 +450,36 @@ class Ctx:
     def set_problem_params(self, params, first=0):
         p = _f64(params).reshape(-1, _f64(params).shape[-1] if np.ndim(params) > 1 else 1)
         self._chk(self.H.idahip_set_problem_params(self.h, first, p.shape[0], _p(p), p.shape[1]), "set_problem_params")
+
+    def set_mass_action(self, reactions, d):
+        """IDAHIP_MASS_ACTION: the reaction network, once per ctx (include/ida_hip.h). reactions = [(reactants, {row: nu, ...}), ...]
+        with at most three reactant species per reaction (repeats allowed); d [n] the coefficients of y'. Checked here
+        (idahip.mass_action.flatten, a NetworkError names the first offending item) and again by the library."""
+        from . import mass_action
+        slots, rows, reacs, nu, dd = mass_action.flatten(self.n, reactions, d)
+        self.set_mass_action_raw(slots, rows, reacs, nu, dd)
+
+    def set_mass_action_raw(self, slots, rows, reacs, nu, d):
+        """idahip_set_mass_action on the flat arrays, unchecked on this side (the library's own refusals)."""
+        slots, rows, reacs, nu, d = _i32(slots).reshape(-1, 3), _i32(rows), _i32(reacs), _f64(nu), _f64(d)
+        assert rows.size == reacs.size == nu.size and d.size == self.n
+        self._chk(self.H.idahip_set_mass_action(self.h, slots.shape[0], _p(slots, i32p), rows.size, _p(rows, i32p), _p(reacs, i32p), _p(nu), _p(d)),
+                  "set_mass_action")
+
+    def mass_action_pattern(self):
+        """(nnz, ml, mu) of the network's Jacobian pattern: its positions (every diagonal one included) and half-bandwidths."""
+        nnz, ml, mu = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.H.idahip_mass_action_pattern(self.h, C.byref(nnz), C.byref(ml), C.byref(mu)), "mass_action_pattern")
+        return nnz.value, ml.value, mu.value
+
+    def mass_action_jac(self, cj, idx=None):
+        """The analytic Jacobian of the listed systems at the ctx's yy -> [nsys][n][n], column-major per system (J[q, j, i] = J(i, j))."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        cj = np.broadcast_to(_f64(cj), idx.shape)
+        J = np.empty((idx.size, self.n, self.n))
+        for q, s in enumerate(idx):  # (idahip_mass_action_jac is an inspection call: one system at a time)
+            self._chk(self.H.idahip_mass_action_jac(self.h, int(s), float(cj[q]), _p(J[q])), "mass_action_jac")
+        return J
 
     def set_linear_dense(self, A, B, c, first=0):
         """A, B: [count][n][n] stored column-major per system, i.e. A[s, j, i] = A_s(i, j); c: [count][n]."""

@@ -313,6 +313,130 @@ def bruss1d(m=2048, batch=256, alpha=0.02):
             "touts": 0.25 * np.arange(1, 5)}
 
 
+# ---------------------------------------------------------------------------------------- mass-action networks (IDAHIP_MASS_ACTION)
+# A network problem carries "reactions" = [(reactants, {row: nu})], "d" [n] and "params" = the rate constants [batch][R]
+# (include/ida_hip.h, idahip/mass_action.py); make_ctx uploads the network, then the constants.
+def _network(n, reactions, d, k, yy0, yp0, rtol, atol, touts):
+    return {"kind": "mass_action", "n": n, "reactions": reactions, "d": np.asarray(d, dtype=np.float64),
+            "params": np.ascontiguousarray(k, dtype=np.float64), "yy0": yy0, "yp0": yp0, "rtol": rtol, "atol": atol, "touts": touts}
+
+
+def roberts_network():
+    """Roberts (config 1) as a network: y0' = -0.04 y0 + 1e4 y1 y2, y1' = 0.04 y0 - 1e4 y1 y2 - 3e7 y1^2, and the conservation row
+    y0 + y1 + y2 - 1 = 0 as three first-order entries (nu = -1, k = 1) and one zero-order entry (nu = +1, k = 1). The differential
+    rows are y' - f here and f - y' in IDAHIP_ROBERTS: the same solution, the residual's sign reversed."""
+    p = roberts()
+    reactions = [((0,), {0: -1.0, 1: 1.0}), ((1, 2), {0: 1.0, 1: -1.0}), ((1, 1), {1: -1.0}),
+                 ((0,), {2: -1.0}), ((1,), {2: -1.0}), ((2,), {2: -1.0}), ((), {2: 1.0})]
+    k = np.array([[0.04, 1.0e4, 3.0e7, 1.0, 1.0, 1.0, 1.0]])
+    return _network(3, reactions, [1.0, 1.0, 0.0], k, p["yy0"], p["yp0"], p["rtol"], p["atol"], p["touts"])
+
+
+def lorenz63_network(batch=1024, seed=63):
+    """Lorenz63 (config 2) as a network, the systems and parameters of lorenz63(batch, seed): products expanded,
+    y0' = p y1 - p y0, y1' = r y0 - y0 y2 - y1, y2' = y0 y1 - b y2 (negative values are fine for polynomial kinetics)."""
+    q = lorenz63(batch, seed)
+    p, r, b = q["params"][0]
+    reactions = [((1,), {0: 1.0}), ((0,), {0: -1.0}), ((0,), {1: 1.0}), ((0, 2), {1: -1.0}), ((1,), {1: -1.0}),
+                 ((0, 1), {2: 1.0}), ((2,), {2: -1.0})]
+    k = np.tile(np.array([p, p, r, 1.0, 1.0, 1.0, b]), (batch, 1))
+    return _network(3, reactions, [1.0, 1.0, 1.0], k, q["yy0"], q["yp0"], q["rtol"], q["atol"], q["touts"])
+
+
+def bruss1d_network(m=2048, batch=256, alpha=0.02):
+    """The systems of bruss1d(m, batch, alpha) as a network: per interior grid point the reactions 0 -> u (a), u -> 0 (b + 1),
+    u -> v (b), 2u + v -> 3u (1) and the six diffusion terms (d, 2d, d for each species), one reaction per term; the end points are
+    algebraic rows ub - u = 0, vb - v = 0. Pattern bandwidths (2, 2)."""
+    q = bruss1d(m, batch, alpha)
+    n = 2 * m
+    P = q["params"]
+    a, b, dd, ub, vb = (P[:, c] for c in range(5))
+    one = np.ones(batch)
+    reactions, cols = [], []
+
+    def add(reactants, stoich, kcol):
+        reactions.append((tuple(reactants), stoich))
+        cols.append(kcol)
+
+    d = np.ones(n)
+    for i in range(m):
+        u, v = 2 * i, 2 * i + 1
+        if i == 0 or i == m - 1:
+            d[u] = d[v] = 0.0
+            add((), {u: 1.0}, ub)
+            add((u,), {u: -1.0}, one)
+            add((), {v: 1.0}, vb)
+            add((v,), {v: -1.0}, one)
+            continue
+        add((), {u: 1.0}, a)
+        add((u,), {u: -1.0}, b + 1.0)
+        add((u, u, v), {u: 1.0, v: -1.0}, one)
+        add((u - 2,), {u: 1.0}, dd)
+        add((u,), {u: -1.0}, 2.0 * dd)
+        add((u + 2,), {u: 1.0}, dd)
+        add((u,), {v: 1.0}, b)
+        add((v - 2,), {v: 1.0}, dd)
+        add((v,), {v: -1.0}, 2.0 * dd)
+        add((v + 2,), {v: 1.0}, dd)
+    return _network(n, reactions, d, np.stack(cols, axis=1), q["yy0"], q["yp0"], q["rtol"], q["atol"], q["touts"])
+
+
+def reaction_chain(n=12, batch=64, seed=7):
+    """A seeded reaction network of n >= 6 species for the table-driven kernels. Species n-2 is inert (a row without entries,
+    y' = 0); the others react along the chain 0, 1, ..., n-3, n-1: neighbours c, c' by the reversible first-order pair c <-> c' and
+    the reversible second-order pair c + c' <-> 2 c', all of which conserve the sum of the reacting species. Species 0 is a hub: it
+    exchanges with every other reacting species through further first-order channels until its row has more than 64 entries. The
+    last row is that conservation law (algebraic, d = 0): -sum + total = 0, the total as the rate constant of a zero-order reaction.
+    Rate constants: 10^U(-3, 3) per reaction and system (PCG64 `seed`); y(0) = U(0.5, 1.5), y_{n-1}(0) from the conservation
+    row, y'(0) = the right-hand side. rtol 1e-6, atol 1e-9."""
+    from . import mass_action
+    assert n >= 6
+    rng = np.random.Generator(np.random.PCG64(seed))
+    chain = list(range(n - 2)) + [n - 1]
+    reactions = []
+    for c, cn in zip(chain[:-1], chain[1:]):
+        reactions.append(((c,), {c: -1.0, cn: 1.0}))
+        reactions.append(((cn,), {cn: -1.0, c: 1.0}))
+        reactions.append(((c, cn), {c: -1.0, cn: 1.0}))
+        reactions.append(((cn, cn), {cn: -1.0, c: 1.0}))
+    hub_entries, j = 4, 0
+    while hub_entries <= 64:
+        partner = chain[2 + j % (len(chain) - 2)]
+        reactions.append(((0,), {0: -1.0, partner: 1.0}))
+        reactions.append(((partner,), {partner: -1.0, 0: 1.0}))
+        hub_entries += 2
+        j += 1
+    nkin = len(reactions)
+    last = n - 1
+    # the conservation row replaces the last species' differential equation: drop its kinetic entries
+    reactions = [(r, {row: v for row, v in st.items() if row != last}) for r, st in reactions]
+    for c in chain:
+        reactions.append(((c,), {last: -1.0}))
+    reactions.append(((), {last: 1.0}))
+    R = len(reactions)
+    d = np.ones(n)
+    d[last] = 0.0
+    k = np.ones((batch, R))
+    k[:, :nkin] = 10.0 ** rng.uniform(-3.0, 3.0, size=(batch, nkin))
+    y0 = rng.uniform(0.5, 1.5, size=(batch, n))
+    total = 2.0 * len(chain)  # the conserved sum every system starts with
+    tab = mass_action.tables(n, reactions, d)
+    yp0 = np.zeros((batch, n))
+    for s in range(batch):
+        partial = 0.0
+        for c in chain[:-1]:
+            partial = partial + y0[s, c]
+        y0[s, last] = total - partial
+        # the constant term, so that the row's ordered sum is exactly zero at y(0)
+        k[s, R - 1] = 0.0
+        k[s, R - 1] = -mass_action.rhs(tab, k[s], y0[s])[last]
+        f = mass_action.rhs(tab, k[s], y0[s])
+        assert f[last] == 0.0
+        yp0[s] = f
+        yp0[s, last] = -sum(f[c] for c in chain[:-1])
+    return _network(n, reactions, d, k, y0, yp0, 1.0e-6, np.array([1.0e-9]), 0.01 * np.arange(1, 4))
+
+
 def make_ctx(prob, device=0, stream=None, band=False, krylov=None):
     """Create a device context for a generated problem and load its data (import kept local: this module is also
     used by CPU-only tests). band=True: a band ctx -- (1, 1) for heat1d, (2, 2) for bruss1d, prob["band"] for a host-callback problem with a band
@@ -334,6 +458,9 @@ def make_ctx(prob, device=0, stream=None, band=False, krylov=None):
             ctx.set_linear_dense(prob["A"][f:f + step], prob["B"][f:f + step], prob["c"][f:f + step], first=f)
     elif prob["kind"] == "host_callback":
         ctx.set_host_problem(prob["res"], prob["jac"])
+    elif prob["kind"] == "mass_action":
+        ctx.set_mass_action(prob["reactions"], prob["d"])
+        ctx.set_problem_params(prob["params"])
     elif "params" in prob:
         ctx.set_problem_params(prob["params"])
     return ctx
