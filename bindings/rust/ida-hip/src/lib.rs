@@ -366,6 +366,30 @@ impl Ctx {
         self.check(rc).map(|_| ())
     }
 
+    /// The same with rate laws, instead of [`Ctx::set_mass_action`] (once per context across the two): `factors` [nfac][5] =
+    /// (reaction, op, species, constant, exponent) with op 1 (IDAHIP_RATE_SAT) or 2 (IDAHIP_RATE_INH), at most 4 per reaction,
+    /// exponent 1..=4; `nconst` constants per system follow the rate constants in the parameters (nparam = nreac + nconst).
+    #[allow(clippy::too_many_arguments)]
+    pub fn set_rate_network(&mut self, reactants: &[i32], factors: &[i32], nconst: usize, rows: &[i32], reacs: &[i32], nu: &[f64], d: &[f64]) -> Result<(), Error> {
+        assert!(reactants.len() % 3 == 0 && factors.len() % 5 == 0 && rows.len() == reacs.len() && rows.len() == nu.len() && d.len() == self.n());
+        let rc = unsafe {
+            sys::idahip_set_rate_network(
+                self.raw,
+                (reactants.len() / 3) as c_int,
+                reactants.as_ptr(),
+                (factors.len() / 5) as c_int,
+                factors.as_ptr(),
+                nconst as c_int,
+                rows.len() as c_int,
+                rows.as_ptr(),
+                reacs.as_ptr(),
+                nu.as_ptr(),
+                d.as_ptr(),
+            )
+        };
+        self.check(rc).map(|_| ())
+    }
+
     /// (positions, ml, mu) of the network's Jacobian pattern, every diagonal position included.
     pub fn mass_action_pattern(&mut self) -> Result<(usize, usize, usize), Error> {
         let (mut nnz, mut ml, mut mu): (c_int, c_int, c_int) = (0, 0, 0);

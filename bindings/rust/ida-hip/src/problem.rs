@@ -52,9 +52,13 @@ where
 }
 
 /// A mass-action reaction network (`Problem::MassAction`, include/ida_hip.h): the tables `Ctx::set_mass_action` takes, built one
-/// reaction at a time. Entries are numbered in the order they are added, so within a row they keep that order.
+/// reaction at a time. Entries are numbered in the order they are added, so within a row they keep that order. A reaction may carry
+/// rate-law factors (`factor`: Michaelis-Menten and Hill terms over `constants` per-system constants); the network then goes up
+/// through `Ctx::set_rate_network`, and a system's parameters are its rate constants followed by its constants.
 pub struct MassAction {
     n: usize,
+    nconst: usize,
+    factors: Vec<i32>,
     reactants: Vec<i32>,
     rows: Vec<i32>,
     reacs: Vec<i32>,
@@ -65,7 +69,7 @@ pub struct MassAction {
 impl MassAction {
     /// `n` unknowns, every row differential (d = 1.0) and no reaction yet.
     pub fn new(n: usize) -> Self {
-        MassAction { n, reactants: Vec::new(), rows: Vec::new(), reacs: Vec::new(), nu: Vec::new(), d: vec![1.0; n] }
+        MassAction { n, nconst: 0, factors: Vec::new(), reactants: Vec::new(), rows: Vec::new(), reacs: Vec::new(), nu: Vec::new(), d: vec![1.0; n] }
     }
     /// Reaction of order `reactants.len()` <= 3 (a species may repeat: y1^2 is `&[1, 1]`) with the stoichiometric coefficient `nu`
     /// in each `(row, nu)` of `stoich`. Returns the reaction's index: the position of its rate constant in a system's parameters.
@@ -83,6 +87,27 @@ impl MassAction {
         }
         r
     }
+    /// `nconst` constants K per system (they follow the rate constants in a system's parameters) for the factors to name.
+    pub fn constants(&mut self, nconst: usize) -> &mut Self {
+        self.nconst = nconst;
+        self
+    }
+    /// A factor of reaction `reaction`, after those it already has (at most 4): `RateLaw::Sat` is y^h / (K^h + y^h), `RateLaw::Inh` is
+    /// K^h / (K^h + y^h), with y = `species`, K = constant number `constant`, and the exponent 1 <= `h` <= 4.
+    pub fn factor(&mut self, reaction: usize, law: RateLaw, species: usize, constant: usize, h: u32) -> &mut Self {
+        assert!(reaction < self.nreac() && species < self.n && constant < self.nconst && (1..=4).contains(&h));
+        assert!(self.factors.chunks(5).filter(|f| f[0] as usize == reaction).count() < 4);
+        let op: i32 = match law {
+            RateLaw::Sat => 1, // IDAHIP_RATE_SAT
+            RateLaw::Inh => 2, // IDAHIP_RATE_INH
+        };
+        self.factors.extend_from_slice(&[reaction as i32, op, species as i32, constant as i32, h as i32]);
+        self
+    }
+    /// Parameters per system: the rate constants, then the constants.
+    pub fn nparam(&self) -> usize {
+        self.nreac() + self.nconst
+    }
     /// Row `row` is algebraic: d = 0.0 (a conservation law written as entries that sum to zero).
     pub fn algebraic(&mut self, row: usize) -> &mut Self {
         self.d[row] = 0.0;
@@ -94,6 +119,18 @@ impl MassAction {
     }
     /// Uploads the network to a `Problem::MassAction` context.
     pub fn apply(&self, ctx: &mut Ctx) -> Result<(), Error> {
-        ctx.set_mass_action(&self.reactants, &self.rows, &self.reacs, &self.nu, &self.d)
+        if self.factors.is_empty() && self.nconst == 0 {
+            return ctx.set_mass_action(&self.reactants, &self.rows, &self.reacs, &self.nu, &self.d);
+        }
+        ctx.set_rate_network(&self.reactants, &self.factors, self.nconst, &self.rows, &self.reacs, &self.nu, &self.d)
     }
+}
+
+/// The rate laws a reaction's factor can be (include/ida_hip.h, IDAHIP_RATE_SAT / IDAHIP_RATE_INH).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum RateLaw {
+    /// y^h / (K^h + y^h): Michaelis-Menten at h = 1, an activating Hill term above
+    Sat,
+    /// K^h / (K^h + y^h): inhibition
+    Inh,
 }

@@ -67,7 +67,26 @@ typedef enum {
  * and the device lock-step rounds for 8 < n <= 4096; idahip_create_band and idahip_create_krylov refuse the kind (-2), and the
  * one-thread device stepper (n <= 8) does not take it. Until idahip_set_mass_action has been called, every call that would evaluate
  * the problem -- idahip_nls_sys*, idahip_nls_lsetup*, idahip_jac_dq, idahip_newton_iter2, idahip_ic_res / _setup* / _trial,
- * idahip_round_solve, idahip_set_problem_params, idaens_create -- returns -2 with a text, and nothing is launched. */
+ * idahip_round_solve, idahip_set_problem_params, idaens_create -- returns -2 with a text, and nothing is launched.
+ *
+ * RATE LAWS (idahip_set_rate_network instead of idahip_set_mass_action): a reaction may carry FACTORS, at most 4, in the caller's
+ * order. A factor is (op, species s, constant c, exponent h) with op IDAHIP_RATE_SAT (y^h / (K^h + y^h): Michaelis-Menten at h = 1,
+ * an activating Hill term above) or IDAHIP_RATE_INH (K^h / (K^h + y^h)), 0 <= s < n, 0 <= c < nconst, 1 <= h <= 4. The constants
+ * are per system and follow the rate constants in the parameter vector: [k_0 .. k_{R-1}, K_0 .. K_{nconst-1}], nparam = R + nconst.
+ *   pw(x, h):   p = x;  (h - 1 times) p = p * x
+ *   f(factor):  yh = pw(y_s, h);  Kh = pw(K_c, h);  den = Kh + yh;   SAT: f = yh / den;   INH: f = Kh / den
+ *   df(factor): num = Kh if h == 1, else num = ((double)h * Kh) * pw(y_s, h - 1);   q = num / (den * den);   SAT: df = q;   INH: df = -q
+ *   rate:       q_r as above, then q_r = q_r * f(factor) for the reaction's factors, in order; the residual is unchanged otherwise
+ *   J:          position (i, j) takes the row's entries in order; within an entry first one term per slot p with s_r[p] == j, in
+ *               slot order: g as above (k_r times the other slots), then g = g * f(factor) for every factor in order; then one
+ *               term per factor whose species is j, in factor order: g = k_r times ALL slots in order, then times the factors in
+ *               order with df in place of f for that one factor. Each term is nu_e * g; sum, base and sign as above.
+ * The pattern gains the positions reached through a factor. den == 0 is not trapped: the result is what IEEE gives (NaN, +-inf),
+ * and a NaN acc is F_i as it is, sign included (the subtraction does not touch it).
+ * A network without factors is the polynomial network above, by the same tables and the same kernels. */
+#define IDAHIP_RATE_SAT 1
+#define IDAHIP_RATE_INH 2
+#define IDAHIP_RATE_MAX_FACTORS 4
 
 /* IDAHIP_BRUSS1D: the nonlinear, stiff, banded device problem. m grid points, two species interleaved: n = 2m (even, n >= 10),
  * y[2i] = u_i, y[2i+1] = v_i; parameters [a, b, d, ub, vb] per system (idahip_set_problem_params, nparam = 5), d = the diffusion
@@ -305,7 +324,7 @@ int idahip_set_constraints(idahip_ctx* ctx, const double* hC /* [n] or NULL = cl
 /* 1 if constraints are set (hC, when non-null, receives them), 0 if not, -1 for a null ctx */
 int idahip_constraints(const idahip_ctx* ctx, double* hC);
 /* per-system problem parameters, systems [first, first+count): LORENZ63 [count][3], HEAT1D [count][1], BRUSS1D [count][5],
- * MASS_ACTION [count][nreac] */
+ * MASS_ACTION [count][nreac] (idahip_set_rate_network: [count][nreac + nconst]) */
 int idahip_set_problem_params(idahip_ctx* ctx, int first, int count, const double* hParams, int nparam);
 /* IDAHIP_MASS_ACTION: the network, once per ctx, after idahip_create and before anything evaluates the problem. reactants
  * [nreac][3], rows / reacs / nu [nentries], d [n] as defined above. Everything is validated -- index ranges, -1 only in trailing
@@ -314,6 +333,13 @@ int idahip_set_problem_params(idahip_ctx* ctx, int first, int count, const doubl
  * of the Jacobian's pattern, and allocates the rate constants [batch][nreac] (all 0.0 until idahip_set_problem_params). */
 int idahip_set_mass_action(idahip_ctx* ctx, int nreac, const int32_t* reactants /*[nreac][3]*/, int nentries, const int32_t* rows,
                            const int32_t* reacs, const double* nu, const double* d /*[n]*/);
+/* The same with rate laws (defined above), instead of idahip_set_mass_action: once per ctx across the two setters. factors [nfac][5] =
+ * (reaction, op, species, constant, exponent), in any order of reactions; the factors of one reaction keep the caller's order.
+ * nconst >= 0 constants per system follow the rate constants (nparam = nreac + nconst); a constant no factor uses is allowed.
+ * Validated as above, and: every factor's reaction, op, species, constant and exponent range, at most 4 factors per reaction.
+ * With nfac = 0 and nconst = 0 it is idahip_set_mass_action. */
+int idahip_set_rate_network(idahip_ctx* ctx, int nreac, const int32_t* reactants /*[nreac][3]*/, int nfac, const int32_t* factors /*[nfac][5]*/,
+                            int nconst, int nentries, const int32_t* rows, const int32_t* reacs, const double* nu, const double* d /*[n]*/);
 /* the pattern of the network's Jacobian: its positions (*nnz) and half-bandwidths (*ml = max i - j, *mu = max j - i); any pointer
  * may be null. -2 on a ctx of another kind and before idahip_set_mass_action. */
 int idahip_mass_action_pattern(idahip_ctx* ctx, int* nnz, int* ml, int* mu);

@@ -33,7 +33,8 @@ struct Slot {
     bool pending = false;
 };
 
-struct MaNet;  // mass_action.hpp
+struct MaNet;     // mass_action.hpp
+struct MaLawNet;  // mass_action.hpp
 
 }  // namespace idahip
 
@@ -139,6 +140,7 @@ struct idahip_ctx {
     // and what idahip_mass_action_pattern reports; ma == nullptr: the network is not set yet
     void* ma_blob = nullptr;
     idahip::MaNet* ma = nullptr;
+    idahip::MaLawNet* ma_law = nullptr;  // the same network with its factors (idahip_set_rate_network with nfac > 0), else null
     int ma_nnz = 0, ma_ml = 0, ma_mu = 0;
     int ma_force_wg = 0;  // measurements: the workgroup-per-system residual at every n (IDAHIP_MA_WG, read at idahip_create)
     idahip_res_fn cb_res = nullptr;                   // HOST_CALLBACK

@@ -68,19 +68,34 @@ int ma_unset(idahip_ctx* c, const char* who) {
     return 0;
 }
 
+// does the network carry rate-law factors (idahip_set_rate_network with nfac > 0)? Every launch of a mass_action.hpp kernel picks
+// its instantiation by this: a polynomial network runs <false>, the code without factors
+bool ma_laws(const idahip_ctx* c) { return c->ma_law != nullptr; }
+// the kernel argument of an instantiation: the polynomial network's struct, or the one with the factors
+template <bool LAWS>
+const MaNetOf<LAWS>& ma_net(const idahip_ctx* c) {
+    if constexpr (LAWS) return *c->ma_law;
+    else return *c->ma;
+}
+
 // the residual of a mass-action ctx (mass_action.hpp): n <= 64 one wavefront per system, above one workgroup per system
-template <class ARGS>
-void launch_ma_sys(idahip_ctx* c, const ARGS& a, int nsys) {
+template <bool LAWS, class ARGS>
+void launch_ma_sys_as(idahip_ctx* c, const ARGS& a, int nsys) {
     const int n = c->n;
     if (n <= MA_WAVE_MAX_N && !c->ma_force_wg) {
-        hipLaunchKernelGGL(ma_sys_wave_kernel<ARGS>, dim3((nsys + MA_SPW - 1) / MA_SPW), dim3(256), 0, c->stream, a, *c->ma, (const double*)c->params, nsys);
+        hipLaunchKernelGGL((ma_sys_wave_kernel<LAWS, ARGS>), dim3((nsys + MA_SPW - 1) / MA_SPW), dim3(256), 0, c->stream, a, ma_net<LAWS>(c), (const double*)c->params, nsys);
         return;
     }
     bool solve = false;
     if constexpr (ARGS::IC) solve = a.lu != nullptr;
     const size_t shm = (solve ? 2 : 1) * sizeof(double) * n;
-    if (n % 2 == 0) hipLaunchKernelGGL((ma_sys_kernel<2, ARGS>), dim3(nsys), dim3(256), shm, c->stream, a, *c->ma, (const double*)c->params);
-    else hipLaunchKernelGGL((ma_sys_kernel<1, ARGS>), dim3(nsys), dim3(256), shm, c->stream, a, *c->ma, (const double*)c->params);
+    if (n % 2 == 0) hipLaunchKernelGGL((ma_sys_kernel<LAWS, 2, ARGS>), dim3(nsys), dim3(256), shm, c->stream, a, ma_net<LAWS>(c), (const double*)c->params);
+    else hipLaunchKernelGGL((ma_sys_kernel<LAWS, 1, ARGS>), dim3(nsys), dim3(256), shm, c->stream, a, ma_net<LAWS>(c), (const double*)c->params);
+}
+template <class ARGS>
+void launch_ma_sys(idahip_ctx* c, const ARGS& a, int nsys) {
+    if (ma_laws(c)) launch_ma_sys_as<true>(c, a, nsys);
+    else launch_ma_sys_as<false>(c, a, nsys);
 }
 
 // grid.y of the kernels that split one system's work into chunks: the launch reaches 2048 workgroups, or `cap` chunks per system
@@ -332,6 +347,7 @@ int idahip_destroy(idahip_ctx* c) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete c->ma;
+    delete c->ma_law;
     if (c->rnd_host) (void)hipHostFree(c->rnd_host);
     if (c->cb_jpin) (void)hipHostFree(c->cb_jpin);
     if (c->cb_jdev) (void)hipFree(c->cb_jdev);
@@ -578,33 +594,58 @@ int idahip_set_linear_dense(idahip_ctx* c, int first, int count, const double* h
 }
 
 // IDAHIP_MASS_ACTION: validate the network, build the residual's row-CSR and the Jacobian pattern's CSR (mass_action.hpp) on the host,
-// upload both in one allocation, and allocate the rate constants [batch][nreac]
-int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, int nentries, const int32_t* rows, const int32_t* reacs,
-                           const double* nu, const double* d) {
+// upload both in one allocation, and allocate the parameters [batch][nreac + nconst]. Both setters end here (who: the one called);
+// without factors the tables are the polynomial network's, and nothing of the rate laws is uploaded.
+static int set_network(idahip_ctx* c, const char* who, int nreac, const int32_t* reactants, int nfac, const int32_t* factors, int nconst,
+                       int nentries, const int32_t* rows, const int32_t* reacs, const double* nu, const double* d) {
     DevGuard dev_guard__(c);
     if (!c) return -1;
-    if (c->kind != IDAHIP_MASS_ACTION) return fail(c, -2, "idahip_set_mass_action: not an IDAHIP_MASS_ACTION ctx (kind %d)", (int)c->kind);
-    if (c->ma) return fail(c, -2, "idahip_set_mass_action: the reaction network is already set (once per ctx)");
-    if (nreac < 1) return fail(c, -2, "idahip_set_mass_action: nreac = %d, at least one reaction", nreac);
-    if (nentries < 0) return fail(c, -2, "idahip_set_mass_action: nentries = %d is negative", nentries);
-    if (!reactants || !d || (nentries > 0 && (!rows || !reacs || !nu))) return null_argument(c);
+    if (c->kind != IDAHIP_MASS_ACTION) return fail(c, -2, "%s: not an IDAHIP_MASS_ACTION ctx (kind %d)", who, (int)c->kind);
+    if (c->ma) return fail(c, -2, "%s: the reaction network is already set (once per ctx)", who);
+    if (nreac < 1) return fail(c, -2, "%s: nreac = %d, at least one reaction", who, nreac);
+    if (nentries < 0) return fail(c, -2, "%s: nentries = %d is negative", who, nentries);
+    if (nfac < 0) return fail(c, -2, "%s: nfac = %d is negative", who, nfac);
+    if (nconst < 0) return fail(c, -2, "%s: nconst = %d is negative", who, nconst);
+    if (!reactants || !d || (nentries > 0 && (!rows || !reacs || !nu)) || (nfac > 0 && !factors)) return null_argument(c);
     const int n = c->n;
     for (int r = 0; r < nreac; ++r) {
         bool ended = false;
         for (int p = 0; p < 3; ++p) {
             const int sp = reactants[3 * r + p];
-            if (sp < -1 || sp >= n) return fail(c, -2, "idahip_set_mass_action: reaction %d, slot %d: species %d outside [0, %d)", r, p, sp, n);
+            if (sp < -1 || sp >= n) return fail(c, -2, "%s: reaction %d, slot %d: species %d outside [0, %d)", who, r, p, sp, n);
             if (sp == -1) ended = true;
-            else if (ended) return fail(c, -2, "idahip_set_mass_action: reaction %d, slot %d: a species after an unused slot (-1 only in trailing slots)", r, p);
+            else if (ended) return fail(c, -2, "%s: reaction %d, slot %d: a species after an unused slot (-1 only in trailing slots)", who, r, p);
+        }
+    }
+    // the factors, reaction by reaction: a stable counting sort keeps the caller's order within a reaction
+    std::vector<int> fac_ptr(nreac + 1, 0);
+    for (int f = 0; f < nfac; ++f) {
+        const int32_t* q = factors + 5 * f;
+        if (q[0] < 0 || q[0] >= nreac) return fail(c, -2, "%s: factor %d: reaction %d outside [0, %d)", who, f, q[0], nreac);
+        if (q[1] != IDAHIP_RATE_SAT && q[1] != IDAHIP_RATE_INH)
+            return fail(c, -2, "%s: factor %d: op %d is neither IDAHIP_RATE_SAT (1) nor IDAHIP_RATE_INH (2)", who, f, q[1]);
+        if (q[2] < 0 || q[2] >= n) return fail(c, -2, "%s: factor %d: species %d outside [0, %d)", who, f, q[2], n);
+        if (q[3] < 0 || q[3] >= nconst) return fail(c, -2, "%s: factor %d: constant %d outside [0, %d)", who, f, q[3], nconst);
+        if (q[4] < 1 || q[4] > 4) return fail(c, -2, "%s: factor %d: exponent %d outside [1, 4]", who, f, q[4]);
+        if (++fac_ptr[q[0] + 1] > IDAHIP_RATE_MAX_FACTORS)
+            return fail(c, -2, "%s: factor %d: reaction %d has more than %d factors", who, f, q[0], IDAHIP_RATE_MAX_FACTORS);
+    }
+    for (int r = 0; r < nreac; ++r) fac_ptr[r + 1] += fac_ptr[r];
+    std::vector<MaFac> facs((size_t)nfac);
+    {
+        std::vector<int> fill(fac_ptr.begin(), fac_ptr.end() - 1);
+        for (int f = 0; f < nfac; ++f) {
+            const int32_t* q = factors + 5 * f;
+            facs[(size_t)fill[q[0]]++] = MaFac{q[1], q[2], q[3], q[4]};
         }
     }
     for (int e = 0; e < nentries; ++e) {
-        if (rows[e] < 0 || rows[e] >= n) return fail(c, -2, "idahip_set_mass_action: entry %d: row %d outside [0, %d)", e, rows[e], n);
-        if (reacs[e] < 0 || reacs[e] >= nreac) return fail(c, -2, "idahip_set_mass_action: entry %d: reaction %d outside [0, %d)", e, reacs[e], nreac);
-        if (!std::isfinite(nu[e])) return fail(c, -2, "idahip_set_mass_action: entry %d: nu = %g is not finite", e, nu[e]);
+        if (rows[e] < 0 || rows[e] >= n) return fail(c, -2, "%s: entry %d: row %d outside [0, %d)", who, e, rows[e], n);
+        if (reacs[e] < 0 || reacs[e] >= nreac) return fail(c, -2, "%s: entry %d: reaction %d outside [0, %d)", who, e, reacs[e], nreac);
+        if (!std::isfinite(nu[e])) return fail(c, -2, "%s: entry %d: nu = %g is not finite", who, e, nu[e]);
     }
     for (int i = 0; i < n; ++i)
-        if (!std::isfinite(d[i])) return fail(c, -2, "idahip_set_mass_action: d[%d] = %g is not finite", i, d[i]);
+        if (!std::isfinite(d[i])) return fail(c, -2, "%s: d[%d] = %g is not finite", who, i, d[i]);
     // the residual's rows: a stable counting sort of the entries by row keeps the caller's order within a row
     std::vector<int> row_ptr(n + 1, 0);
     for (int e = 0; e < nentries; ++e) row_ptr[rows[e] + 1] += 1;
@@ -618,8 +659,10 @@ int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, i
         }
     }
     // the Jacobian's pattern, column-major: every diagonal position, and (i, j) for every slot of an entry of row i that holds j;
-    // a position's terms in the header's order (the row's entries in order, within an entry the slots in order)
-    std::map<long, std::vector<MaTerm>> pat;
+    // a position's terms in the header's order (the row's entries in order, within an entry the slots in order, then the reaction's
+    // factors in order: those terms keep all three slots and name the factor they differentiate)
+    struct JTerm { MaTerm t; int dfac; };
+    std::map<long, std::vector<JTerm>> pat;
     for (int i = 0; i < n; ++i) {
         pat[(long)i * n + i];
         for (int e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
@@ -629,13 +672,16 @@ int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, i
                 int o[2] = {-1, -1}, k = 0;
                 for (int q = 0; q < 3; ++q)
                     if (q != p && s[q] >= 0) o[k++] = s[q];
-                pat[(long)s[p] * n + i].push_back(MaTerm{t.nu, t.r, o[0], o[1], -1});
+                pat[(long)s[p] * n + i].push_back(JTerm{MaTerm{t.nu, t.r, o[0], o[1], -1}, -1});
             }
+            for (int f = fac_ptr[t.r]; f < fac_ptr[t.r + 1]; ++f)
+                pat[(long)facs[(size_t)f].s * n + i].push_back(JTerm{t, f - fac_ptr[t.r]});
         }
     }
     const int nnz = (int)pat.size();
     std::vector<int> col_ptr(n + 1, 0), pos_row, pos_ptr;
     std::vector<MaTerm> jterms;
+    std::vector<int> jdfac;
     pos_row.reserve(nnz);
     pos_ptr.reserve(nnz + 1);
     int ml = 0, mu = 0;
@@ -644,7 +690,10 @@ int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, i
         col_ptr[j + 1] += 1;
         pos_row.push_back(i);
         pos_ptr.push_back((int)jterms.size());
-        jterms.insert(jterms.end(), kv.second.begin(), kv.second.end());
+        for (const JTerm& jt : kv.second) {
+            jterms.push_back(jt.t);
+            jdfac.push_back(jt.dfac);
+        }
         ml = std::max(ml, i - j);
         mu = std::max(mu, j - i);
     }
@@ -655,7 +704,12 @@ int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, i
     const size_t off_d = (ints * sizeof(int) + 7) & ~(size_t)7;
     const size_t off_rt = off_d + sizeof(double) * n;
     const size_t off_jt = off_rt + sizeof(MaTerm) * rterms.size();
-    const size_t total = off_jt + sizeof(MaTerm) * jterms.size();
+    // (rate laws only, after the polynomial network's tables: the factors, 16 bytes each, then fac_ptr and jdfac)
+    const size_t off_fc = off_jt + sizeof(MaTerm) * jterms.size();
+    const size_t off_fp = off_fc + (nfac > 0 ? sizeof(MaFac) * facs.size() : 0);
+    const size_t off_jd = off_fp + (nfac > 0 ? sizeof(int) * fac_ptr.size() : 0);
+    const size_t total = off_jd + (nfac > 0 ? sizeof(int) * jdfac.size() : 0);
+    const int nparam = nreac + nconst;
     std::vector<char> blob(total, 0);
     int* hi = reinterpret_cast<int*>(blob.data());
     std::memcpy(hi, row_ptr.data(), sizeof(int) * (n + 1));
@@ -665,19 +719,24 @@ int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, i
     std::memcpy(blob.data() + off_d, d, sizeof(double) * n);
     if (!rterms.empty()) std::memcpy(blob.data() + off_rt, rterms.data(), sizeof(MaTerm) * rterms.size());
     if (!jterms.empty()) std::memcpy(blob.data() + off_jt, jterms.data(), sizeof(MaTerm) * jterms.size());
+    if (nfac > 0) {
+        std::memcpy(blob.data() + off_fc, facs.data(), sizeof(MaFac) * facs.size());
+        std::memcpy(blob.data() + off_fp, fac_ptr.data(), sizeof(int) * fac_ptr.size());
+        if (!jdfac.empty()) std::memcpy(blob.data() + off_jd, jdfac.data(), sizeof(int) * jdfac.size());
+    }
     char* dev = nullptr;
     double* params = nullptr;
-    if (hipMalloc((void**)&dev, total) != hipSuccess) return fail(c, -100, "idahip_set_mass_action: %zu bytes of network tables", total);
-    if (hipMalloc((void**)&params, sizeof(double) * (size_t)c->batch * nreac) != hipSuccess) {
+    if (hipMalloc((void**)&dev, total) != hipSuccess) return fail(c, -100, "%s: %zu bytes of network tables", who, total);
+    if (hipMalloc((void**)&params, sizeof(double) * (size_t)c->batch * nparam) != hipSuccess) {
         (void)hipFree(dev);
-        return fail(c, -100, "idahip_set_mass_action: rate constants of %d systems x %d reactions", c->batch, nreac);
+        return fail(c, -100, "%s: parameters of %d systems x %d", who, c->batch, nparam);
     }
     hipError_t e = hipMemcpy(dev, blob.data(), total, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(params, 0, sizeof(double) * (size_t)c->batch * nreac);
+    if (e == hipSuccess) e = hipMemset(params, 0, sizeof(double) * (size_t)c->batch * nparam);
     if (e != hipSuccess) {
         (void)hipFree(dev);
         (void)hipFree(params);
-        return fail(c, -100, "idahip_set_mass_action: upload failed: %s", hipGetErrorString(e));
+        return fail(c, -100, "%s: upload failed: %s", who, hipGetErrorString(e));
     }
     MaNet* m = new MaNet();
     const int* di = reinterpret_cast<const int*>(dev);
@@ -685,10 +744,29 @@ int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, i
     m->d = reinterpret_cast<const double*>(dev + off_d);
     m->rterms = reinterpret_cast<const MaTerm*>(dev + off_rt);
     m->jterms = reinterpret_cast<const MaTerm*>(dev + off_jt);
-    m->nreac = nreac;
+    m->nparam = nparam;
+    if (nfac > 0) {
+        MaLawNet* l = new MaLawNet();
+        static_cast<MaNet&>(*l) = *m;
+        l->nreac = nreac;
+        l->facs = reinterpret_cast<const MaFac*>(dev + off_fc);
+        l->fac_ptr = reinterpret_cast<const int*>(dev + off_fp);
+        l->jdfac = reinterpret_cast<const int*>(dev + off_jd);
+        c->ma_law = l;
+    }
     c->ma_blob = dev; c->ma = m; c->ma_nnz = nnz; c->ma_ml = ml; c->ma_mu = mu;
-    c->params = params; c->nparam = nreac;
+    c->params = params; c->nparam = nparam;
     return 0;
+}
+
+int idahip_set_mass_action(idahip_ctx* c, int nreac, const int32_t* reactants, int nentries, const int32_t* rows, const int32_t* reacs,
+                           const double* nu, const double* d) {
+    return set_network(c, "idahip_set_mass_action", nreac, reactants, 0, nullptr, 0, nentries, rows, reacs, nu, d);
+}
+
+int idahip_set_rate_network(idahip_ctx* c, int nreac, const int32_t* reactants, int nfac, const int32_t* factors, int nconst, int nentries,
+                            const int32_t* rows, const int32_t* reacs, const double* nu, const double* d) {
+    return set_network(c, "idahip_set_rate_network", nreac, reactants, nfac, factors, nconst, nentries, rows, reacs, nu, d);
 }
 
 int idahip_mass_action_pattern(idahip_ctx* c, int* nnz, int* ml, int* mu) {
@@ -1153,7 +1231,8 @@ int launch_dq_jac(idahip_ctx* c, double* out, bool compact, const int* d_idx, co
         case IDAHIP_MASS_ACTION: {
             if (int rc = ma_unset(c, "DQ jac")) return rc;
             const int chunks = launch_chunks(nsys, n);
-            hipLaunchKernelGGL(ma_dq_jac_kernel, dim3(nsys, chunks), dim3(256), 2 * sizeof(double) * n, c->stream, d, *c->ma, (const double*)c->params, chunks);
+            if (ma_laws(c)) hipLaunchKernelGGL(ma_dq_jac_kernel<true>, dim3(nsys, chunks), dim3(256), 2 * sizeof(double) * n, c->stream, d, *c->ma_law, (const double*)c->params, chunks);
+            else hipLaunchKernelGGL(ma_dq_jac_kernel<false>, dim3(nsys, chunks), dim3(256), 2 * sizeof(double) * n, c->stream, d, *c->ma, (const double*)c->params, chunks);
             break;
         }
         default: {
@@ -1208,8 +1287,10 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
         case IDAHIP_MASS_ACTION: {
             if (int rc = ma_unset(c, "jac")) return rc;
             const int chunks = launch_chunks(nsys, n);
-            hipLaunchKernelGGL(ma_jac_kernel, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->yy, *c->ma, (const double*)c->params,
-                               d_idx, d_cj, chunks, d_skip, 0);
+            if (ma_laws(c)) hipLaunchKernelGGL(ma_jac_kernel<true>, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->yy, *c->ma_law, (const double*)c->params,
+                                               d_idx, d_cj, chunks, d_skip, 0);
+            else hipLaunchKernelGGL(ma_jac_kernel<false>, dim3(nsys, chunks), dim3(256), 0, c->stream, work, n, (const double*)c->yy, *c->ma, (const double*)c->params,
+                                    d_idx, d_cj, chunks, d_skip, 0);
             break;
         }
         default: {
@@ -1342,8 +1423,10 @@ int idahip_mass_action_jac(idahip_ctx* c, int sys, double cj, double* hJ) {
     if (int rc = dq_grow(c, &c->dq_out, &c->dq_out_cap, mat)) return rc;
     const int chunks = launch_chunks(1, n);
     if (!f.launch(IDAHIP_K_JAC, 1, "ma_jac", [&] {
-            hipLaunchKernelGGL(ma_jac_kernel, dim3(1, chunks), dim3(256), 0, c->stream, c->dq_out, n, (const double*)c->yy, *c->ma,
-                               (const double*)c->params, f.idx, d_cj, chunks, (const int*)nullptr, 1);
+            if (ma_laws(c)) hipLaunchKernelGGL(ma_jac_kernel<true>, dim3(1, chunks), dim3(256), 0, c->stream, c->dq_out, n, (const double*)c->yy, *c->ma_law,
+                                               (const double*)c->params, f.idx, d_cj, chunks, (const int*)nullptr, 1);
+            else hipLaunchKernelGGL(ma_jac_kernel<false>, dim3(1, chunks), dim3(256), 0, c->stream, c->dq_out, n, (const double*)c->yy, *c->ma,
+                                    (const double*)c->params, f.idx, d_cj, chunks, (const int*)nullptr, 1);
         }))
         return f.rc;
     IDAHIP_HIP(c, hipMemcpyAsync(hJ, c->dq_out, sizeof(double) * mat, hipMemcpyDeviceToHost, c->stream));

@@ -52,7 +52,7 @@ HIP_SYMBOLS = [
     "idahip_krylov_upload_prec",
     "idahip_set_krylov_rounds", "idahip_krylov_rounds", "idahip_krylov_rounds_put_counters", "idahip_krylov_rounds_get_counters",
     "idahip_set_suppress_alg", "idahip_suppress_alg", "idahip_wrms_masked",
-    "idahip_set_mass_action", "idahip_mass_action_pattern", "idahip_mass_action_jac",
+    "idahip_set_mass_action", "idahip_mass_action_pattern", "idahip_mass_action_jac", "idahip_set_rate_network",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
@@ -119,6 +119,7 @@ def load():
     H.idahip_set_problem_params.argtypes = [vp, ci, ci, dp, ci]
     H.idahip_set_linear_dense.argtypes = [vp, ci, ci, dp, dp, dp]
     H.idahip_set_mass_action.argtypes = [vp, ci, i32p, ci, i32p, i32p, dp, dp]
+    H.idahip_set_rate_network.argtypes = [vp, ci, i32p, ci, i32p, ci, ci, i32p, i32p, dp, dp]
     H.idahip_mass_action_pattern.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     H.idahip_mass_action_jac.argtypes = [vp, ci, cd, dp]
     H.idahip_upload.argtypes = [vp, ci, ci, ci, dp]
@@ -465,6 +466,22 @@ class Ctx:
         assert rows.size == reacs.size == nu.size and d.size == self.n
         self._chk(self.H.idahip_set_mass_action(self.h, slots.shape[0], _p(slots, i32p), rows.size, _p(rows, i32p), _p(reacs, i32p), _p(nu), _p(d)),
                   "set_mass_action")
+
+    def set_rate_network(self, reactions, d, nconst):
+        """IDAHIP_MASS_ACTION with rate laws, instead of set_mass_action (include/ida_hip.h): reactions = [(reactants, {row: nu, ...}
+        [, factors]), ...] with factors = [("sat" | "inh", species, constant, h), ...], at most 4 per reaction, 1 <= h <= 4; nconst
+        constants per system, which follow the rate constants in set_problem_params: [k_0 .. k_{R-1}, K_0 .. K_{nconst-1}]. Checked
+        here (idahip.mass_action.flatten_laws) and again by the library."""
+        from . import mass_action
+        slots, fac, rows, reacs, nu, dd = mass_action.flatten_laws(self.n, reactions, d, nconst)
+        self.set_rate_network_raw(slots, fac, nconst, rows, reacs, nu, dd)
+
+    def set_rate_network_raw(self, slots, factors, nconst, rows, reacs, nu, d):
+        """idahip_set_rate_network on the flat arrays, unchecked on this side (the library's own refusals)."""
+        slots, factors, rows, reacs, nu, d = _i32(slots).reshape(-1, 3), _i32(factors).reshape(-1, 5), _i32(rows), _i32(reacs), _f64(nu), _f64(d)
+        assert rows.size == reacs.size == nu.size and d.size == self.n
+        self._chk(self.H.idahip_set_rate_network(self.h, slots.shape[0], _p(slots, i32p), factors.shape[0], _p(factors, i32p), int(nconst), rows.size,
+                                                 _p(rows, i32p), _p(reacs, i32p), _p(nu), _p(d)), "set_rate_network")
 
     def mass_action_pattern(self):
         """(nnz, ml, mu) of the network's Jacobian pattern: its positions (every diagonal one included) and half-bandwidths."""

@@ -315,7 +315,8 @@ def bruss1d(m=2048, batch=256, alpha=0.02):
 
 # ---------------------------------------------------------------------------------------- mass-action networks (IDAHIP_MASS_ACTION)
 # A network problem carries "reactions" = [(reactants, {row: nu})], "d" [n] and "params" = the rate constants [batch][R]
-# (include/ida_hip.h, idahip/mass_action.py); make_ctx uploads the network, then the constants.
+# (include/ida_hip.h, idahip/mass_action.py); make_ctx uploads the network, then the constants. A network with rate laws carries
+# "nconst" as well, reactions with a third item (the factors), and "params" = [batch][R + nconst].
 def _network(n, reactions, d, k, yy0, yp0, rtol, atol, touts):
     return {"kind": "mass_action", "n": n, "reactions": reactions, "d": np.asarray(d, dtype=np.float64),
             "params": np.ascontiguousarray(k, dtype=np.float64), "yy0": yy0, "yp0": yp0, "rtol": rtol, "atol": atol, "touts": touts}
@@ -437,6 +438,51 @@ def reaction_chain(n=12, batch=64, seed=7):
     return _network(n, reactions, d, k, y0, yp0, 1.0e-6, np.array([1.0e-9]), 0.01 * np.arange(1, 4))
 
 
+def enzyme_chain(n=9, batch=64, seed=11):
+    """A seeded network with rate laws (idahip_set_rate_network) of n >= 5 species: m = n - 1 differential species and their total
+    as the algebraic last one (d = 0); nconst = m constants. Reactions, in this order: an inhibited feed () -> 0 with
+    inh(m-1, K_0, h = 2); the chain i -> i+1 for i = 0 .. m-2 as zero-order reactions with sat(i, K_{1+i}, h = 1 + i % 3)
+    (Michaelis-Menten and Hill steps); the first-order drain of m-1; 0 + 1 -> 2 with [inh(2, K_0, 1), sat(0, K_1, 2)] (species 0 in a
+    slot and in a factor of one reaction); then the total's row: +y_i for every i < m, -y_{n-1}. Parameters (PCG64 `seed`, drawn in
+    the order k, K, y0): the first m + 2 rate constants 10^U(-1, 2), the rest 1; K = 10^U(-1, 1); y(0) = U(0.5, 1.5), y_{n-1}(0) the
+    ordered sum of the others, so that the algebraic row is exactly 0; y'(0) = the right-hand side. rtol 1e-6, atol 1e-9."""
+    from . import mass_action
+    assert n >= 5
+    m = n - 1
+    rng = np.random.Generator(np.random.PCG64(seed))
+    reactions = [((), {0: 1.0}, [("inh", m - 1, 0, 2)])]
+    for i in range(m - 1):
+        reactions.append(((), {i: -1.0, i + 1: 1.0}, [("sat", i, 1 + i, 1 + i % 3)]))
+    reactions.append(((m - 1,), {m - 1: -1.0}))
+    reactions.append(((0, 1), {0: -1.0, 1: -1.0, 2: 1.0}, [("inh", 2, 0, 1), ("sat", 0, 1, 2)]))
+    for i in range(m):
+        reactions.append(((i,), {n - 1: 1.0}))
+    reactions.append(((n - 1,), {n - 1: -1.0}))
+    R = len(reactions)
+    assert R == 2 * m + 3
+    d = np.ones(n)
+    d[n - 1] = 0.0
+    k = np.ones((batch, R))
+    k[:, :m + 2] = 10.0 ** rng.uniform(-1.0, 2.0, size=(batch, m + 2))
+    K = 10.0 ** rng.uniform(-1.0, 1.0, size=(batch, m))
+    y0 = rng.uniform(0.5, 1.5, size=(batch, n))
+    params = np.concatenate([k, K], axis=1)
+    tab = mass_action.tables_laws(n, reactions, d, m)
+    yp0 = np.zeros((batch, n))
+    for s in range(batch):
+        total = y0[s, 0]
+        for i in range(1, m):
+            total = total + y0[s, i]
+        y0[s, n - 1] = total
+        f = mass_action.rhs_laws(tab, params[s], y0[s])
+        assert f[n - 1] == 0.0
+        yp0[s] = f
+        yp0[s, n - 1] = sum(f[i] for i in range(m))
+    out = _network(n, reactions, d, params, y0, yp0, 1.0e-6, np.array([1.0e-9]), 0.01 * np.arange(1, 4))
+    out["nconst"] = m
+    return out
+
+
 def make_ctx(prob, device=0, stream=None, band=False, krylov=None):
     """Create a device context for a generated problem and load its data (import kept local: this module is also
     used by CPU-only tests). band=True: a band ctx -- (1, 1) for heat1d, (2, 2) for bruss1d, prob["band"] for a host-callback problem with a band
@@ -459,7 +505,10 @@ def make_ctx(prob, device=0, stream=None, band=False, krylov=None):
     elif prob["kind"] == "host_callback":
         ctx.set_host_problem(prob["res"], prob["jac"])
     elif prob["kind"] == "mass_action":
-        ctx.set_mass_action(prob["reactions"], prob["d"])
+        if "nconst" in prob:  # a network with rate laws: params = [k, K]
+            ctx.set_rate_network(prob["reactions"], prob["d"], prob["nconst"])
+        else:
+            ctx.set_mass_action(prob["reactions"], prob["d"])
         ctx.set_problem_params(prob["params"])
     elif "params" in prob:
         ctx.set_problem_params(prob["params"])
