@@ -32,11 +32,11 @@ def lorenz():
             "atol": p["atol"], "tout1": 0.1, "yy0": p["yy0"], "yp0": np.zeros((16, 3)), "data": {"params": p["params"]}}
 
 
-def linear(n, pattern, icopt=IC.YA_YDP_INIT, dq=False):
+def linear(n, pattern, icopt=IC.YA_YDP_INIT, dq=False, B=None):
     """F = A y' + B y - c with A = diag(id) (I + small coupling) -- singular in the algebraic rows --, B diagonally dominant,
     random y0. pattern: "one_alg" (one algebraic component), "one_diff" (all but one), "mixed" (every third algebraic).
     Y_INIT: y0' is given (random) and y0 is solved for."""
-    B = 4 if n >= 257 else 16
+    B = B or (4 if n >= 257 else 16)
     id_ = {"one_alg": np.ones(n), "one_diff": np.zeros(n), "mixed": np.where(np.arange(n) % 3 == 2, 0.0, 1.0)}[pattern].copy()
     if pattern == "one_alg":
         id_[n // 2] = 0.0
@@ -122,9 +122,79 @@ DQ = ["linear9_dq", "heat16_band_dq"]
 EXPECTED_FAILURES = {"linesearch": {2: IC.CONV_FAIL, 3: IC.LINESEARCH_FAIL, 4: IC.NO_RECOVERY}}
 
 
+# ---- batches with mixed fates on the device kinds (their trials run in the fused kernels): systems that converge, backtrack, retry
+# at a smaller step size and fail side by side, with a different step size hic -- so a different cj -- in every system
+def bruss_mixed():
+    """bruss1d(m = 16) with Y_INIT: y'(0) the problem's own (non-zero: hic differs per system), y(0) scaled componentwise by
+    1 + 0.1 m_s U(-1, 1) with a magnitude m_s per system, from a nudge to a guess far outside the basin of attraction."""
+    from idahip import problems
+    mags = np.array([0.01, 0.1, 0.5, 2.5, 2.5, 4.0, 8.0, 2.5, 9.9])
+    p = problems.bruss1d(m=16, batch=mags.size)
+    u = _rng(5, 16, 19).uniform(-1.0, 1.0, size=p["yy0"].shape)
+    return {"kind": "bruss1d", "n": 32, "band": None, "dq": False, "icopt": IC.Y_INIT, "id": None, "rtol": p["rtol"], "atol": p["atol"],
+            "tout1": 0.25, "yy0": p["yy0"] * (1.0 + 0.1 * mags[:, None] * u), "yp0": p["yp0"].copy(), "data": {"params": p["params"]}}
+
+
+def heat_mixed(n, B, hard):
+    """heat1d with YA_YDP_INIT: the systems `hard` start as the heat cases above do (sin + 0.1 with y' = 0: their first step size
+    fails and they retry at hic/10), every other one from the generator's own consistent values, with its non-zero y'(0)."""
+    from idahip import problems
+    c = heat(n)
+    p = problems.heat1d(n=n, batch=B)
+    yy0, yp0 = p["yy0"].copy(), p["yp0"].copy()
+    for b in hard:
+        yy0[b], yp0[b] = c["yy0"][0], 0.0
+    return dict(c, yy0=yy0, yp0=yp0, data={"params": p["params"]})
+
+
+def linear_singular(n, sys, row):
+    """linear(n, "mixed") with a zero row in A and in B of one system: its Jacobian is singular at every step size."""
+    c = linear(n, "mixed")
+    d = {k: v.copy() for k, v in c["data"].items()}
+    d["A"][sys, :, row] = 0.0  # column-major per system: [j][i]
+    d["B"][sys, :, row] = 0.0
+    return dict(c, data=d)
+
+
+def linear_inf(n, sys, comp):
+    """linear(n, "mixed") with y_comp(0) = +inf in one system: its weight there is +0.0."""
+    c = linear(n, "mixed")
+    yy0 = c["yy0"].copy()
+    yy0[sys, comp] = np.inf
+    return dict(c, yy0=yy0)
+
+
+def linear_big(n, B):
+    """linear(n, "mixed") at the benchmark's size, B systems, from a non-zero y'(0) in the differential components"""
+    c = linear(n, "mixed")
+    yp0 = np.stack([c["id"] * _rng(6, n, b).uniform(-50.0, 50.0, size=n) * (1.0 + 10.0 * b) for b in range(B)])
+    return dict(c, yy0=c["yy0"][:B], yp0=yp0, data={k: v[:B] for k, v in c["data"].items()})
+
+
+MIXED = {
+    "bruss32_mixed": bruss_mixed,
+    "heat65_mixed": lambda: heat_mixed(65, 5, (1, 3)),
+    "linear40_singular": lambda: linear_singular(40, 5, 17),
+    "linear40_inf": lambda: linear_inf(40, 3, 11),
+    "linear512_mixed": lambda: linear_big(512, 4),
+    "heat1030": lambda: heat_mixed(1030, 2, (1,)),
+}
+
+
+# every status of the reference on them (test_calcic_ref.py asserts these and the properties each case is there for)
+MIXED_STATUS = {
+    "bruss32_mixed": [0, 0, 0, IC.CONV_FAIL, IC.CONV_FAIL, IC.CONV_FAIL, IC.LINESEARCH_FAIL, 0, IC.CONV_FAIL],
+    "heat65_mixed": [0] * 5,
+    "linear40_singular": [0] * 5 + [IC.NO_RECOVERY] + [0] * 10,
+    "linear40_inf": [0] * 3 + [IC.BAD_EWT] + [0] * 12,
+    "linear512_mixed": [0] * 4,
+    "heat1030": [0] * 2,
+}
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
-    return CASES[name]()
+    return (CASES.get(name) or MIXED[name])()
 
 
 def sysdata(c, b):
@@ -135,6 +205,15 @@ def sysdata(c, b):
         return {"params": d["params"][b]}
     if c["kind"] == "heat1d":
         return {"coef": d["params"][b, 0]}
+    if c["kind"] == "bruss1d":
+        return {"params": d["params"][b]}
+    if c["kind"] == "mass_action":  # a network with rate laws ("nconst") is ratelaw_ref's, a plain one massaction_ref's
+        import massaction_ref
+        import ratelaw_ref
+        M = ratelaw_ref if "nconst" in d else massaction_ref
+        if "_net" not in c:
+            c["_net"] = M.Net(dict(d, n=c["n"]))
+        return {"ref": M, "net": c["_net"], "k": d["params"][b]}
     return {}
 
 
@@ -169,5 +248,6 @@ def make_ctx(c):
     assert ctx.batch == B
     if c["dq"]:
         ctx.set_jacobian_dq(True)
-    ctx.set_id(c["id"])
+    if c["id"] is not None:
+        ctx.set_id(c["id"])
     return ctx

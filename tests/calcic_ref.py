@@ -4,6 +4,10 @@ problem_jac, getrf / getrs, wrms, and dq_ref's difference-quotient Jacobians -- 
 too (host-callback problems). numpy's elementwise float64 arithmetic is IEEE without fused multiply-add, so every value here is
 what libidaens + libidahip must produce: bit for bit on a dense ctx, by value on a band ctx.
 
+The steps the device runs as entry points of their own -- begin, trial_point, solve_norm, accept, commit -- are module-level
+functions, and calc_ic is made of them: tests/test_gpu_ic_entry_points.py compares each idahip_ic_* call with the same statement of
+its formula that the whole runs are compared with.
+
 TEST INFRASTRUCTURE ONLY."""
 import math
 
@@ -30,6 +34,36 @@ def ewt_set(y, rtol, atol):
         return 1.0 / (rtol * np.abs(y) + atol)
 
 
+def begin(phi0, phi1, rtol, atol):
+    """idahip_ic_begin / IDACalcIC's first lines -> (ewt = ewt_set(phi0), bad: some weight <= 0 (a NaN is not), ||phi1||_wrms(ewt))"""
+    ewt = ewt_set(phi0, rtol, atol)
+    return ewt, bool((ewt <= 0.0).any()), O.wrms(phi1, ewt)
+
+
+def commit(y0, rtol, atol):
+    """the weights of a converged pass -> (ewt = ewt_set(y0), bad)"""
+    ewt = ewt_set(y0, rtol, atol)
+    return ewt, bool((ewt <= 0.0).any())
+
+
+def trial_point(y0, yp0, delta, lam, cj, diff):
+    """The line search's point: a differential component (diff[i]; none with Y_INIT) keeps y and moves y' by (cj*lam)*delta, every
+    other one moves y by lam*delta and keeps y'."""
+    with np.errstate(all="ignore"):
+        return np.where(diff, y0, y0 - lam * delta), np.where(diff, yp0 - (cj * lam) * delta, yp0)
+
+
+def solve_norm(lu, piv, rhs, ewt):
+    """-> (x = LU^-1 rhs, ||x||_wrms(ewt)): getrs without scaling, the sum taken left to right"""
+    x = O.getrs(lu, piv, rhs)
+    return x, O.wrms(x, ewt)
+
+
+def accept(y0, yp0, ynew, ypnew, delnew, icopt):
+    """an accepted trial -> (iterate y, iterate y', direction): y' moves only with YA_YDP_INIT; delta <- delnew"""
+    return ynew, (ypnew if icopt == YA_YDP_INIT else yp0), delnew
+
+
 class Problem:
     """res(y, yp) -> F [n]; jac(cj, y, yp, rr, hic, ewt) -> J [n][n] column-major (J[j, i] = J(i, j)); dq_evals: residual
     evaluations one Jacobian adds to nre_dq (0: analytic)."""
@@ -41,6 +75,15 @@ class Problem:
 def device_problem(kind, n, sysdata, t0=0.0, dq=False, band=None):
     """One system of a built-in problem kind. sysdata: params (lorenz63) / coef (heat1d) / A, B, c (linear_dense, column-major).
     dq: the ctx's difference-quotient Jacobian (dense ctx, or band=(ml, mu) for heat1d on a band ctx)."""
+    if kind == "bruss1d":  # sysdata: params [a, b, d, ub, vb] (bruss_ref)
+        import bruss_ref as BR
+        assert not dq
+        p = sysdata["params"]
+        return Problem(n, lambda y, yp: BR.res(p, y, yp), lambda cj, y, yp, rr, hic, ewt: BR.jac(p, cj, y))
+    if kind == "mass_action":  # sysdata: net (massaction_ref.Net or ratelaw_ref.Net), ref (that module), k (the system's constants)
+        assert not dq
+        M, net, k = sysdata["ref"], sysdata["net"], sysdata["k"]
+        return Problem(n, lambda y, yp: M.res(net, k, y, yp), lambda cj, y, yp, rr, hic, ewt: M.jac(net, k, cj, y))
     kw = {}
     if kind == "lorenz63":
         kw["params"] = sysdata["params"]
@@ -88,14 +131,13 @@ def calc_ic(prob, yy0, yp0, rtol, atol, icopt, tout1, id=None, t0=0.0):
         return {"status": status, "yy": phi0 if ok else given[0], "yp": phi1 if ok else given[1], "ewt": ewt, "hic": hic,
                 "counters": cnt}
 
-    ewt = ewt_set(phi0, rtol, atol)
-    if (ewt <= 0.0).any():
+    ewt, bad, ypnorm = begin(phi0, phi1, rtol, atol)
+    if bad:
         return done(BAD_EWT)
     tdist = abs(tout1 - t0)
     if tdist == 0.0 or tdist < 2.0 * EPS * (abs(t0) + abs(tout1)):  # t0 == tout1 == 0: the bound is 0 too, and 0 < 0 is false
         return done(ILL_INPUT)
     hic = 0.001 * tdist
-    ypnorm = O.wrms(phi1, ewt)
     if ypnorm > 0.5 / hic:
         hic = 0.5 / ypnorm
     if tout1 < t0:
@@ -113,13 +155,10 @@ def calc_ic(prob, yy0, yp0, rtol, atol, icopt, tout1, id=None, t0=0.0):
         while True:
             if nbacks == MAXBACKS:
                 return LINESRCH
-            with np.errstate(all="ignore"):
-                ynew = np.where(diff, st["yy0"], st["yy0"] - lam * st["delta"])
-                ypnew = np.where(diff, st["yp0"] - (cj * lam) * st["delta"], st["yp0"])
+            ynew, ypnew = trial_point(st["yy0"], st["yp0"], st["delta"], lam, cj, diff)
             st["savres"] = prob.res(ynew, ypnew)
             cnt["nre"] += 1
-            st["delnew"] = O.getrs(lu, piv, st["savres"])
-            fnormp = O.wrms(st["delnew"], ewt)
+            st["delnew"], fnormp = solve_norm(lu, piv, st["savres"], ewt)
             if fnormp * fnormp * 0.5 <= f1norm + ALPHALS * slpi * lam:
                 break
             if lam < minlam:
@@ -127,15 +166,12 @@ def calc_ic(prob, yy0, yp0, rtol, atol, icopt, tout1, id=None, t0=0.0):
             lam /= 2.0
             cnt["nbacktr"] += 1
             nbacks += 1
-        st["yy0"] = ynew
-        if icopt == YA_YDP_INIT:
-            st["yp0"] = ypnew
+        st["yy0"], st["yp0"], st["accepted"] = accept(st["yy0"], st["yp0"], ynew, ypnew, st["delnew"], icopt)
         st["fnorm"] = fnormp
         return OK
 
     def newton(lu, piv):
-        st["delta"] = O.getrs(lu, piv, st["delta"])
-        st["fnorm"] = O.wrms(st["delta"], ewt)
+        st["delta"], st["fnorm"] = solve_norm(lu, piv, st["delta"], ewt)
         if st["fnorm"] <= EPS_NEWT:
             return OK
         fnorm0 = oldfnrm = st["fnorm"]
@@ -153,7 +189,7 @@ def calc_ic(prob, yy0, yp0, rtol, atol, icopt, tout1, id=None, t0=0.0):
             if m >= MAXNIT:
                 ret = CONV
                 break
-            st["delta"] = st["delnew"]
+            st["delta"] = st["accepted"]
             oldfnrm = st["fnorm"]
         if rate <= ICRATEMAX:
             return ret
@@ -194,8 +230,8 @@ def calc_ic(prob, yy0, yp0, rtol, atol, icopt, tout1, id=None, t0=0.0):
             cj = 1.0 / hic
         if ret != OK:
             break
-        ewt = ewt_set(st["yy0"], rtol, atol)
-        if (ewt <= 0.0).any():
+        ewt, bad = commit(st["yy0"], rtol, atol)
+        if bad:
             return done(BAD_EWT, hic)
         phi0, phi1 = st["yy0"].copy(), st["yp0"].copy()
     if ret == OK:

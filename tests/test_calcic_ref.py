@@ -8,6 +8,7 @@ import pytest
 
 import calcic_cases as K
 import calcic_ref as IC
+import oracle_lib as O
 
 
 def bits(a):
@@ -63,6 +64,62 @@ def test_the_cases_reach_the_paths_they_are_meant_for():
         r = K.reference(name)
         assert (r["counters"]["nre_dq"] > 0).all() and (r["status"] == 0).all()
     assert (K.reference("linear40_yinit")["status"] == 0).all()
+
+
+def test_mixed_cases_keep_the_properties_they_were_chosen_for():
+    """The batches of K.MIXED on the reference alone: what each must show for its GPU test (test_gpu_calc_ic.py) to reach the fused
+    trial kernels with a per-position lambda and cj, lists that shrink unevenly, ic_reset on a sublist and every failure status."""
+    for name in K.MIXED:
+        c, r = K.case(name), K.reference(name)
+        assert r["status"].tolist() == K.MIXED_STATUS[name], (name, r["status"].tolist())
+        for b in np.flatnonzero(r["status"] != 0):  # a failed system keeps what it was given
+            assert np.array_equal(bits(r["yy"][b]), bits(c["yy0"][b])) and np.array_equal(bits(r["yp"][b]), bits(c["yp0"][b]))
+        for b in np.flatnonzero(r["status"] == 0):
+            again = IC.calc_ic(K.ref_problem(c, int(b)), r["yy"][b], r["yp"][b], c["rtol"], c["atol"], c["icopt"], c["tout1"], id=c["id"])
+            assert again["status"] == 0, (name, b)  # (a second run has another hic, so it may iterate again; it must not fail)
+    # Brusselator, Y_INIT: successes and failures side by side, backtracking in both, a different hic per system
+    r = K.reference("bruss32_mixed")
+    ok, cnt = r["status"] == 0, r["counters"]
+    assert ok.any() and (r["status"] == IC.CONV_FAIL).any() and (r["status"] == IC.LINESEARCH_FAIL).any()
+    assert (cnt["nbacktr"][ok] > 0).any() and (cnt["nbacktr"][~ok] > 0).any() and (cnt["nbacktr"][ok] == 0).any()  # lambda < 1 beside lambda = 1
+    assert (cnt["nsetups"][ok] > 2).any()  # slow convergence: a second Jacobian at the same step size (delta <- savres)
+    assert np.unique(r["hic"]).size == ok.size and len(set(cnt["nni"][ok].tolist())) >= 3
+    assert (np.abs(K.case("bruss32_mixed")["yp0"]).max(axis=1) > 0.0).all()
+    # heat, YA_YDP_INIT: part of the batch retries at hic/10 (ic_reset on a sublist, two cj in one launch) and then succeeds
+    for name, hard in (("heat65_mixed", [1, 3]), ("heat1030", [1])):
+        r = K.reference(name)
+        assert (r["status"] == 0).all() and np.flatnonzero(r["counters"]["ncfn"] > 0).tolist() == hard, name
+        assert np.unique(r["hic"]).size == r["hic"].size - len(hard) + 1  # (the hard ones start from y' = 0 and share theirs)
+        assert (r["counters"]["nni"][hard] > 0).all() and np.delete(r["counters"]["nni"], hard).max() == 0
+    # a singular system runs through all five step sizes while the others converge
+    r = K.reference("linear40_singular")
+    assert r["counters"]["ncfn"][5] == IC.MAXNH and r["counters"]["nni"][5] == 0 and r["counters"]["nsetups"][5] == IC.MAXNH
+    assert (np.delete(r["status"], 5) == 0).all() and (np.delete(r["counters"]["ncfn"], 5) == 0).all()
+    # +inf in y(0): the weight is +0.0, BAD_EWT before anything is counted; the rest of the batch as without it
+    r, plain = K.reference("linear40_inf"), K.reference("linear40_mixed")
+    assert all(r["counters"][k][3] == 0 for k in IC.COUNTERS) and r["ewt"][3] is None
+    keep = np.arange(16) != 3
+    assert np.array_equal(bits(r["yy"][keep]), bits(plain["yy"][keep])) and np.array_equal(bits(r["yp"][keep]), bits(plain["yp"][keep]))
+    # the benchmark's size: a different hic per system from a non-zero y'(0)
+    r = K.reference("linear512_mixed")
+    assert (r["status"] == 0).all() and np.unique(r["hic"]).size == 4 and (r["hic"] < 1.0e-4).all()
+
+
+def test_step_functions_are_what_calc_ic_is_made_of():
+    """begin / commit on the weights' edge: a weight of +0.0 (an infinite component) or below zero (a negative entry of a vector
+    atol) is bad, a NaN is not; trial_point moves y where diff is false and y' where it is true."""
+    y, yp = np.array([1.0, -2.0, 3.0]), np.array([0.5, 0.25, -1.0])
+    ewt, bad, nrm = IC.begin(y, yp, 1e-3, np.full(3, 1e-6))
+    assert not bad and np.array_equal(bits(ewt), bits(IC.ewt_set(y, 1e-3, 1e-6))) and nrm == O.wrms(yp, ewt)
+    assert IC.begin(np.array([1.0, np.inf, 3.0]), yp, 1e-3, np.full(3, 1e-6))[1]
+    assert IC.begin(y, yp, 1e-3, np.array([1e-6, -1.0, 1e-6]))[1]
+    assert not IC.begin(np.array([1.0, np.nan, 3.0]), yp, 1e-3, np.full(3, 1e-6))[1]
+    assert IC.commit(np.array([1.0, np.inf, 3.0]), 1e-3, np.full(3, 1e-6))[1] and not IC.commit(np.array([np.nan, 1.0, 1.0]), 1e-3, np.full(3, 1e-6))[1]
+    d = np.array([1.0, 2.0, 4.0])
+    yn, ypn = IC.trial_point(y, yp, d, 0.5, 8.0, np.array([True, False, True]))
+    assert yn.tolist() == [1.0, -3.0, 3.0] and ypn.tolist() == [-3.5, 0.25, -17.0]
+    a = IC.accept(y, yp, yn, ypn, d, IC.Y_INIT)
+    assert a[0] is yn and a[1] is yp and a[2] is d and IC.accept(y, yp, yn, ypn, d, IC.YA_YDP_INIT)[1] is ypn
 
 
 def test_tout1_at_t0_is_ill_input_at_every_t0():

@@ -84,6 +84,15 @@ def test_line_search_and_failures_share_rounds():
     assert d["c"]["nbacktr"][1] > 0 and d["c"]["nni"][4] == 0
 
 
+@pytest.mark.parametrize("name", sorted(K.MIXED))
+def test_mixed_fates_on_device_kinds(name):
+    """The batches of K.MIXED (test_calcic_ref.py pins what each shows on the reference): successes, backtracking, retries at a
+    smaller step size, CONV_FAIL, LINESEARCH_FAIL, NO_RECOVERY and BAD_EWT side by side on kinds whose trial runs in the fused
+    kernels, every system with its own hic; status, values, weights and every counter as calcic_ref, bit for bit."""
+    status, d = check_against_reference(name, exact=True)
+    assert status.tolist() == K.MIXED_STATUS[name]
+
+
 # ------------------------------------------------------------------------------------------------ hand-over to the steppers
 RUN_COUNTERS = ("nst", "nre", "nje", "nsetups", "nni", "netf", "ncfn", "n_attempts")
 
