@@ -586,6 +586,25 @@ int idahip_round_solve(idahip_ctx* ctx, void* hSys, size_t sys_bytes, const idah
  * Any other value is refused. (Round 2's variant 5, the same kernels with FMA-contracted updates, is gone: DESIGN.md.) */
 int idahip_set_lu_variant(idahip_ctx* ctx, int variant);
 int idahip_lu_variant(const idahip_ctx* ctx); /* the variant in force */
+/* IDAHIP_LINEAR_DENSE with analytic Jacobians, 8 < n <= 512, LU variant 4, the ctx's own work matrix and factors: where the Newton
+ * matrix J = B + cj*A is formed. Inside the factorisation: the first super-panel's launches and the first trailing launch read A
+ * and B and combine them as they load, the residual of the systems that set up is the plain sweep (kernel class IDAHIP_K_SYS;
+ * IDAHIP_K_SYS_JAC and IDAHIP_K_JAC then count nothing) and J never passes through memory. Or outside it: by the fused residual +
+ * Jacobian sweep (idahip_nls_sys_setup, idahip_round_solve) or the Jacobian kernel (idahip_nls_lsetup) into the work matrix.
+ * Same expression, multiply then add: factors, pivots and every result are bit-identical either way.
+ *   never set (the default): inside in idahip_round_solve (the device lock-step stepper) where 448 < n <= 512 -- the first panel is
+ *                            then the eight-slot instantiation, the size the path was measured at; smaller matrices take a
+ *                            first-panel kernel that reads its slot count at run time, unmeasured, and stay outside --;
+ *                            idahip_nls_lsetup and idahip_nls_sys_setup -- and with the latter the host stepper -- launch the
+ *                            kernels they always launched;
+ *   1: inside, in all three, for every eligible n;   0: outside, in all three.
+ * Turning it on is refused (-2) on a ctx that is not eligible (another kind, a band or Krylov ctx, n outside the range); a DQ ctx
+ * or LU variant 3 keep the setting and use the other path while they last. The calls on caller-supplied matrices
+ * (idahip_ls_setup) and the initial-condition calls are not affected. */
+int idahip_set_jac_in_lu(idahip_ctx* ctx, int on);
+/* What is in effect now: 0 = outside everywhere; 1 = inside in idahip_round_solve alone (never set, n > 448); 2 = inside in
+ * idahip_round_solve, idahip_nls_lsetup and idahip_nls_sys_setup (set to 1). */
+int idahip_jac_in_lu(const idahip_ctx* ctx);
 /* Matrices with more than 1024 rows: how a 64-column super-panel is factored. 1 = in one launch of the left-looking
  * workgroup-per-matrix kernel (lu_superpanel_kernel): the faster pipeline for BANDED matrices in dense storage (config 4's heat
  * Jacobians: 238 against 322 us per 4096 x 4096 matrix) and the default for IDAHIP_HEAT1D and IDAHIP_BRUSS1D; 0 = eight 8-column panel launches with a

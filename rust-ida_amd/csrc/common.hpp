@@ -104,6 +104,10 @@ struct idahip_ctx {
     std::vector<int64_t> kry_h_npe, kry_h_nps;  // [batch] the systems' npe / nps around idahip_round_solve (idahip_krylov_rounds_put/get_counters)
     double *ic_y = nullptr, *ic_yp = nullptr;  // [batch][n] initial conditions kept for idahip_restore_initial (lazy)
     double* dky = nullptr;                     // [batch][n] result buffer of idahip_get_dky (lazy)
+    // idahip_set_jac_in_lu: a linear dense ctx with analytic Jacobians forms J = B + cj*A inside the first launches of the factorisation
+    // (LuJac, lu_kernels.hpp) instead of in the residual sweep; in effect only where jac_in_lu_on (idahip.hip) says the ctx is eligible.
+    // -1 = never set: on in idahip_round_solve where n > 448, off in the list entry points; 0 / 1 = set by the caller, for both
+    int jac_in_lu = -1;
     int lu_variant = 4;  // 4: one wave per matrix factors each 64-column super-panel (lu_wavepanel.hpp, default)
     // n > 1024: 1 = a 64-column super-panel is ONE launch of lu_superpanel_kernel (left-looking; made for banded matrices in dense
     // storage, where it is 26 % faster: config 4), 0 = round 4's eight 8-column panel launches with a narrow update after each,

@@ -1306,14 +1306,30 @@ int launch_jac(idahip_ctx* c, double* work, const int* d_idx, const double* d_cj
     return post_launch(c, "jac");
 }
 
+// idahip_set_jac_in_lu: can this ctx form J = B + cj*A inside the factorisation at all, and does it now (LuJac, lu_driver.hpp)
+bool jac_in_lu_can(const idahip_ctx* c) {
+    return c->kind == IDAHIP_LINEAR_DENSE && !c->band && !c->krylov && c->n > TINY_N && c->n <= WP_MAX_ROWS;
+}
+// list_entry: asked by idahip_nls_lsetup / idahip_nls_sys_setup, which take the path only once it has been switched on by name --
+// left alone they launch the kernel classes they always launched. idahip_round_solve takes it unasked only where the first panel is
+// the eight-slot instantiation (n > 448: the size it was measured at, profiles/r08_jac_in_lu_ab.txt); smaller matrices go through an
+// instantiation that reads its slot count at run time and have not been measured: on request only.
+bool jac_in_lu_on(const idahip_ctx* c, bool list_entry) {
+    const bool asked = c->jac_in_lu == 1;
+    const bool unasked = c->jac_in_lu < 0 && !list_entry && c->n > WP_MAX_ROWS - 64;
+    if (!asked && !unasked) return false;
+    return jac_in_lu_can(c) && !c->jac_dq && lu_jac_eligible(c);
+}
+
 // batched getrf of the work matrices into ctx->lu / piv / perm, then the per-system info of the listed systems
-int factor_and_report(ListCall& f, double* work, int32_t* hInfo) {
+// (jq: the work matrices do not hold J, the factorisation forms it: jac_in_lu_on)
+int factor_and_report(ListCall& f, double* work, int32_t* hInfo, const LuJac* jq = nullptr) {
     idahip_ctx* c = f.c;
     const int n = c->n, nsys = f.nsys;
     const long nn = (long)n * n;
     f.launch(IDAHIP_K_LU, nsys, "lu", [&] {
         if (c->band) return band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, f.idx, nsys);
-        return lu_factor_batched(c, work, nn, c->lu, nn, (long long*)c->piv, n, c->perm, f.idx, nsys);
+        return lu_factor_batched(c, work, nn, c->lu, nn, (long long*)c->piv, n, c->perm, f.idx, nsys, nullptr, jq);
     });
     return f.rc ? f.rc : report_info(c, f.hIdx, nsys, hInfo);
 }
@@ -1347,8 +1363,10 @@ int idahip_nls_lsetup(idahip_ctx* c, const double* hTn, const double* hCj, int32
     if (!f.stage()) return f.rc;
     const double* d_cj = f.in(hCj, nsys);
     double* work = (c->n <= TINY_N) ? c->lu : c->jw;
-    f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] { return launch_jac(c, work, f.idx, d_cj, nsys, hTn, hCj, hIdx); });
-    return factor_and_report(f, work, hInfo);
+    const bool jin = jac_in_lu_on(c, true);  // J = B + cj*A is formed by the factorisation itself: no Jacobian kernel
+    const LuJac jq{c->A, c->B, d_cj, 0};
+    if (!jin) f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] { return launch_jac(c, work, f.idx, d_cj, nsys, hTn, hCj, hIdx); });
+    return factor_and_report(f, work, hInfo, jin ? &jq : nullptr);
 }
 
 int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, int reset_ee, int32_t* hInfo, const int32_t* hIdx,
@@ -1364,11 +1382,14 @@ int idahip_nls_sys_setup(idahip_ctx* c, const double* hTn, const double* hCj, in
     a.cj = f.in(hCj, nsys);
     fill_sys_args(c, a, reset_ee);
     double* work = (c->n <= TINY_N) ? c->lu : c->jw;
-    // the linear dense residual sweeps A and B anyway: J = B + cj*A falls out of the same pass
-    const bool fused = c->kind == IDAHIP_LINEAR_DENSE && c->n > TINY_N;
+    // the linear dense residual sweeps A and B anyway: J = B + cj*A falls out of the same pass -- unless the factorisation forms it
+    // as it loads (jac_in_lu_on): the plain sweep then, and no J in memory at all
+    const bool jin = jac_in_lu_on(c, true);
+    const LuJac jq{c->A, c->B, a.cj, 0};
+    const bool fused = c->kind == IDAHIP_LINEAR_DENSE && c->n > TINY_N && !jin;
     f.launch(fused ? IDAHIP_K_SYS_JAC : IDAHIP_K_SYS, nsys, nullptr, [&] { return launch_sys(c, a, nsys, fused ? work : nullptr, hTn, hIdx); });
-    if (!fused) f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] { return launch_jac(c, work, a.idx, a.cj, nsys, hTn, hCj, hIdx); });
-    return factor_and_report(f, work, hInfo);
+    if (!fused && !jin) f.launch(IDAHIP_K_JAC, nsys, nullptr, [&] { return launch_jac(c, work, a.idx, a.cj, nsys, hTn, hCj, hIdx); });
+    return factor_and_report(f, work, hInfo, jin ? &jq : nullptr);
 }
 
 int idahip_nls_lsetup_dq(idahip_ctx* c, const double* hTn, const double* hCj, const double* hHh, int32_t* hInfo, const int32_t* hIdx,
@@ -2566,6 +2587,8 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     a.ypout = hYPout ? c->tiny_ypout : nullptr;
     a.round_base = call->round_base;
     a.fused_jac = (c->kind == IDAHIP_LINEAR_DENSE && !c->jac_dq && !kry) ? 1 : 0;
+    a.jac_in_lu = (a.fused_jac && jac_in_lu_on(c, false)) ? 1 : 0;
+    const LuJac jq{c->A, c->B, c->rnd_d + batch, 1};  // (cj by system id: RoundArgs::cj)
     if ((c->jac_dq || (kry && c->kry_prec)) && !c->dq_hh && (rc = dalloc(c, &c->dq_hh, (size_t)batch))) return rc;
     a.lu_period = kry ? 1 : c->lu_period;  // (a psetup is one band launch: nothing to amortise)
     KryRoundArgs kr{};
@@ -2632,7 +2655,11 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
                 sa.reset_ee = 1; sa.skip = a.skipP;
                 if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
             }
-            if (a.fused_jac) {
+            if (a.jac_in_lu) {  // the plain sweep for the systems that set up: the factorisation forms J from A and B itself
+                KTimer kt(c, IDAHIP_K_SYS, 0);
+                sa.skip = a.skipL;
+                if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+            } else if (a.fused_jac) {
                 KTimer kt(c, IDAHIP_K_SYS_JAC, 0);
                 sa.skip = a.skipL;
                 if ((rc = launch_sys(c, sa, batch, c->jw))) return rc;
@@ -2659,7 +2686,7 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
                 }
                 KTimer kt(c, IDAHIP_K_LU, 0);
                 if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, a.lu_list, nlu, d_cnt);
-                else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt);
+                else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt, a.jac_in_lu ? &jq : nullptr);
                 if (rc) return rc;
                 if ((rc = post_launch(c, "lu"))) return rc;
             }
@@ -2759,6 +2786,17 @@ int idahip_set_lu_variant(idahip_ctx* c, int variant) {
     c->lu_variant = variant;
     return 0;
 }
+
+int idahip_set_jac_in_lu(idahip_ctx* c, int on) {
+    if (!c) return -1;
+    if (on && !jac_in_lu_can(c))
+        return fail(c, -2, "idahip_set_jac_in_lu: J = B + cj*A inside the LU is for a dense IDAHIP_LINEAR_DENSE ctx with %d < n <= %d", TINY_N, WP_MAX_ROWS);
+    c->jac_in_lu = on ? 1 : 0;
+    return 0;
+}
+
+// 0: nowhere now; 1: in idahip_round_solve alone (never set, n > 448); 2: there and in the list entry points (set to 1)
+int idahip_jac_in_lu(const idahip_ctx* c) { return c ? (jac_in_lu_on(c, true) ? 2 : jac_in_lu_on(c, false) ? 1 : 0) : -1; }
 
 // ------------------------------------------------------------------------------------------------ measurement
 int idahip_timing_enable(idahip_ctx* c, int on) {

@@ -13,10 +13,17 @@ namespace idahip {
 // rank-64 trailing kernel; a final row scatter.
 // d_cnt (optional): the list's length lives on the device and nsys is only its upper bound (variant 4): every kernel's
 // surplus workgroups leave on reading it.
+// jq (optional; lu_jac_eligible): the matrices are J = B + cj*A of a linear dense ctx and `work` does NOT hold them: the first
+// super-panel's launches and the first trailing launch form J from A and B as they load (LuJac, lu_kernels.hpp).
+
+// J can be formed inside the factorisation on the wave-per-matrix pipeline alone: TINY_N < n <= WP_MAX_ROWS, LU variant 4
+inline bool lu_jac_eligible(const idahip_ctx* c) { return c->n > TINY_N && c->n <= WP_MAX_ROWS && c->lu_variant >= 4; }
+
 inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* out, long ostride, long long* piv, long pstride,
-                             int* perm, const int* d_idx, int nsys, const int* d_cnt = nullptr) {
+                             int* perm, const int* d_idx, int nsys, const int* d_cnt = nullptr, const LuJac* jq = nullptr) {
     const int n = c->n;
     if (nsys == 0) return 0;
+    if (jq && !lu_jac_eligible(c)) return fail(c, -3, "J = B + cj*A inside the LU needs %d < n <= %d and LU variant 4", TINY_N, WP_MAX_ROWS);
     if (n <= TINY_N) {
         // tiny path factors in place in `work` (one thread per system, reference loops verbatim)
         hipLaunchKernelGGL(tiny_getrf_kernel, dim3((nsys + 63) / 64), dim3(64), 0, c->stream, work, wstride, d_idx, nsys, n, piv,
@@ -115,8 +122,17 @@ inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* 
         case 7: IDAHIP_WP_LAUNCH(7); break;                                                                 \
         default: IDAHIP_WP_LAUNCH(8); break;                                                                \
     }
-            IDAHIP_WP_SWITCH()
-            hipLaunchKernelGGL((lu_wavepanel_kernel<true, 0>), dim3(nsys), dim3(64), 0, c->stream, w, k0);
+            if (jq && k0 == 0) {
+                // the first super-panel of a J that has not been formed: eight slots (n > 448: the flagship's size, and what a ctx
+                // takes unasked) with the slot count folded; any fewer, on request only (idahip_set_jac_in_lu), by the instantiation
+                // that reads the count from the matrix size -- eight slots' registers and loads whatever the count, not measured
+                if (ns == 8) hipLaunchKernelGGL((lu_wavepanel_kernel<false, 8, LuJac>), dim3(nsys), dim3(64), 0, c->stream, w, k0, *jq);
+                else hipLaunchKernelGGL((lu_wavepanel_kernel<false, 0, LuJac>), dim3(nsys), dim3(64), 0, c->stream, w, k0, *jq);
+                hipLaunchKernelGGL((lu_wavepanel_kernel<true, 0, LuJac>), dim3(nsys), dim3(64), 0, c->stream, w, k0, *jq);
+            } else {
+                IDAHIP_WP_SWITCH()
+                hipLaunchKernelGGL((lu_wavepanel_kernel<true, 0>), dim3(nsys), dim3(64), 0, c->stream, w, k0);
+            }
 #undef IDAHIP_WP_SWITCH
 #undef IDAHIP_WP_LAUNCH
         } else {
@@ -149,7 +165,9 @@ inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* 
                 // kernel at full occupancy; the update kernel's workgroups for them leave at once
                 hipLaunchKernelGGL(lu_u12_zero_kernel, dim3(nsys8 * ncb), dim3(256), 0, c->stream, w, k0, nsys, ncb);
                 hipLaunchKernelGGL(lu_trail64w_kernel<LU_BIG_MAX_N>, dim3(nsys8 * (ncb + (nsplit - 1) * nbs)), dim3(256), 0, c->stream, w, k0, nsys, ncb, nsplit);
-            } else
+            } else if (jq && k0 == 0)
+                hipLaunchKernelGGL((lu_trail64w_kernel<LU_MAX_N, LuJac>), dim3(nsys8 * ncb), dim3(256), 0, c->stream, w, k0, nsys, ncb, 1, *jq);
+            else
                 hipLaunchKernelGGL(lu_trail64w_kernel<LU_MAX_N>, dim3(nsys8 * ncb), dim3(256), 0, c->stream, w, k0, nsys, ncb, 1);
         }
     }

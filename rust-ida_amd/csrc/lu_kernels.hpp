@@ -61,6 +61,19 @@ struct LuWs {
 };
 constexpr int L11_STRIDE = 64 * 64;  // elements per system in LuWs::l11
 
+// The Newton matrix of a linear dense ctx, J = B + cj*A, formed by the factorisation's first launches as they load (k0 == 0:
+// lu_wavepanel_kernel<.., LuJac>, lu_trail64w_kernel<1024, LuJac>; idahip_set_jac_in_lu) -- J then never passes through memory. Multiply, then add,
+// unfused: the expression of linear_sys_kernel<*, true> and linear_jac_kernel.
+struct LuJac {
+    const double* a;   // [batch][n * n] A, column-major
+    const double* b;   // [batch][n * n] B
+    const double* cj;  // the systems' cj: by list position, or (cj_by_sys) by system id
+    int cj_by_sys;
+};
+// the kernels that form J take a LuJac as one more argument (a parameter pack that is empty in the plain instantiations)
+__host__ __device__ __forceinline__ LuJac lu_jac_arg() { return LuJac{nullptr, nullptr, nullptr, 0}; }
+__host__ __device__ __forceinline__ LuJac lu_jac_arg(const LuJac& j) { return j; }
+
 __global__ void lu_init_kernel(LuWs w) {
     if (w.cnt && (int)blockIdx.x >= *w.cnt) return;
     const int b = w.idx[blockIdx.x];
@@ -910,8 +923,17 @@ __global__ __launch_bounds__(256) void lu_trail_kernel(LuWs w, int k0, int nsys,
 //      stored in LDS with the lane's four rows / four columns adjacent, so a k-step is four ds_read_b128 for 32 VALU
 //      ops; two k-chunks of 32 through the strip buffer, the next strip's operands in flight behind the second chunk.
 //      49 KB of LDS per workgroup -> three workgroups per CU.
-template <int MAXROWS>
-__global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kernel(LuWs w, int k0, int nsys, int ncb, int nsplit_arg) {
+// JAC (MAXROWS <= 1024, k0 == 0; LuJac): the matrix is J = B + cj*A and only its first super-panel is in the work matrix. The
+// pivot-row gather and the strips' C tiles come from A and B; the multipliers come from the work matrix and the stores go where
+// they always went. The kernel sits at its register limit, so a strip's tile is formed in place: its A values travel where the
+// plain kernel's C values do (in flight behind the strip before), its B values are requested when the strip before has been
+// stored -- into the registers that strip's arithmetic has left -- and the tile becomes b + cj*a there (form_J).
+// (The J-forming instantiation carries one more kernel argument, the pack J = {LuJac}; the plain ones have the signature they always had.)
+template <int MAXROWS, class... J>
+__global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kernel(LuWs w, int k0, int nsys, int ncb, int nsplit_arg, const J... jarg) {
+    constexpr bool JAC = sizeof...(J) == 1;
+    const LuJac jq = lu_jac_arg(jarg...);
+    static_assert(!JAC || MAXROWS <= 1024, "J is formed on the buffer-descriptor path only");
     constexpr int NB = 64, KC = 32;
     constexpr bool NOPRO = tb::NOPRO;  // timing build (exp_switches.hpp): no gather, no U12 solve (U12 = constants); false in the product
     const int nsplit = MAXROWS > 1024 ? nsplit_arg : 1;  // the row split exists for large n only
@@ -969,6 +991,10 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     const int mrem = n - k0 - NB;  // live rows after this panel (> 0)
     const int cb0 = k0 + NB + cbi * 64;
     const int ncols = (n - cb0) < 64 ? (n - cb0) : 64;
+    // JAC: this column block of A and of B (what lies beyond the block's last column is out of the descriptors' range and reads +0.0)
+    const double* __restrict__ Ja = JAC ? jq.a + (long)b * n * n + (long)cb0 * n : nullptr;
+    const double* __restrict__ Jb = JAC ? jq.b + (long)b * n * n + (long)cb0 * n : nullptr;
+    const double jcj = JAC ? ldc(jq.cj + (jq.cj_by_sys ? b : mi)) : 0.0;
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int pl = 4 * (lane & 15) + (lane >> 4);  // LDS slot of column `lane`: columns q, q+16, q+32, q+48 sit together
@@ -1014,6 +1040,15 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
             const int nc = ncols - 16 * j;
             rsC[j] = __builtin_amdgcn_make_buffer_rsrc(A + (long)(cb0 + 16 * j) * n, 0, (nc > 0 ? nc : 0) * n * 8, RSFLAGS);
         }
+    }
+    // JAC: one descriptor per operand for the whole block (the kernel has no scalar registers to spare for four each): the column
+    // group's offset 16 j n goes into the lane's offset, where the range check sees it
+    // (and one for the block in the work matrix, in place of rsC: the strips' stores)
+    __amdgpu_buffer_rsrc_t rsJa, rsJb, rsJw;
+    if constexpr (JAC) {
+        rsJa = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(Ja), 0, ncols * n * 8, RSFLAGS);
+        rsJb = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(Jb), 0, ncols * n * 8, RSFLAGS);
+        rsJw = __builtin_amdgcn_make_buffer_rsrc(A + (long)cb0 * n, 0, ncols * n * 8, RSFLAGS);
     }
 
     // ---- this lane's share of a strip: rows a + 4i, columns q + 16j
@@ -1065,8 +1100,32 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
             vo[i] = (row * 8u + qn8) | ((unsigned)(mrem - 1 - ri) & OOB);  // (the sign of mrem - 1 - ri: set from row mrem on)
         }
     };
+    const unsigned gn8 = (unsigned)(16 * n) * 8u;  // JAC: bytes from one 16-column group of the block to the next
+    // JAC: load_C has brought the strip's A values to creg; its B values are requested here, once the strip before has been stored,
+    // into registers that strip's arithmetic has left, and creg becomes J's tile b + cj*a in place. The strip loop then carries
+    // what the plain kernel's carries and nothing more.
+    auto form_J = [&](int s) {
+        unsigned bvo[4];
+        row_offsets(s, bvo);
+        double breg[4][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) breg[i][j] = buf_load_f64<tb::NT_TRAIL>(rsJb, bvo[i] + (unsigned)j * gn8, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) creg[i][j] = breg[i][j] + jcj * creg[i][j];
+    };
     auto load_C = [&](int s) {
-        if constexpr (BUF) {
+        if constexpr (JAC) {  // the strip's A values
+            unsigned cvo[4];
+            row_offsets(s, cvo);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) creg[i][j] = buf_load_f64<tb::NT_TRAIL>(rsJa, cvo[i] + (unsigned)j * gn8, 0);
+        } else if constexpr (BUF) {
             unsigned cvo[4];
             row_offsets(s, cvo);
 #pragma unroll
@@ -1117,12 +1176,24 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
             // this wave's 16 columns through a descriptor that ends with the block: a lane without a column reads +0.0 (it
             // is kept out of the zero test and stores 0.0 below)
             const int nc = ncols - 16 * wave;
-            const __amdgpu_buffer_rsrc_t rsG =
-                __builtin_amdgcn_make_buffer_rsrc(A + (long)(cb0 + 16 * wave) * n, 0, (nc > 0 ? nc : 0) * n * 8, RSFLAGS);
+            if constexpr (JAC) {  // the pivot rows' entries of A into u, of B into the registers the solve's multiplier ring will use
+                (void)nc;
+                const unsigned wn8 = (unsigned)wave * gn8;
+                double ub[16];
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                if constexpr (tb::NOGATHER) u[i] = 1.0e-3 * (double)(1 + ((i + pr[i]) & 7));  // timing build
-                else u[i] = buf_load_f64(rsG, (unsigned)pr[i] * 8u + qn8, 0);
+                for (int i = 0; i < 16; ++i) u[i] = buf_load_f64(rsJa, (unsigned)pr[i] * 8u + qn8 + wn8, 0);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) ub[i] = buf_load_f64(rsJb, (unsigned)pr[i] * 8u + qn8 + wn8, 0);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) u[i] = ub[i] + jcj * u[i];
+            } else {
+                const __amdgpu_buffer_rsrc_t rsG =
+                    __builtin_amdgcn_make_buffer_rsrc(A + (long)(cb0 + 16 * wave) * n, 0, (nc > 0 ? nc : 0) * n * 8, RSFLAGS);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    if constexpr (tb::NOGATHER) u[i] = 1.0e-3 * (double)(1 + ((i + pr[i]) & 7));  // timing build
+                    else u[i] = buf_load_f64(rsG, (unsigned)pr[i] * 8u + qn8, 0);
+                }
             }
         }
         store_live();
@@ -1209,7 +1280,9 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
         for (int pass = 0; pass < NB / 4; ++pass) {
             const int k = pass * 4 + wave;
             const int pr = ldc(prow + k);
-            const double g = (lane < ncols) ? A[(long)(cb0 + lane) * n + pr] : 0.0;
+            double g;
+            if constexpr (JAC) g = (lane < ncols) ? Jb[(long)lane * n + pr] + jcj * Ja[(long)lane * n + pr] : 0.0;
+            else g = (lane < ncols) ? A[(long)(cb0 + lane) * n + pr] : 0.0;
             nz = nz || (g != 0.0);
             Us[k][pl] = g;
         }
@@ -1226,7 +1299,9 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     };
     if (MAXROWS <= 1024 && !NOPRO) stage_l11(0);
     lds_barrier();
-    if ((s_nz[0] | s_nz[1] | s_nz[2] | s_nz[3]) == 0) {
+    // (JAC: no short cut past the strips -- the block's rows below have to reach the work matrix even when nothing is subtracted from
+    // them; the solve below finds every entry zero and the strips store the tile as it was formed)
+    if (!JAC && (s_nz[0] | s_nz[1] | s_nz[2] | s_nz[3]) == 0) {
         // the 64 pivot rows are zero across this whole column block (banded matrices, off the band): the triangular solve
         // leaves them as they are (a_kj == 0: column untouched, dense.rs:148) and nothing is subtracted from the rows below
         if (split != 0) return;
@@ -1366,7 +1441,7 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     TSTAMP(4);
     const unsigned kmask0 = (unsigned)__builtin_amdgcn_readfirstlane((int)s_kmask[0]);
     const unsigned kmask1 = (unsigned)__builtin_amdgcn_readfirstlane((int)s_kmask[1]);
-    if (slow && (kmask0 | kmask1) == 0u) return;  // (uniform over the workgroup) U12 of this block is all zeros: nothing to subtract
+    if (!JAC && slow && (kmask0 | kmask1) == 0u) return;  // (uniform over the workgroup) U12 of this block is all zeros: nothing to subtract
     if (MAXROWS > 1024 && slow) {
         // Large n, U12 nearly empty (a banded matrix: a few columns next to the panel, a few pivot rows): one live row per
         // thread, and only the columns and pivot rows that have a non-zero entry are touched -- the strips below would read
@@ -1453,6 +1528,9 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
         }
     };
 
+    if constexpr (JAC) {
+        if (s0 < nstrips) form_J(s0);
+    }
 #pragma unroll 1
     for (int s = s0; s < nstrips; s += sstep) {
 #pragma unroll
@@ -1490,7 +1568,13 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) buf_store_f64<tb::NT_TRAIL>(rsC[j], svo[i], 0, c[i][j]);  // no such row or column: out of range, dropped
+                for (int i = 0; i < 4; ++i) {  // no such row or column: out of range, dropped
+                    if constexpr (JAC) buf_store_f64<tb::NT_TRAIL>(rsJw, svo[i] + (unsigned)j * gn8, 0, c[i][j]);
+                    else buf_store_f64<tb::NT_TRAIL>(rsC[j], svo[i], 0, c[i][j]);
+                }
+            if constexpr (JAC) {
+                if (s + sstep < nstrips) form_J(s + sstep);
+            }
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)

@@ -39,8 +39,15 @@ constexpr int WP_RING(int ns) { return !tb::WP_DEEP_RING ? 2 : (ns >= 1 && ns <=
 // NS > 0: the number of slots (= ceil(live rows / 64)) as a compile-time constant -- the per-slot guards fold away and the
 // registers of the unused slots are never allocated (eight instantiations of the FAST kernel, one per super-panel of an
 // N = 512 factorisation); NS = 0: taken from the matrix size at run time (the SLOW kernel).
-template <bool SLOWK, int NS>
-__global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void lu_wavepanel_kernel(LuWs w, const int k0) {
+//
+// JAC (idahip_set_jac_in_lu, k0 == 0 only): the matrix to factor is J = B + cj*A of a linear dense ctx and has not been formed: the
+// block loads read the columns of A and B and combine them, multiply then add, unfused -- the expression of linear_sys_kernel<*, true>
+// and linear_jac_kernel. The blocks are stored to the work matrix as ever, so the multiplier re-reads of the left-looking loop, the
+// SLOW launch's replay and the transposed L11 find there what they always found.
+// (The J-forming instantiations carry one more kernel argument, the pack J = {LuJac}; the plain ones have the signature they always had.)
+template <bool SLOWK, int NS, class... J>
+__global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void lu_wavepanel_kernel(LuWs w, const int k0, const J... jarg) {
+    constexpr bool JAC = sizeof...(J) == 1;
     constexpr int BIG = 1 << 20;  // pstep of a row that is still live
     if (w.cnt && (int)blockIdx.x >= *w.cnt) return;
     const int b = w.idx[blockIdx.x];
@@ -79,18 +86,63 @@ __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void l
     // ------------------------------------------------------------------------------------------------------------------
     // one block of `WB` (= 8 unless PARTIAL) columns starting at column b8 of the super-panel; x = the block, in registers.
     // returns 0 = done, 1 = zero pivot (info set), 2 = FAST assumptions violated (nothing stored)
-    auto load_block = [&](double (&x)[8][8], const int b8, const int wb) {
+    // JAC: the block of J = B + cj*A. A's columns go where the block will live, all slots at once as the plain load's do; B's pass
+    // through a ring of JT register sets -- the registers of the multiplier ring and the pivot-row copies, which are dead while a
+    // block loads -- and a slot becomes b + cj*a as its B values arrive: the kernel keeps the register count of the plain one.
+    // Descriptor loads (the rows' 32-bit offsets are there already): a slot without rows reads row 0 and is zeroed afterwards.
+    const LuJac jq = lu_jac_arg(jarg...);
+    double jcj = 0.0;
+    __amdgpu_buffer_rsrc_t rsJa = rsrc, rsJb = rsrc;
+    if constexpr (JAC) {
+        jcj = jq.cj[jq.cj_by_sys ? b : (int)blockIdx.x];
+        rsJa = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(jq.a) + (long)b * n * n, 0, n * n * 8, 0x00020000);
+        rsJb = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(jq.b) + (long)b * n * n, 0, n * n * 8, 0x00020000);
+    }
+    auto load_block_jac = [&](double (&x)[8][8], const int b8, const int wb) {
+        constexpr int JT = 2;
+        const int coloff = (k0 + b8) * n * 8;
+        auto jo = [&](const int j) { return coloff + (j < wb ? j : wb - 1) * n * 8; };  // (a partial block: its last column once more, zeroed below)
         static_for<0, NSC>([&](auto st) {
             constexpr int S = decltype(st)::value;
-            if (S < nslots) {
-                const double* __restrict__ src = A + (long)(k0 + b8) * n + rowid[S];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) x[S][j] = (j < wb) ? src[(long)j * n] : 0.0;
-            } else {
+            for (int j = 0; j < 8; ++j) x[S][j] = buf_load_f64(rsJa, roff[S], jo(j));
+        });
+        double t[JT][8];
+        static_for<0, (JT < NSC ? JT : NSC)>([&](auto st) {
+            constexpr int S = decltype(st)::value;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) x[S][j] = 0.0;
+            for (int j = 0; j < 8; ++j) t[S][j] = buf_load_f64(rsJb, roff[S], jo(j));
+        });
+        static_for<0, NSC>([&](auto st) {
+            constexpr int S = decltype(st)::value;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const double v = t[S % JT][j] + jcj * x[S][j];
+                x[S][j] = (S < nslots && j < wb) ? v : 0.0;
+            }
+            if constexpr (S + JT < NSC) {
+                __builtin_amdgcn_sched_barrier(0);  // (the ring's next request stays behind the use of the registers it fills)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) t[S % JT][j] = buf_load_f64(rsJb, roff[S + JT], jo(j));
             }
         });
+    };
+    auto load_block = [&](double (&x)[8][8], const int b8, const int wb) {
+        if constexpr (JAC) {
+            load_block_jac(x, b8, wb);
+        } else {
+            static_for<0, NSC>([&](auto st) {
+                constexpr int S = decltype(st)::value;
+                if (S < nslots) {
+                    const double* __restrict__ src = A + (long)(k0 + b8) * n + rowid[S];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) x[S][j] = (j < wb) ? src[(long)j * n] : 0.0;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) x[S][j] = 0.0;
+                }
+            });
+        }
     };
     auto store_block = [&](const double (&x)[8][8], const int b8, const int wb) {
         static_for<0, NSC>([&](auto st) {

@@ -39,6 +39,7 @@ struct RoundArgs {
     long long round;        // index of this round within the call
     int first_round;        // systems enter the call in this round
     int fused_jac;          // the problem has a fused residual + Jacobian kernel (linear dense); otherwise two launches serve a setup
+    int jac_in_lu;          // linear dense, idahip_set_jac_in_lu: the factorisation forms J = B + cj*A itself, the systems that set up are swept by the plain residual
     int lu_period;          // idahip_set_lu_period: > 1 = a round may postpone its linear setups (round_lists_kernel), at most lu_period - 1 rounds in a row
     // per-system round state (device arrays of length batch)
     int* stepping;          // the system takes step attempts
@@ -271,7 +272,9 @@ __global__ __launch_bounds__(1024) void round_lists_kernel(RoundArgs a) {
         a.lu_cnt[0] = s_base;
         const unsigned long long cnt = (unsigned long long)s_base;  // the per-class statistics of the systems that set up in this round
         if (cnt) {
-            if (a.fused_jac) {
+            if (a.jac_in_lu) {
+                atomicAdd(&a.stats[IDAHIP_K_SYS], cnt);
+            } else if (a.fused_jac) {
                 atomicAdd(&a.stats[IDAHIP_K_SYS_JAC], cnt);
             } else {
                 atomicAdd(&a.stats[IDAHIP_K_SYS], cnt);
