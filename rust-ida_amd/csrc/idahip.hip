@@ -1529,7 +1529,7 @@ int idahip_newton_iter2(idahip_ctx* c, const double* hScale, const double* hTn, 
     // iteration m = 0 and its convergence test
     f.launch(IDAHIP_K_NEWTON_ITER, nsys, nullptr, [&] {
         const int rc = launch_newton_iter(c, a.idx, d_scale, d_sum, nullptr, nsys);
-        if (!rc) hipLaunchKernelGGL(ctest_kernel, tg, tb, 0, c->stream, (const double*)d_sum, n, 0, d_toldel, d_ss, d_eps, d_dn, d_conv, nsys);
+        if (!rc) hipLaunchKernelGGL(ctest_kernel<0>, tg, tb, 0, c->stream, (const double*)d_sum, n, d_toldel, d_ss, d_eps, d_dn, d_conv, nsys);
         return rc;
     });
     a.skip = d_conv;
@@ -1538,7 +1538,7 @@ int idahip_newton_iter2(idahip_ctx* c, const double* hScale, const double* hTn, 
     // iteration m = 1 and its convergence test
     f.launch(IDAHIP_K_NEWTON_ITER, 0, "ctest", [&] {
         const int rc = launch_newton_iter(c, a.idx, d_scale, d_sum, d_conv, nsys);
-        if (!rc) hipLaunchKernelGGL(ctest_kernel, tg, tb, 0, c->stream, (const double*)d_sum, n, 1, d_toldel, d_ss, d_eps, d_dn, d_conv, nsys);
+        if (!rc) hipLaunchKernelGGL(ctest_kernel<1>, tg, tb, 0, c->stream, (const double*)d_sum, n, d_toldel, d_ss, d_eps, d_dn, d_conv, nsys);
         return rc;
     });
     if (!f.fetch()) return f.rc;
@@ -2369,27 +2369,52 @@ static FlowArgs flow_args(idahip_ctx* c, const idahip_tiny_call* call) {
     return f;
 }
 
-int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc,
-                      double* hYout, double* hYPout) {
-    DevGuard dev_guard__(c);
-    if (!c) return -1;
-    if (!hSys || !call || !hRoundsDone || !hAcc || !call->touts || call->ntout < 1) return null_argument(c);
+// What idahip_tiny_solve and idahip_round_solve share around their launches. stepper_call_args: the refusals that come before an
+// entry point's own (extra: a further pointer it needs). stepper_call_begin: the refusals that come after them, the buffers, and the
+// four uploads (records, touts, start rounds, accumulator reset). stepper_call_end: the six downloads, left on the stream.
+static int stepper_call_args(idahip_ctx* c, const void* hSys, size_t sys_bytes, const idahip_tiny_call* call, const void* hRoundsDone, const void* hAcc,
+                             const void* extra) {
+    if (!hSys || !call || !hRoundsDone || !hAcc || !extra || !call->touts || call->ntout < 1) return null_argument(c);
     if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
-    if (c->n != 3 || (c->kind != IDAHIP_ROBERTS && c->kind != IDAHIP_LORENZ63))
-        return fail(c, -2, "the device-resident stepper takes the Roberts and Lorenz63 problems (n = 3)");
-    if (c->jac_dq && !c->h_constr.empty()) return fail(c, -2, "difference-quotient Jacobians and constraints do not combine (DESIGN.md section 4g)");
-    if (const int rcm = missing_id(c, "idahip_tiny_solve")) return rcm;
+    return 0;
+}
+static int stepper_call_begin(idahip_ctx* c, const char* who, const void* hSys, const idahip_tiny_call* call, bool outputs) {
+    if (const int rcm = missing_id(c, who)) return rcm;
     if (call->recycle && (!c->ic_y || !c->ic_yp)) return fail(c, -2, "recycle needs idahip_snapshot_initial");
     if (call->recycle && call->max_rounds < 1) return fail(c, -2, "recycle needs a round limit");
-    const int batch = c->batch, n = c->n;
-    int rc = stepper_buffers(c, call, hYout || hYPout);
-    if (rc) return rc;
-    const size_t ysz = (size_t)call->ntout * batch * n;
+    if (const int rc = stepper_buffers(c, call, outputs)) return rc;
+    const int batch = c->batch;
     IDAHIP_HIP(c, hipMemcpyAsync(c->tiny_sys, hSys, (size_t)batch * sizeof(idactl::SysCore), hipMemcpyHostToDevice, c->stream));
     IDAHIP_HIP(c, hipMemcpyAsync(c->tiny_touts, call->touts, sizeof(double) * call->ntout, hipMemcpyHostToDevice, c->stream));
     if (call->start_round)
         IDAHIP_HIP(c, hipMemcpyAsync(c->tiny_start, call->start_round, sizeof(int64_t) * batch, hipMemcpyHostToDevice, c->stream));
     IDAHIP_HIP(c, hipMemsetAsync(c->tiny_acc, 0, 2 * sizeof(uint64_t), c->stream));
+    return 0;
+}
+static int stepper_call_end(idahip_ctx* c, void* hSys, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc, double* hYout, double* hYPout) {
+    const int batch = c->batch;
+    const size_t ysz = (size_t)call->ntout * batch * c->n;
+    IDAHIP_HIP(c, hipMemcpyAsync(hSys, c->tiny_sys, (size_t)batch * sizeof(idactl::SysCore), hipMemcpyDeviceToHost, c->stream));
+    if (call->nroots > 0)
+        IDAHIP_HIP(c, hipMemcpyAsync(call->root_states, c->tiny_roots, (size_t)batch * sizeof(idahip_root_state), hipMemcpyDeviceToHost, c->stream));
+    IDAHIP_HIP(c, hipMemcpyAsync(hRoundsDone, c->tiny_rounds, sizeof(int64_t) * batch, hipMemcpyDeviceToHost, c->stream));
+    IDAHIP_HIP(c, hipMemcpyAsync(hAcc, c->tiny_acc, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (hYout) IDAHIP_HIP(c, hipMemcpyAsync(hYout, c->tiny_yout, sizeof(double) * ysz, hipMemcpyDeviceToHost, c->stream));
+    if (hYPout) IDAHIP_HIP(c, hipMemcpyAsync(hYPout, c->tiny_ypout, sizeof(double) * ysz, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_tiny_call* call, int64_t* hRoundsDone, uint64_t* hAcc,
+                      double* hYout, double* hYPout) {
+    DevGuard dev_guard__(c);
+    if (!c) return -1;
+    if (int rca = stepper_call_args(c, hSys, sys_bytes, call, hRoundsDone, hAcc, hAcc)) return rca;
+    if (c->n != 3 || (c->kind != IDAHIP_ROBERTS && c->kind != IDAHIP_LORENZ63))
+        return fail(c, -2, "the device-resident stepper takes the Roberts and Lorenz63 problems (n = 3)");
+    if (c->jac_dq && !c->h_constr.empty()) return fail(c, -2, "difference-quotient Jacobians and constraints do not combine (DESIGN.md section 4g)");
+    const int batch = c->batch, n = c->n;
+    int rc = stepper_call_begin(c, "idahip_tiny_solve", hSys, call, hYout || hYPout);
+    if (rc) return rc;
     TinyIdaArgs a;
     a.sys = (idactl::SysCore*)c->tiny_sys;
     a.v = vec_state(c);
@@ -2437,13 +2462,7 @@ int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_
         hipLaunchKernelGGL(kern, dim3((batch + spw - 1) / spw), dim3(spw), shm, c->stream, a, lds_vec, constr ? (const double*)c->d_constr : (const double*)nullptr);
         if ((rc = post_launch(c, "tiny_ida"))) return rc;
     }
-    IDAHIP_HIP(c, hipMemcpyAsync(hSys, c->tiny_sys, (size_t)batch * sizeof(idactl::SysCore), hipMemcpyDeviceToHost, c->stream));
-    if (call->nroots > 0)
-        IDAHIP_HIP(c, hipMemcpyAsync(call->root_states, c->tiny_roots, (size_t)batch * sizeof(idahip_root_state), hipMemcpyDeviceToHost, c->stream));
-    IDAHIP_HIP(c, hipMemcpyAsync(hRoundsDone, c->tiny_rounds, sizeof(int64_t) * batch, hipMemcpyDeviceToHost, c->stream));
-    IDAHIP_HIP(c, hipMemcpyAsync(hAcc, c->tiny_acc, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (hYout) IDAHIP_HIP(c, hipMemcpyAsync(hYout, c->tiny_yout, sizeof(double) * ysz, hipMemcpyDeviceToHost, c->stream));
-    if (hYPout) IDAHIP_HIP(c, hipMemcpyAsync(hYPout, c->tiny_ypout, sizeof(double) * ysz, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stepper_call_end(c, hSys, call, hRoundsDone, hAcc, hYout, hYPout))) return rc;
     IDAHIP_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2486,50 +2505,111 @@ static int stepper_buffers(idahip_ctx* c, const idahip_tiny_call* call, bool out
     return 0;
 }
 
-// The Newton solve of one round on a Krylov ctx (round_ida.hpp, idahip_set_krylov_rounds): the residuals, the band preconditioner's
-// setup on the device-built list, and four passes of { SPGMR ; control ; residual }, booked under the classes of the host stepper's
-// calls. Always the one-launch solve (idahip_set_krylov_fused is ignored: the two paths are bit-identical).
-static int krylov_round_newton(idahip_ctx* c, const RoundArgs& a, const KryRoundArgs& kr, SysArgs& sa) {
+// the setup launches of a round on a Krylov ctx: the residual of the systems that set up (no Jacobian is formed: nje stays) and the
+// band preconditioner's setup on the device-built list
+static int krylov_round_setup(idahip_ctx* c, const RoundArgs& a, SysArgs& sa) {
     const int batch = c->batch, n = c->n;
-    const dim3 per_sys((batch + 255) / 256), blk(256);
     int rc;
-    {   // sys(y0), y <- y0 = 0: every system whose Newton solve starts in this round, those without a setup ...
-        KTimer kt(c, IDAHIP_K_SYS, 0);
-        sa.reset_ee = 1; sa.skip = a.skipP;
-        if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
-    }
-    {   // ... and those with one (no Jacobian is formed: nje stays)
+    {
         KTimer kt(c, IDAHIP_K_SYS, 0);
         sa.skip = a.skipL;
         if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
     }
-    if (c->kry_prec) {  // psetup of the listed systems at the residual sys has just left: P, then its factors
-        {
-            KTimer kt(c, IDAHIP_K_JAC, 0);
-            hipLaunchKernelGGL(dq_round_prep_kernel, per_sys, blk, 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh, batch,
-                               (long)std::min(c->kry_pml + c->kry_pmu + 1, n));
-            DqArgs d;
-            fill_dq_args(c, d, c->kry_pml, c->kry_pmu, c->kry_pldab);
-            d.idx = a.ident; d.cj = a.cj; d.hh = c->dq_hh; d.skip = a.skipL;
-            d.out = c->kry_pab; d.compact = 0;
-            if ((rc = launch_band_dq(c, d, batch, "band DQ jac (preconditioner)"))) return rc;
-        }
-        KTimer kt(c, IDAHIP_K_LU, 0);
-        if ((rc = band_factor(c, c->kry_pab, (long)c->kry_pldab * n, c->kry_ppiv, n, c->kry_pml, c->kry_pmu, a.lu_list, batch, a.lu_cnt))) return rc;
+    if (!c->kry_prec) return 0;
+    {   // psetup of the listed systems at the residual sys has just left: P, then its factors
+        KTimer kt(c, IDAHIP_K_JAC, 0);
+        hipLaunchKernelGGL(dq_round_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh, batch,
+                           (long)std::min(c->kry_pml + c->kry_pmu + 1, n));
+        DqArgs d;
+        fill_dq_args(c, d, c->kry_pml, c->kry_pmu, c->kry_pldab);
+        d.idx = a.ident; d.cj = a.cj; d.hh = c->dq_hh; d.skip = a.skipL;
+        d.out = c->kry_pab; d.compact = 0;
+        if ((rc = launch_band_dq(c, d, batch, "band DQ jac (preconditioner)"))) return rc;
     }
-    hipLaunchKernelGGL(round_krylov_ctl_kernel, per_sys, blk, 0, c->stream, a, kr, 0);
+    KTimer kt(c, IDAHIP_K_LU, 0);
+    return band_factor(c, c->kry_pab, (long)c->kry_pldab * n, c->kry_ppiv, n, c->kry_pml, c->kry_pmu, a.lu_list, batch, a.lu_cnt);
+}
+
+// the setup launches of a round on a direct ctx: residual and Jacobian of the systems that set up, and the factorisation of the
+// device-built list. lu_cnt_on_host: the list's length is on its way to the host (ev_cnt) and sizes the LU's launches.
+static int direct_round_setup(idahip_ctx* c, const RoundArgs& a, SysArgs& sa, bool lu_cnt_on_host) {
+    const int batch = c->batch, n = c->n;
+    const long nn = (long)n * n;
+    int rc;
+    if (a.jac_in_lu) {  // the plain sweep for the systems that set up: the factorisation forms J from A and B itself
+        KTimer kt(c, IDAHIP_K_SYS, 0);
+        sa.skip = a.skipL;
+        if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+    } else if (a.fused_jac) {  // J = B + cj A falls out of the same sweep
+        KTimer kt(c, IDAHIP_K_SYS_JAC, 0);
+        sa.skip = a.skipL;
+        if ((rc = launch_sys(c, sa, batch, c->jw))) return rc;
+    } else {  // no fused residual + Jacobian kernel for this problem: the residual, then the Jacobian of the same systems
+        {
+            KTimer kt(c, IDAHIP_K_SYS, 0);
+            sa.skip = a.skipL;
+            if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+        }
+        KTimer kt(c, IDAHIP_K_JAC, 0);
+        if (c->jac_dq)  // the systems' hh from their records, and their nre_dq
+            hipLaunchKernelGGL(dq_round_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh,
+                               batch, dq_evals(c));
+        if ((rc = launch_jac(c, c->jw, a.ident, a.cj, batch, nullptr, nullptr, nullptr, a.skipL, c->dq_hh))) return rc;
+    }
+    int nlu = batch;
+    const int* d_cnt = a.lu_cnt;
+    if (lu_cnt_on_host) {
+        IDAHIP_HIP(c, hipEventSynchronize(c->ev_cnt));
+        nlu = c->rnd_host[2];
+        d_cnt = nullptr;
+        if (nlu < 0 || nlu > batch) return fail(c, -4, "list length %d outside 0..%d", nlu, batch);
+    }
+    const LuJac jq{c->A, c->B, a.cj, 1};  // (cj by system id)
+    KTimer kt(c, IDAHIP_K_LU, 0);
+    if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, a.lu_list, nlu, d_cnt);
+    else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt, a.jac_in_lu ? &jq : nullptr);
+    if (rc) return rc;
+    return post_launch(c, "lu");
+}
+
+// The Newton solve of one round (round_ida.hpp): the residual of the systems that start without a linear setup, the residual and
+// setup of those that start with one, the control kernel's phase 0, then MAXNLSIT passes of { iteration ; control ; residual },
+// booked under the classes of the host stepper's calls. A direct ctx and a Krylov ctx (kr non-null: idahip_set_krylov_rounds) differ
+// in the setup launches, the iteration launch and the control kernel's instantiation. A Krylov ctx always takes the one-launch solve
+// (idahip_set_krylov_fused is ignored: the two paths are bit-identical).
+static int round_newton(idahip_ctx* c, const RoundArgs& a, const KryRoundArgs* kr, SysArgs& sa, bool lu_cnt_on_host) {
+    const int batch = c->batch;
+    const dim3 per_sys((batch + 255) / 256), blk(256);
+    const auto ctl = [&](int phase) {
+        if (kr) hipLaunchKernelGGL(round_ctl_kernel<true>, per_sys, blk, 0, c->stream, a, *kr, phase);
+        else hipLaunchKernelGGL(round_ctl_kernel<false>, per_sys, blk, 0, c->stream, a, NoKryArgs{}, phase);
+    };
+    int rc;
+    {   // sys(y0), y <- y0 = 0 (newton.rs:73)
+        KTimer kt(c, IDAHIP_K_SYS, 0);
+        sa.reset_ee = 1; sa.skip = a.skipP;
+        if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
+    }
+    if ((rc = kr ? krylov_round_setup(c, a, sa) : direct_round_setup(c, a, sa, lu_cnt_on_host))) return rc;
+    ctl(0);
     KryArgs ka{};
-    fill_kry_args(c, ka);
-    ka.idx = a.ident; ka.cj = a.cj; ka.tol = kr.tol; ka.skip = a.skipI;
-    ka.newton = 1;
-    ka.nli = c->kry_rint; ka.flag = c->kry_rint + batch; ka.resnorm = c->kry_rres; ka.nrm = a.nrm_out;
+    if (kr) {
+        fill_kry_args(c, ka);
+        ka.idx = a.ident; ka.cj = a.cj; ka.tol = kr->tol; ka.skip = a.skipI;
+        ka.newton = 1;
+        ka.nli = c->kry_rint; ka.flag = c->kry_rint + batch; ka.resnorm = c->kry_rres; ka.nrm = a.nrm_out;
+    }
     for (int m = 1; m <= idactl::MAXNLSIT; ++m) {
         {
             KTimer kt(c, IDAHIP_K_NEWTON_ITER, 0);
-            if (!launch_krylov_fused<true>(c, ka, batch)) return fail(c, -2, "no fused Krylov kernel for problem kind %d", (int)c->kind);
-            if ((rc = post_launch(c, "krylov_fused (round)"))) return rc;
+            if (kr) {
+                if (!launch_krylov_fused<true>(c, ka, batch)) return fail(c, -2, "no fused Krylov kernel for problem kind %d", (int)c->kind);
+                if ((rc = post_launch(c, "krylov_fused (round)"))) return rc;
+            } else if ((rc = launch_newton_iter(c, a.ident, a.scale, a.nrm_out, a.skipI, batch))) {
+                return rc;
+            }
         }
-        hipLaunchKernelGGL(round_krylov_ctl_kernel, per_sys, blk, 0, c->stream, a, kr, m);
+        ctl(m);
         if (m < idactl::MAXNLSIT) {
             KTimer kt(c, IDAHIP_K_SYS, 0);
             sa.reset_ee = 0; sa.skip = a.skipS;
@@ -2545,8 +2625,7 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
         if (int rc = refuse_krylov(c, "idahip_round_solve")) return rc;
     DevGuard dev_guard__(c);
     if (!c) return -1;
-    if (!hSys || !call || !hRoundsDone || !hAcc || !rounds_run || !call->touts || call->ntout < 1) return null_argument(c);
-    if (sys_bytes != sizeof(idactl::SysCore)) return fail(c, -2, "controller state of %zu bytes, this library expects %zu", sys_bytes, sizeof(idactl::SysCore));
+    if (int rca = stepper_call_args(c, hSys, sys_bytes, call, hRoundsDone, hAcc, rounds_run)) return rca;
     if (int rcu = ma_unset(c, "idahip_round_solve")) return rcu;
     const KindFacts& facts = kind_facts(c->kind);
     const bool lin = c->kind == IDAHIP_LINEAR_DENSE && facts.rounds && c->n <= LU_BIG_MAX_N;
@@ -2558,12 +2637,8 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     if (!kry && (c->n <= TINY_N || !(lin || banded || network) || c->lu_variant < 4))
         return fail(c, -2, "the device-resident lock-step stepper takes linear dense, heat, Brusselator and mass-action problems with %d < n <= %d (LU variant 4)", TINY_N, LU_BIG_MAX_N);
     if (!c->h_constr.empty()) return fail(c, -2, "the device lock-step stepper does not check constraints: the host stepper does (DESIGN.md section 4g)");
-    if (const int rcm = missing_id(c, "idahip_round_solve")) return rcm;
-    if (call->recycle && (!c->ic_y || !c->ic_yp)) return fail(c, -2, "recycle needs idahip_snapshot_initial");
-    if (call->recycle && call->max_rounds < 1) return fail(c, -2, "recycle needs a round limit");
     const int batch = c->batch, n = c->n;
-    const long nn = (long)n * n;
-    int rc = stepper_buffers(c, call, hYout || hYPout);
+    int rc = stepper_call_begin(c, "idahip_round_solve", hSys, call, hYout || hYPout);
     if (rc) return rc;
     if (!c->rnd_i) rc |= dalloc(c, &c->rnd_i, (size_t)8 * batch + 8 + 2 * IDAHIP_K_COUNT);
     if (!c->rnd_d) rc |= dalloc(c, &c->rnd_d, (size_t)4 * batch);
@@ -2572,12 +2647,6 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     // whether any system of the call has a stop time: the kernels without it are the ones that ran before there was one
     bool tstop = false;
     for (int b = 0; b < batch; ++b) tstop = tstop || static_cast<const idactl::SysCore*>(hSys)[b].tstopset;
-    const size_t ysz = (size_t)call->ntout * batch * n;
-    IDAHIP_HIP(c, hipMemcpyAsync(c->tiny_sys, hSys, (size_t)batch * sizeof(idactl::SysCore), hipMemcpyHostToDevice, c->stream));
-    IDAHIP_HIP(c, hipMemcpyAsync(c->tiny_touts, call->touts, sizeof(double) * call->ntout, hipMemcpyHostToDevice, c->stream));
-    if (call->start_round)
-        IDAHIP_HIP(c, hipMemcpyAsync(c->tiny_start, call->start_round, sizeof(int64_t) * batch, hipMemcpyHostToDevice, c->stream));
-    IDAHIP_HIP(c, hipMemsetAsync(c->tiny_acc, 0, 2 * sizeof(uint64_t), c->stream));
     RoundArgs a;
     a.f = flow_args(c, call);
     a.sys = (idactl::SysCore*)c->tiny_sys;
@@ -2588,7 +2657,6 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     a.round_base = call->round_base;
     a.fused_jac = (c->kind == IDAHIP_LINEAR_DENSE && !c->jac_dq && !kry) ? 1 : 0;
     a.jac_in_lu = (a.fused_jac && jac_in_lu_on(c, false)) ? 1 : 0;
-    const LuJac jq{c->A, c->B, c->rnd_d + batch, 1};  // (cj by system id: RoundArgs::cj)
     if ((c->jac_dq || (kry && c->kry_prec)) && !c->dq_hh && (rc = dalloc(c, &c->dq_hh, (size_t)batch))) return rc;
     a.lu_period = kry ? 1 : c->lu_period;  // (a psetup is one band launch: nothing to amortise)
     KryRoundArgs kr{};
@@ -2621,7 +2689,6 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     hipLaunchKernelGGL(round_init_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a);
     IDAHIP_HIP(c, hipMemsetAsync(a.summary, 0, 2 * sizeof(int), c->stream));
     const size_t shm_wg = sizeof(double) * (4 * (size_t)n + 8);
-    const size_t shm_it = 2 * sizeof(double) * n;
     SysArgs sa;
     fill_sys_args(c, sa, 1);
     sa.idx = a.ident; sa.tn = a.tn; sa.cj = a.cj;
@@ -2638,72 +2705,17 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
             // (a Krylov ctx without the preconditioner factors nothing: no list)
             if (!kry || c->kry_prec) hipLaunchKernelGGL(round_lists_kernel, dim3(1), dim3(1024), 0, c->stream, a);
         }
-        if (kry) {
-            if ((rc = krylov_round_newton(c, a, kr, sa))) return rc;
-        } else {
-            // n > 1024 (config 4): a factorisation is ~640 launches, most of them one workgroup per matrix, and a third of a small
-            // batch needs one in any round -- launches sized for the whole batch cost more than they do at n = 512 (11.4 against
-            // 12.3 k iters/s in round 4). The list's length comes back to the host (4 bytes, behind the residual kernels enqueued
-            // below: the copy's round trip is hidden) and the LU's launches are sized by it, as the host stepper's are.
-            const bool lu_cnt_on_host = n > LU_MAX_N && !c->band;  // (the band LU is one launch: its surplus lanes leave on reading the count)
-            if (lu_cnt_on_host) {
-                IDAHIP_HIP(c, hipMemcpyAsync(c->rnd_host + 2, a.lu_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-                IDAHIP_HIP(c, hipEventRecord(c->ev_cnt, c->stream));
-            }
-            {   // sys(y0), y <- y0 = 0 (newton.rs:73): without and with the Jacobian (J = B + cj A falls out of the same sweep)
-                KTimer kt(c, IDAHIP_K_SYS, 0);
-                sa.reset_ee = 1; sa.skip = a.skipP;
-                if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
-            }
-            if (a.jac_in_lu) {  // the plain sweep for the systems that set up: the factorisation forms J from A and B itself
-                KTimer kt(c, IDAHIP_K_SYS, 0);
-                sa.skip = a.skipL;
-                if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
-            } else if (a.fused_jac) {
-                KTimer kt(c, IDAHIP_K_SYS_JAC, 0);
-                sa.skip = a.skipL;
-                if ((rc = launch_sys(c, sa, batch, c->jw))) return rc;
-            } else {  // no fused residual + Jacobian kernel for this problem: the residual, then the Jacobian of the same systems
-                {
-                    KTimer kt(c, IDAHIP_K_SYS, 0);
-                    sa.skip = a.skipL;
-                    if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
-                }
-                KTimer kt(c, IDAHIP_K_JAC, 0);
-                if (c->jac_dq)  // the systems' hh from their records, and their nre_dq
-                    hipLaunchKernelGGL(dq_round_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a.sys, (const int*)a.skipL, c->dq_hh,
-                                       batch, dq_evals(c));
-                if ((rc = launch_jac(c, c->jw, a.ident, a.cj, batch, nullptr, nullptr, nullptr, a.skipL, c->dq_hh))) return rc;
-            }
-            {
-                int nlu = batch;
-                const int* d_cnt = a.lu_cnt;
-                if (lu_cnt_on_host) {
-                    IDAHIP_HIP(c, hipEventSynchronize(c->ev_cnt));
-                    nlu = c->rnd_host[2];
-                    d_cnt = nullptr;
-                    if (nlu < 0 || nlu > batch) return fail(c, -4, "list length %d outside 0..%d", nlu, batch);
-                }
-                KTimer kt(c, IDAHIP_K_LU, 0);
-                if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, a.lu_list, nlu, d_cnt);
-                else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt, a.jac_in_lu ? &jq : nullptr);
-                if (rc) return rc;
-                if ((rc = post_launch(c, "lu"))) return rc;
-            }
-            hipLaunchKernelGGL(round_newton_ctl_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a, 0);
-            for (int m = 1; m <= idactl::MAXNLSIT; ++m) {
-                {
-                    KTimer kt(c, IDAHIP_K_NEWTON_ITER, 0);
-                    if ((rc = launch_newton_iter(c, a.ident, a.scale, a.nrm_out, a.skipI, batch))) return rc;
-                }
-                hipLaunchKernelGGL(round_newton_ctl_kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, a, m);
-                if (m < idactl::MAXNLSIT) {
-                    KTimer kt(c, IDAHIP_K_SYS, 0);
-                    sa.reset_ee = 0; sa.skip = a.skipS;
-                    if ((rc = launch_sys(c, sa, batch, nullptr))) return rc;
-                }
-            }
+        // n > 1024 (config 4): a factorisation is ~640 launches, most of them one workgroup per matrix, and a third of a small
+        // batch needs one in any round -- launches sized for the whole batch cost more than they do at n = 512 (11.4 against
+        // 12.3 k iters/s in round 4). The list's length comes back to the host (4 bytes, behind the residual kernels enqueued
+        // next: the copy's round trip is hidden) and the LU's launches are sized by it, as the host stepper's are.
+        const bool lu_cnt_on_host = !kry && n > LU_MAX_N && !c->band;  // (the band LU is one launch: its surplus lanes leave on reading the count)
+        if (lu_cnt_on_host) {
+            IDAHIP_HIP(c, hipMemcpyAsync(c->rnd_host + 2, a.lu_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            IDAHIP_HIP(c, hipEventRecord(c->ev_cnt, c->stream));
         }
+        rc = round_newton(c, a, kry ? &kr : nullptr, sa, lu_cnt_on_host);
+        if (rc) return rc;
         IDAHIP_HIP(c, hipMemsetAsync(a.summary, 0, sizeof(int), c->stream));
         {
             KTimer kt(c, IDAHIP_K_VECTOR, 0);
@@ -2721,15 +2733,8 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
             }
         }
     }
-    (void)shm_it;
     *rounds_run = r;
-    IDAHIP_HIP(c, hipMemcpyAsync(hSys, c->tiny_sys, (size_t)batch * sizeof(idactl::SysCore), hipMemcpyDeviceToHost, c->stream));
-    if (call->nroots > 0)
-        IDAHIP_HIP(c, hipMemcpyAsync(call->root_states, c->tiny_roots, (size_t)batch * sizeof(idahip_root_state), hipMemcpyDeviceToHost, c->stream));
-    IDAHIP_HIP(c, hipMemcpyAsync(hRoundsDone, c->tiny_rounds, sizeof(int64_t) * batch, hipMemcpyDeviceToHost, c->stream));
-    IDAHIP_HIP(c, hipMemcpyAsync(hAcc, c->tiny_acc, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (hYout) IDAHIP_HIP(c, hipMemcpyAsync(hYout, c->tiny_yout, sizeof(double) * ysz, hipMemcpyDeviceToHost, c->stream));
-    if (hYPout) IDAHIP_HIP(c, hipMemcpyAsync(hYPout, c->tiny_ypout, sizeof(double) * ysz, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stepper_call_end(c, hSys, call, hRoundsDone, hAcc, hYout, hYPout))) return rc;
     unsigned long long hstats[IDAHIP_K_COUNT];
     IDAHIP_HIP(c, hipMemcpyAsync(hstats, a.stats, sizeof hstats, hipMemcpyDeviceToHost, c->stream));
     std::vector<int64_t> kcnt;

@@ -8,7 +8,7 @@
 //   round_lists_kernel   one workgroup: the list of systems whose Newton solve starts with a linear setup (+ its length)
 //   sys / sys+jac        the residual kernels of problem_kernels.hpp over the whole batch, each system skipped by one of them
 //   lu_factor_batched    on the device-built list (launches sized for the worst case; surplus workgroups leave at once)
-//   4 x { newton_iter_kernel ; round_newton_ctl_kernel (idaNlsConvTest and Newton's bookkeeping, thread / system) ; sys }
+//   4 x { newton_iter_kernel ; round_ctl_kernel<false> (idaNlsConvTest and Newton's bookkeeping, thread / system) ; sys }
 //   round_end_kernel     workgroup / system: final yy/yp + error-test norms, test_error / handle_n_flag / complete_step,
 //                        stop tests, interpolation to tout, the next tout of the schedule, Ida::new again when streaming
 // The control flow is ida_flow.hpp's (shared with the one-thread-per-system stepper), the decisions ida_controller.hpp's
@@ -19,7 +19,7 @@
 // A Krylov ctx with idahip_set_krylov_rounds on runs the same round with the linear algebra replaced:
 //   round_begin_kernel ; (preconditioner: round_lists_kernel) ; sys ; sys of the systems that set up
 //   preconditioner:      dq_round_prep_kernel ; band DQ Jacobian into kry_pab ; band getrf on the device-built list
-//   4 x { krylov_fused_kernel<.., ROUND> ; round_krylov_ctl_kernel ; sys }   (phase 0 of the control kernel before the first pass)
+//   4 x { krylov_fused_kernel<.., ROUND> ; round_ctl_kernel<true> ; sys }   (phase 0 of the control kernel before the first pass)
 //   round_end_kernel
 #pragma once
 #include "ida_flow.hpp"
@@ -285,80 +285,8 @@ __global__ __launch_bounds__(1024) void round_lists_kernel(RoundArgs a) {
     }
 }
 
-// ---- what follows a convergence test (newton.rs:109-153): converged / iterate again / ConvergenceRecover. true = sys(y), then the
-// next iteration pass
-__device__ __forceinline__ bool round_after_ctest(const RoundArgs& a, idactl::SysCore& s, int b, int ret, bool converged) {
-    if (ret == idactl::NLS_SUCCESS && converged) {
-        s.jcur = false;
-        s.nls_ret = idactl::NLS_SUCCESS;
-        a.skipI[b] = 1;
-        return false;
-    }
-    if (ret == idactl::NLS_SUCCESS) {
-        s.curiter += 1;
-        if (s.curiter >= idactl::MAXNLSIT) ret = idactl::NLS_CONV_RECVR;
-    }
-    if (ret == idactl::NLS_SUCCESS) {
-        a.skipS[b] = 0;  // sys(y), then iterate again
-        s.nre += 1;
-        return true;
-    }
-    s.nconvfails += 1;  // ConvergenceRecover
-    a.skipI[b] = 1;
-    if (!s.jcur) {
-        s.call_lsetup = true;
-        s.newton_retry = true;  // sys(y0) + setup + iterations again: in the next round
-    } else {
-        s.nls_ret = idactl::NLS_CONV_RECVR;
-    }
-    return false;
-}
-
-// ---- Newton's bookkeeping between the batched kernels (newton.rs:73-153, ida_nls.rs:168-179, 218-266); one thread per system.
-// phase 0: after the residual (and setup) kernels; phase 1..4: after the m-th newton_iter_kernel of the round
-__global__ void round_newton_ctl_kernel(RoundArgs a, int phase) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool mine = b < a.f.batch && a.in_newton[b] && (phase == 0 || a.skipI[b] == 0);
-    // counters of the per-class statistics: one atomic per wavefront, not one per system
-    const unsigned long long m_iter = __ballot(mine && phase != 0);
-    if (m_iter != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&a.stats[IDAHIP_K_NEWTON_ITER], (unsigned long long)__popcll(m_iter));
-    bool again = false;
-    if (mine) {
-        idactl::SysCore& s = a.sys[b];  // in place: the few fields this step touches, not the 752-byte record both ways
-        const int n = a.v.n;
-        if (phase == 0) {
-            s.nre += 1;  // sys(y0)
-            bool go = true;
-            if (a.skipL[b] == 0) {
-                idactl::after_lsetup(s, a.lu_info[b]);
-                if (s.nls_ret == idactl::NLS_LSETUP_RECVR) {
-                    s.nconvfails += 1;  // jcur is true: no retry (newton.rs:146-153 with Q3)
-                    go = false;
-                }
-            }
-            if (go) {
-                s.curiter = 0;
-                a.skipI[b] = 0;
-                a.scale[b] = idactl::after_lsolve(s, IDAHIP_LS_DIRECT /* = idahip_ls_type(): the only LSolver of this library */, 0, false) ? 2.0 / (1.0 + s.cjratio) : 1.0;  // ida_ls.rs:387-418
-            }
-        } else {
-            a.skipS[b] = 1;
-            const double delnrm = sqrt(a.nrm_out[b] / (double)n);
-            s.niters += 1;
-            bool converged = false;
-            const int ret = idactl::conv_test(s, delnrm, &converged);
-            again = round_after_ctest(a, s, b, ret, converged);
-        }
-    }
-    const unsigned long long m_sys = __ballot(again);
-    if (m_sys != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&a.stats[IDAHIP_K_SYS], (unsigned long long)__popcll(m_sys));
-}
-
-// ---- the same bookkeeping on a Krylov ctx (idahip_set_krylov_rounds; krylov_kernels.hpp): the linear setup forms
-// nothing (after_lsetup_nojac) or is the band preconditioner's psetup, whose Jacobian and factorisation the round has launched on
-// the list; the iteration is krylov_fused_kernel<.., ROUND>, whose tolerance is formed here from the record. The order per system
-// is the host stepper's (ensemble_ida.cpp, newton_solve_batched). npe / nps and the ready flags live in arrays of their own: the
-// record's size is the one-thread stepper's LDS footprint per system.
+// ---- what a Krylov ctx adds to the control kernel's arguments (idahip_set_krylov_rounds; krylov_kernels.hpp).
+// npe / nps and the ready flags live in arrays of their own: the record's size is the one-thread stepper's LDS footprint per system.
 struct KryRoundArgs {
     int prec;            // the ctx has the band preconditioner on
     const int* nli;      // [batch] linear iterations / flag of the pass's solve
@@ -368,52 +296,80 @@ struct KryRoundArgs {
     long long* nps;
     long long* ready;    // [batch] nonzero: the system had a psetup in this call
 };
+struct NoKryArgs {};  // the direct instantiation takes none of them
+template <bool KRYLOV>
+using CtlKryArgs = std::conditional_t<KRYLOV, KryRoundArgs, NoKryArgs>;
 
-__global__ void round_krylov_ctl_kernel(RoundArgs a, KryRoundArgs k, int phase) {
+// ---- Newton's bookkeeping between the batched kernels (ida_nls.rs:168-179, 218-266); one thread per system. The flow is
+// ida_controller.hpp's (newton_begin / newton_after_ctest); this kernel maps its outcomes onto the round's skip flags: iterate =
+// skipS cleared (sys(y), then the next pass), restart = newton_retry (sys(y0) + setup + iterations again: in the next round), done
+// or restart = skipI set. phase 0: after the residual (and setup) kernels; phase 1..4: after the m-th iteration kernel of the round.
+// KRYLOV: the linear setup forms nothing (after_lsetup_nojac) or is the band preconditioner's psetup, whose Jacobian and
+// factorisation the round has launched on the list; the iteration is krylov_fused_kernel<.., ROUND>, whose tolerance is formed here
+// from the record. The order per system is the host stepper's (ensemble_ida.cpp, newton_solve_batched).
+template <bool KRYLOV>
+__global__ void round_ctl_kernel(RoundArgs a, CtlKryArgs<KRYLOV> k, int phase) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     const bool mine = b < a.f.batch && a.in_newton[b] && (phase == 0 || a.skipI[b] == 0);
+    // counters of the per-class statistics: one atomic per wavefront, not one per system
     const unsigned long long m_iter = __ballot(mine && phase != 0);
     if (m_iter != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&a.stats[IDAHIP_K_NEWTON_ITER], (unsigned long long)__popcll(m_iter));
-    // without the preconditioner no list is built: the residuals of the systems that set up are counted here (the others: round_begin_kernel)
-    bool again = mine && phase == 0 && !k.prec && a.skipL[b] == 0;
+    bool again = false;
+    // a Krylov ctx without the preconditioner builds no list: the residuals of the systems that set up are counted here (the others: round_begin_kernel)
+    if constexpr (KRYLOV) again = mine && phase == 0 && !k.prec && a.skipL[b] == 0;
     if (mine) {
-        idactl::SysCore& s = a.sys[b];
+        idactl::SysCore& s = a.sys[b];  // in place: the few fields this step touches, not the 752-byte record both ways
         const int n = a.v.n;
         if (phase == 0) {
             s.nre += 1;  // sys(y0)
-            bool go = true;
-            if (a.skipL[b] == 0) {
-                if (s.nsetups == 0) {  // the system's first setup (a system idaens_stream has created anew included)
-                    k.npe[b] = 0;
-                    k.nps[b] = 0;
-                }
-                idactl::after_lsetup_nojac(s);
-                if (k.prec) {  // (nre_dq: dq_round_prep_kernel)
-                    if (a.lu_info[b] != 0) s.nls_ret = idactl::NLS_LSETUP_RECVR;
-                    k.npe[b] += 1;
-                    k.ready[b] = 1;
-                }
-                if (s.nls_ret == idactl::NLS_LSETUP_RECVR) {
-                    s.nconvfails += 1;  // jcur is true: no retry
-                    go = false;
+            const bool setup = a.skipL[b] == 0;
+            if (setup) {
+                if constexpr (KRYLOV) {
+                    if (s.nsetups == 0) {  // the system's first setup (a system idaens_stream has created anew included)
+                        k.npe[b] = 0;
+                        k.nps[b] = 0;
+                    }
+                    idactl::after_lsetup_nojac(s);
+                    if (k.prec) {  // (nre_dq: dq_round_prep_kernel)
+                        if (a.lu_info[b] != 0) s.nls_ret = idactl::NLS_LSETUP_RECVR;
+                        k.npe[b] += 1;
+                        k.ready[b] = 1;
+                    }
+                } else {
+                    idactl::after_lsetup(s, a.lu_info[b]);
                 }
             }
-            if (go) {
-                s.curiter = 0;
+            if (idactl::newton_begin(s, setup)) {
                 a.skipI[b] = 0;
-                k.tol[b] = idakry::tolerance(n, s.eps_newt);
+                // a Krylov ctx does not scale the correction: the host passes the same array as a.scale and as k.tol, the solver's tolerance
+                if constexpr (KRYLOV) k.tol[b] = idakry::tolerance(n, s.eps_newt);
+                else a.scale[b] = idactl::after_lsolve(s, IDAHIP_LS_DIRECT /* = idahip_ls_type(): the only LSolver of this library */, 0, false) ? 2.0 / (1.0 + s.cjratio) : 1.0;  // ida_ls.rs:387-418
             }
         } else {
             a.skipS[b] = 1;
-            const int nli = k.nli[b], flag = k.flag[b];
-            s.niters += 1;
-            (void)idactl::after_lsolve(s, IDAHIP_LS_ITERATIVE, nli, flag != 0);  // the correction is not scaled
-            s.nre_dq += nli;
-            if (k.prec) k.nps[b] += 1 + nli;
             bool converged = false;
-            int ret = idactl::NLS_CONV_RECVR;  // every flag other than SUCCESS: ConvergenceRecover, no convergence test
-            if (flag == idakry::SUCCESS) ret = idactl::conv_test(s, sqrt(a.nrm_out[b] / (double)n), &converged);
-            again = round_after_ctest(a, s, b, ret, converged);
+            int ret = idactl::NLS_CONV_RECVR;  // a Krylov solve's every flag other than SUCCESS: ConvergenceRecover, no convergence test
+            if constexpr (KRYLOV) {
+                const int nli = k.nli[b], flag = k.flag[b];
+                s.niters += 1;
+                (void)idactl::after_lsolve(s, IDAHIP_LS_ITERATIVE, nli, flag != 0);  // the correction is not scaled
+                s.nre_dq += nli;
+                if (k.prec) k.nps[b] += 1 + nli;
+                if (flag == idakry::SUCCESS) ret = idactl::conv_test(s, sqrt(a.nrm_out[b] / (double)n), &converged);
+            } else {
+                const double delnrm = sqrt(a.nrm_out[b] / (double)n);
+                s.niters += 1;
+                ret = idactl::conv_test(s, delnrm, &converged);
+            }
+            const idactl::NewtonNext next = idactl::newton_after_ctest(s, ret, converged);
+            again = next == idactl::NEWTON_ITERATE;
+            if (again) {
+                a.skipS[b] = 0;  // sys(y), then iterate again
+                s.nre += 1;
+            } else {
+                a.skipI[b] = 1;
+                if (next == idactl::NEWTON_RESTART) s.newton_retry = true;
+            }
         }
     }
     const unsigned long long m_sys = __ballot(again);

@@ -14,6 +14,7 @@
 // different systems overlap the short serial diagonal phases with each other's streaming.
 #pragma once
 #include "common.hpp"
+#include "../host/ida_controller.hpp"
 
 namespace idahip {
 
@@ -458,38 +459,29 @@ __device__ __forceinline__ double ic_tiny_solve(const double* __restrict__ LU, c
 
 
 // ------------------------------------------------------------------------------------------------ idaNlsConvTest on the device
-// The first two convergence tests of a Newton solve (src/ida_nls.rs:243-262) need no pow: m = 0 is two comparisons, m = 1 has
+// The first two convergence tests of a Newton solve are the controller's conv_test_core<M> (host/ida_controller.hpp) with the
+// iteration M = 0 or 1 fixed at compile time, so no pow is compiled in: m = 0 is two comparisons, m = 1 has
 // rate = (delnrm / oldnrm)^(1/1) = delnrm / oldnrm exactly. sum[q] is the kernel's sequential sum of (delta_i ewt_i)^2;
 // delnrm = sqrt(sum / n) -- a correctly rounded division and square root, as on the host (norm_rms.rs:36-37).
 // conv[q]: 0 = keep iterating, 1 = converged at m = 0, 2 = converged at m = 1, 3 = ConvergenceRecover at m = 1 (rate > 0.9).
-__global__ void ctest_kernel(const double* __restrict__ sum, int n, int m, const double* __restrict__ toldel, const double* __restrict__ ss,
+// ss[q] is the ss of the previous solve / setup; the host replays both tests over delnrm to bring its records up to date.
+template <int M>
+__global__ void ctest_kernel(const double* __restrict__ sum, int n, const double* __restrict__ toldel, const double* __restrict__ ss,
                              const double* __restrict__ eps_newt, double* __restrict__ delnrm /*[nsys][2]*/, int* __restrict__ conv,
                              int nsys) {
+    static_assert(M == 0 || M == 1, "the two tests that need no pow");
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nsys) return;
-    if (m == 0) {
-        const double d0 = sqrt(sum[q] / (double)n);
-        delnrm[2 * q] = d0;
-        delnrm[2 * q + 1] = 0.0;
-        int c = 0;
-        if (d0 <= 0.0001 * toldel[q]) c = 1;       // ida_nls.rs:245
-        else if (ss[q] * d0 <= eps_newt[q]) c = 1;  // ida_nls.rs:260 with the ss of the previous solve / setup
-        conv[q] = c;
-    } else {
-        if (conv[q] != 0) return;
-        const double d0 = delnrm[2 * q];
-        const double d1 = sqrt(sum[q] / (double)n);
-        delnrm[2 * q + 1] = d1;
-        const double rate = d1 / d0;               // powf(base, 1/m) with m = 1 (ida_nls.rs:249-253)
-        int c = 0;
-        if (rate > 0.9) {                          // RATEMAX (ida_nls.rs:15,254)
-            c = 3;
-        } else {
-            const double ss1 = rate / (1.0 - rate);
-            if (ss1 * d1 <= eps_newt[q]) c = 2;
-        }
-        conv[q] = c;
-    }
+    if (M == 1 && conv[q] != 0) return;
+    const double d = sqrt(sum[q] / (double)n);
+    double oldnrm = 0.0;
+    if (M == 0) delnrm[2 * q + 1] = 0.0;
+    else oldnrm = delnrm[2 * q];
+    delnrm[2 * q + M] = d;
+    double ssq = ss[q];
+    bool converged = false;
+    const int ret = idactl::conv_test_core<M>(M, d, toldel[q], eps_newt[q], oldnrm, ssq, &converged);
+    conv[q] = ret != idactl::NLS_SUCCESS ? 3 : converged ? M + 1 : 0;
 }
 
 }  // namespace idahip

@@ -223,46 +223,25 @@ struct TinyNewton {
         }
         return sqrt(acc / (double)n);
     }
+    // the flow is ida_controller.hpp's (newton_begin / newton_after_ctest); here: restart = the loop's first block again, iterate =
+    // sys(y) and the loop's body again, done = return
     __device__ void solve() const {
         bool restart = true;
         for (;;) {
             if (restart) {
                 nls_sys(true);  // sys(y0), y <- y0 = 0 (newton.rs:73)
-                if (s.call_lsetup) {
-                    idactl::after_lsetup(s, lsetup());
-                    if (s.nls_ret == idactl::NLS_LSETUP_RECVR) {
-                        s.nconvfails += 1;  // jcur is true: no retry (newton.rs:146-153 with Q3)
-                        return;
-                    }
-                }
-                s.curiter = 0;
+                if (s.call_lsetup) idactl::after_lsetup(s, lsetup());
+                if (!idactl::newton_begin(s, s.call_lsetup)) return;
                 restart = false;
             }
             const double delnrm = newton_iter();
             s.niters += 1;
             bool converged = false;
-            int ret = idactl::conv_test(s, delnrm, &converged);
-            if (ret == idactl::NLS_SUCCESS && converged) {
-                s.jcur = false;
-                s.nls_ret = idactl::NLS_SUCCESS;
-                return;
-            }
-            if (ret == idactl::NLS_SUCCESS) {
-                s.curiter += 1;
-                if (s.curiter >= idactl::MAXNLSIT) ret = idactl::NLS_CONV_RECVR;
-            }
-            if (ret == idactl::NLS_SUCCESS) {
-                nls_sys(false);  // sys(y), then iterate again
-                continue;
-            }
-            s.nconvfails += 1;  // ConvergenceRecover
-            if (!s.jcur) {
-                s.call_lsetup = true;
-                restart = true;
-                continue;
-            }
-            s.nls_ret = idactl::NLS_CONV_RECVR;
-            return;
+            const int ret = idactl::conv_test(s, delnrm, &converged);
+            const idactl::NewtonNext next = idactl::newton_after_ctest(s, ret, converged);
+            if (next == idactl::NEWTON_DONE) return;
+            if (next == idactl::NEWTON_ITERATE) nls_sys(false);  // sys(y)
+            else restart = true;
         }
     }
 };

@@ -219,9 +219,13 @@ long dq_band_evals(idaens* e) {
 int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
     std::vector<Sys>& S = e->sys;
     std::vector<int32_t> R(act), I, C, L, P;
-    std::vector<uint8_t> jbad(e->batch, 0);
     std::vector<double> tn, cj, hh, sc, nrm;
     std::vector<int32_t> info;
+    // the arguments of a listed device call: tn / cj / hh of the list's systems
+    auto gather = [&](const std::vector<int32_t>& list) {
+        tn.clear(); cj.clear(); hh.clear();
+        for (int b : list) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); hh.push_back(S[b].hh); }
+    };
     while (!R.empty() || !I.empty()) {
         if (!R.empty()) {
             // sys(y0), y <- y0 = 0 (newton.rs:73); the systems whose Newton solve then calls setup (call_lsetup) get both
@@ -234,8 +238,7 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
             const bool kry = idahip_krylov(e->ctx, nullptr) == 1;
             for (int b : R) (S[b].call_lsetup && !dq && !kry ? L : P).push_back(b);
             if (!P.empty()) {
-                tn.clear(); cj.clear();
-                for (int b : P) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); }
+                gather(P);
                 ENS_CALL(e, idahip_nls_sys(e->ctx, tn.data(), cj.data(), 1, P.data(), (int)P.size()));
             }
             for (int b : R) S[b].nre += 1;
@@ -250,8 +253,7 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
                 for (int b : R)
                     if (S[b].call_lsetup) L.push_back(b);
                 if (!L.empty()) {
-                    tn.clear(); cj.clear(); hh.clear();
-                    for (int b : L) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); hh.push_back(S[b].hh); }
+                    gather(L);
                     info.assign(L.size(), 0);
                     ENS_CALL(e, idahip_krylov_psetup(e->ctx, tn.data(), cj.data(), hh.data(), info.data(), L.data(), (int)L.size()));
                     const long evals = std::min<long>((long)pml + pmu + 1, (long)e->n);
@@ -268,8 +270,7 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
                 for (int b : R)
                     if (S[b].call_lsetup) L.push_back(b);
             if (!L.empty() && dq) {
-                tn.clear(); cj.clear(); hh.clear();
-                for (int b : L) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); hh.push_back(S[b].hh); }
+                gather(L);
                 info.assign(L.size(), 0);
                 ENS_CALL(e, idahip_nls_lsetup_dq(e->ctx, tn.data(), cj.data(), hh.data(), info.data(), L.data(), (int)L.size()));
                 const long evals = idahip_band(e->ctx, nullptr, nullptr) > 0 ? dq_band_evals(e) : (long)e->n;
@@ -279,8 +280,7 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
                     after_lsetup(s, info[q]);
                 }
             } else if (!L.empty()) {
-                tn.clear(); cj.clear();
-                for (int b : L) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); }
+                gather(L);
                 info.assign(L.size(), 0);
                 ENS_CALL(e, idahip_nls_sys_setup(e->ctx, tn.data(), cj.data(), 1, info.data(), L.data(), (int)L.size()));
                 for (size_t q = 0; q < L.size(); ++q) {
@@ -288,15 +288,8 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
                     after_lsetup(s, info[q]);  // idaNlsLSetup / idaLsSetup bookkeeping (ida_nls.rs:168-179, ida_ls.rs:250)
                 }
             }
-            for (int b : R) {
-                Sys& s = S[b];
-                if (s.call_lsetup && s.nls_ret == NLS_LSETUP_RECVR) {
-                    s.nconvfails += 1;  // jcur is true: no retry (newton.rs:146-153 with Q3)
-                    continue;
-                }
-                s.curiter = 0;
-                I.push_back(b);
-            }
+            for (int b : R)
+                if (newton_begin(S[b], S[b].call_lsetup)) I.push_back(b);
             R.clear();
         }
         if (I.empty()) break;
@@ -315,32 +308,12 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
             return efail(e, -3, "LSolverType %d: only the direct solvers and the matrix-free SPGMR of a Krylov ctx are implemented", lst);
         }
         C.clear();
-        // what follows a convergence test (newton.rs:109-153): converged / iterate again / ConvergenceRecover
+        // what follows a convergence test is newton_after_ctest's (ida_controller.hpp); here: iterate = list C (sys(y), then the next
+        // pass), restart = list R, done = on no list
         auto after_ctest = [&](int b, int ret, bool converged) {
-            Sys& s = S[b];
-            if (ret == NLS_SUCCESS && converged) {
-                s.jcur = false;
-                s.nls_ret = NLS_SUCCESS;
-                return;
-            }
-            if (ret == NLS_SUCCESS) {
-                s.curiter += 1;
-                if (s.curiter >= MAXNLSIT) ret = NLS_CONV_RECVR;
-            }
-            if (ret == NLS_SUCCESS) {
-                C.push_back(b);  // sys(y) then iterate again
-                return;
-            }
-            // ConvergenceRecover
-            if (!s.jcur) {
-                s.nconvfails += 1;
-                s.call_lsetup = true;
-                jbad[b] = 1;
-                R.push_back(b);
-            } else {
-                s.nconvfails += 1;
-                s.nls_ret = NLS_CONV_RECVR;
-            }
+            const NewtonNext next = newton_after_ctest(S[b], ret, converged);
+            if (next == NEWTON_ITERATE) C.push_back(b);
+            else if (next == NEWTON_RESTART) R.push_back(b);
         };
         bool all_fresh = e->fused_newton && lst == IDAHIP_LS_DIRECT;
         for (int b : I) all_fresh = all_fresh && S[b].curiter == 0;
@@ -349,9 +322,9 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
             // library from eps_newt; the correction is not scaled (ida_ls.rs:405-410); nli / ncfl through after_lsolve; the residual
             // evaluations of the difference quotients (one per linear iteration) go to nre_dq; every flag other than SUCCESS is
             // recoverable and takes Newton's ConvergenceRecover exit (newton.rs:146-153), ee left alone
-            tn.clear(); cj.clear();
+            gather(I);
             std::vector<double> epsv;
-            for (int b : I) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); epsv.push_back(S[b].eps_newt); }
+            for (int b : I) epsv.push_back(S[b].eps_newt);
             nrm.assign(I.size(), 0.0);
             std::vector<int32_t> nli(I.size(), 0), lflag(I.size(), 0);
             const bool prec_on = idahip_krylov_band_prec(e->ctx, nullptr, nullptr) == 1;
@@ -372,14 +345,12 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
                 after_ctest(b, ret, converged);
             }
         } else if (all_fresh) {
-            // the first two iterations in one device call: both convergence tests are decided there (no powf needed for
-            // m <= 1, ida_nls.rs:243-262); the scalar state is brought up to date here from the two norms it returns
-            tn.clear(); cj.clear();
+            // the first two iterations in one device call: both convergence tests are decided there (ctest_kernel<0>, <1>: the same
+            // conv_test_core, no pow for m <= 1); the scalar state is brought up to date here by replaying the two tests, and what
+            // follows them, over the two norms it returns. The device's flags say whether the second iteration ran.
+            gather(I);
             std::vector<double> told, ssv, epsv;
-            for (int b : I) {
-                tn.push_back(S[b].tn); cj.push_back(S[b].cj);
-                told.push_back(S[b].toldel); ssv.push_back(S[b].ss); epsv.push_back(S[b].eps_newt);
-            }
+            for (int b : I) { told.push_back(S[b].toldel); ssv.push_back(S[b].ss); epsv.push_back(S[b].eps_newt); }
             nrm.assign(2 * I.size(), 0.0);
             std::vector<int32_t> conv(I.size(), 0);
             ENS_CALL(e, idahip_newton_iter2(e->ctx, sc.data(), tn.data(), cj.data(), told.data(), ssv.data(), epsv.data(), nrm.data(),
@@ -387,22 +358,16 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
             for (size_t q = 0; q < I.size(); ++q) {
                 const int b = I[q];
                 Sys& s = S[b];
+                bool converged = false;
                 s.niters += 1;
-                s.oldnrm = nrm[2 * q];           // m = 0 (ida_nls.rs:244)
-                if (conv[q] == 1) {
-                    after_ctest(b, NLS_SUCCESS, true);
-                    continue;
-                }
-                s.curiter = 1;                   // the device went on: sys(y), second iteration, test with m = 1
+                int ret = conv_test(s, nrm[2 * q], &converged);  // m = 0: never a failure
+                // the device's flag decides whether the second iteration ran (newton_after_ctest itself, not the lambda: the device
+                // has run this sys(y) already, the system joins no list yet)
+                if (newton_after_ctest(s, ret, conv[q] == 1) != NEWTON_ITERATE) continue;
                 s.nre += 1;
                 s.niters += 1;
-                const double rate = nrm[2 * q + 1] / s.oldnrm;  // powf(base, 1/1)
-                if (conv[q] == 3) {
-                    after_ctest(b, NLS_CONV_RECVR, false);
-                    continue;
-                }
-                s.ss = rate / (1.0 - rate);
-                after_ctest(b, NLS_SUCCESS, conv[q] == 2);
+                ret = conv_test(s, nrm[2 * q + 1], &converged);  // m = 1
+                after_ctest(b, ret, converged);
             }
         } else {
         nrm.assign(I.size(), 0.0);
@@ -417,8 +382,7 @@ int newton_solve_batched(idaens* e, const std::vector<int32_t>& act) {
         }
         }
         if (!C.empty()) {
-            tn.clear(); cj.clear();
-            for (int b : C) { tn.push_back(S[b].tn); cj.push_back(S[b].cj); }
+            gather(C);
             ENS_CALL(e, idahip_nls_sys(e->ctx, tn.data(), cj.data(), 0, C.data(), (int)C.size()));
             for (int b : C) S[b].nre += 1;
         }

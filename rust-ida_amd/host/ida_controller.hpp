@@ -7,6 +7,7 @@
 //   set_coeffs            /root/reference/src/lib.rs:722-782
 //   nonlinear_solve       /root/reference/src/lib.rs:787-812       (lsetup decision, ss resets)
 //   idaNlsConvTest        /root/reference/src/ida_nls.rs:218-266
+//   Newton::solve         /root/reference/crates/nonlinear/src/newton.rs:51-167   (control flow: newton_begin, newton_after_ctest)
 //   test_error            /root/reference/src/lib.rs:967-1039      (decisions; the norms come from the vector code)
 //   restore               /root/reference/src/lib.rs:1044-1083
 //   handle_n_flag         /root/reference/src/lib.rs:1120-1244
@@ -219,24 +220,75 @@ IDA_HD inline bool after_lsolve(SysCore& s, int ls_type, long num_iters, bool fa
     return (ls_type == 0 || ls_type == 2) && s.cjratio != 1.0;
 }
 
-// ---------------------------------------------------------------- idaNlsConvTest (ida_nls.rs:218-266) for iteration m = s.curiter
-// returns NLS_SUCCESS (with *converged) or NLS_CONV_RECVR
-IDA_HD inline int conv_test(SysCore& s, double delnrm, bool* converged) {
-    const int m = s.curiter;
+// ---------------------------------------------------------------- idaNlsConvTest (ida_nls.rs:218-266)
+// The test over the scalars it reads and writes, for iteration m; returns NLS_SUCCESS (with *converged) or NLS_CONV_RECVR. (toldel and
+// eps_newt by reference: each is read on the path that needs it, not ahead of the test.)
+// M >= 0 fixes the iteration at compile time (ctest_kernel<0>, <1>: no pow is compiled in): with M = 1 the rate is the base itself,
+// which is what pow(b, 1.0) returns bit for bit (tests/native/newton_check.cpp).
+template <int M = -1>
+IDA_HD inline int conv_test_core(int m_rt, double delnrm, const double& toldel, const double& eps_newt, double& oldnrm, double& ss, bool* converged) {
+    const int m = M >= 0 ? M : m_rt;
     *converged = false;
     int ret = NLS_SUCCESS;
     if (m == 0) {
-        s.oldnrm = delnrm;
-        if (delnrm <= 0.0001 * s.toldel) *converged = true;
+        oldnrm = delnrm;
+        if (delnrm <= 0.0001 * toldel) *converged = true;
     } else {
-        const double base = delnrm / s.oldnrm;
-        const double arg = 1.0 / (double)m;
-        const double rate = IDA_POW(base, arg);
+        const double base = delnrm / oldnrm;
+        double rate = base;
+        if (M != 1) {
+            const double arg = 1.0 / (double)m;
+            rate = IDA_POW(base, arg);
+        }
         if (rate > RATEMAX) ret = NLS_CONV_RECVR;
-        else s.ss = rate / (1.0 - rate);
+        else ss = rate / (1.0 - rate);
     }
-    if (ret == NLS_SUCCESS && !*converged && s.ss * delnrm <= s.eps_newt) *converged = true;
+    if (ret == NLS_SUCCESS && !*converged && ss * delnrm <= eps_newt) *converged = true;
     return ret;
+}
+// for iteration m = s.curiter of the system's Newton solve
+IDA_HD inline int conv_test(SysCore& s, double delnrm, bool* converged) {
+    return conv_test_core(s.curiter, delnrm, s.toldel, s.eps_newt, s.oldnrm, s.ss, converged);
+}
+
+// ---------------------------------------------------------------- Newton::solve's control flow (crates/nonlinear/src/newton.rs:51-167)
+// The steppers differ in how they run sys / setup / solve (lists of systems, skip flags of a lock-step round, one thread); what
+// happens between those calls is decided here. One rule for the counters of the calls themselves: the caller books nre where it runs
+// a residual and niters where it runs a linear solve.
+enum NewtonNext { NEWTON_DONE,      // s.nls_ret holds the solve's result
+                  NEWTON_ITERATE,   // sys(y), then the next iteration
+                  NEWTON_RESTART }; // stale Jacobian: call_lsetup is set; sys(y0), setup, iterate again
+// after sys(y0) and, where s.call_lsetup, the linear setup (newton.rs:73-92); setup_ran: after_lsetup / after_lsetup_nojac (and
+// a failed psetup) have set nls_ret. false = the setup failed, and with jcur true there is no retry (newton.rs:146-153 with Q3);
+// true = iterate
+IDA_HD inline bool newton_begin(SysCore& s, bool setup_ran) {
+    if (setup_ran && s.nls_ret == NLS_LSETUP_RECVR) {
+        s.nconvfails += 1;
+        return false;
+    }
+    s.curiter = 0;
+    return true;
+}
+// what follows a linear solve and its convergence test (newton.rs:96-153): ret is conv_test's, or NLS_CONV_RECVR where the
+// linear solve failed and no test was made
+IDA_HD inline NewtonNext newton_after_ctest(SysCore& s, int ret, bool converged) {
+    if (ret == NLS_SUCCESS && converged) {
+        s.jcur = false;
+        s.nls_ret = NLS_SUCCESS;
+        return NEWTON_DONE;
+    }
+    if (ret == NLS_SUCCESS) {
+        s.curiter += 1;
+        if (s.curiter >= MAXNLSIT) ret = NLS_CONV_RECVR;
+    }
+    if (ret == NLS_SUCCESS) return NEWTON_ITERATE;
+    s.nconvfails += 1;  // ConvergenceRecover
+    if (!s.jcur) {
+        s.call_lsetup = true;
+        return NEWTON_RESTART;
+    }
+    s.nls_ret = NLS_CONV_RECVR;  // Q3: a current Jacobian, no retry
+    return NEWTON_DONE;
 }
 
 // ---------------------------------------------------------------- test_error decisions (lib.rs:967-1039)

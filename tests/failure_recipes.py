@@ -89,6 +89,36 @@ def jump_case(name, n, after=None, mxstep=None):
             "after": [float(t) for t in after], "mxstep": mxstep}
 
 
+# repeated jump: Newton's restart with a stale Jacobian (ConvergenceRecover, then a setup and the iterations again; newton.rs:146-152),
+# several times per system. After the three quiet touts A is scaled by 3 and by 1/3 alternately before each of eight further touts 0.05
+# apart: the Jacobian a system holds is that of another A every time. tests/test_gpu_newton_restarts.py runs it at these sizes.
+REPEATED_SIZES = [24, 200]
+REPEATED_TOUTS = [T_JUMP + 0.05 * k for k in range(1, 9)]
+
+
+def repeated_jump_case(n):
+    """linear_dense(n), batch of five: `edits` maps the index of a tout to the edit made before it, for the systems `edited`."""
+    from idahip import problems
+    p = problems.linear_dense(n=n, batch=batch_of(n), procs=1)
+    edits = {len(BEFORE) + k: ("scale", "A", 3.0 if k % 2 == 0 else 1.0 / 3.0) for k in range(len(REPEATED_TOUTS))}
+    return {"name": "A*3, A/3 repeated n=%d" % n, "prob": p, "edited": edited_of(n), "edit": None, "edits": edits, "expect": "restarts",
+            "before": list(BEFORE), "after": list(REPEATED_TOUTS), "mxstep": None}
+
+
+def apply_edits_to_ctx(ctx, case, i, cur):
+    """The edit a repeated-jump case makes before tout i (if any), through idahip_set_linear_dense. cur: {system: (A, B, c)}, the arrays
+    as edited so far -- filled here with copies on first use, edited in place like the oracle's."""
+    edit = case.get("edits", {}).get(i)
+    if edit is None:
+        return
+    p = case["prob"]
+    for s in case["edited"]:
+        if s not in cur:
+            cur[s] = (p["A"][s:s + 1].copy(), p["B"][s:s + 1].copy(), p["c"][s:s + 1].copy())
+        edit_arrays(edit, *cur[s])
+        ctx.set_linear_dense(*cur[s], first=s)
+
+
 def singular_case(n, when, band=None, only=None):
     """One system of the batch (system 1) gets an exactly zero column in A and in B: from the start, or at T_JUMP ("mid").
     band = (ml, mu): band_problems.banded_linear instead of linear_dense, for a band ctx with host callbacks.
@@ -241,6 +271,8 @@ def oracle_reference(case, nthreads=16):
         for i, t in enumerate(touts):
             if i == len(case["before"]) and case["edit"] is not None and s in case["edited"]:
                 apply_to_oracle(o, case["edit"])
+            if i in case.get("edits", {}) and s in case["edited"]:
+                apply_to_oracle(o, case["edits"][i])
             if not dead:
                 st, tret = o.solve(t)
                 rec = (st, tret, o.getv("yy"), o.getv("yp"))

@@ -47,6 +47,20 @@ def test_a_jump_after_thirty_rounds_fails_the_next_step_too(n):
         assert ref["counters"]["nst"][r["sys"]] == r["nst"] and ref["counters"]["netf"][r["sys"]] == r["netf"]
 
 
+@pytest.mark.parametrize("n", F.REPEATED_SIZES)
+def test_the_repeated_jump_restarts_newton_with_a_stale_jacobian_more_than_once(n):
+    """The condition of tests/test_gpu_newton_restarts.py: every edited system takes Newton's restart (ConvergenceRecover with a stale
+    Jacobian: nls_nconvfails counts it, ncfn does not) at least twice, and every system ends with status 0. The oracle gives 5 / 3 / 4
+    restarts at n = 24 and 5 / 4 / 4 at n = 200, no ncfn, in about 190 to 200 steps."""
+    case = F.repeated_jump_case(n)
+    ref = F.oracle_reference(case)
+    c, ed = ref["counters"], case["edited"]
+    restarts = c["nls_nconvfails"] - c["ncfn"]
+    print("restarts", restarts, "ncfn", c["ncfn"], "nst", c["nst"])
+    assert (ref["status"] == 0).all(), ref["status"]
+    assert (restarts[ed] >= 2).all(), restarts
+
+
 @pytest.mark.parametrize("kind,n,tout,expect", F.GPU_FIRST_STEPS + [("heat1d", n, 1.0, "recover") for n, _ in F.BAND_FIRST_STEPS[:1]])
 def test_first_step_recipes_fail_before_the_first_step(kind, n, tout, expect):
     """recover: failures at nst == 0 and the integration goes on to tout; first_terminal: -3 with ten error-test failures at nst == 0."""
