@@ -879,6 +879,53 @@ impl HipEnsemble {
         Ok(status)
     }
 
+    /// `calc_ic` for listed systems that have not taken a step since they were created or reinitialised (after an event): `tout1`
+    /// and the returned status go by list position. Refused when a listed system has started, and for what `calc_ic` refuses.
+    pub fn calc_ic_systems(&mut self, icopt: IcOpt, idx: &[i32], tout1: &[f64]) -> Result<Vec<Status>, Error> {
+        assert_eq!(idx.len(), tout1.len());
+        let code = match icopt {
+            IcOpt::YaYdpInit => sys::IDAENS_YA_YDP_INIT,
+            IcOpt::YInit => sys::IDAENS_Y_INIT,
+        };
+        let mut status = vec![0i32; idx.len()];
+        let rc = unsafe { sys::idaens_calc_ic_systems(self.raw, code, idx.as_ptr(), idx.len() as c_int, tout1.as_ptr(), status.as_mut_ptr()) };
+        if rc < 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(status)
+    }
+
+    /// C IDA's `IDAReInit` for the listed systems: each is a created system again at `t0[q]` with y0 = `yy0[q]`, y0' = `yp0[q]`
+    /// (`yy0`, `yp0`: `idx.len() * n` values by list position). Counters, root state, stop time and a fatal status start over; the
+    /// next `solve` runs the first-call block for these systems alone. Refused: a system inside a round-limited call, a t0 that is
+    /// not finite, an id out of range or listed twice.
+    pub fn reinit(&mut self, idx: &[i32], t0: &[f64], yy0: &[f64], yp0: &[f64]) -> Result<(), Error> {
+        assert_eq!(idx.len(), t0.len());
+        assert_eq!(yy0.len(), idx.len() * self.ctx.n);
+        assert_eq!(yp0.len(), idx.len() * self.ctx.n);
+        let rc = unsafe { sys::idaens_reinit(self.raw, idx.as_ptr(), idx.len() as c_int, t0.as_ptr(), yy0.as_ptr(), yp0.as_ptr()) };
+        if rc != 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(())
+    }
+
+    /// The event path of `reinit`: t0 = the tret each listed system last returned with, the new values = what it reported there
+    /// plus the jump `dy` / `dyp` (`idx.len() * n` values; `None`: that side as it is), added on the device.
+    pub fn reinit_at_return(&mut self, idx: &[i32], dy: Option<&[f64]>, dyp: Option<&[f64]>) -> Result<(), Error> {
+        for v in [dy, dyp].iter().flatten() {
+            assert_eq!(v.len(), idx.len() * self.ctx.n);
+        }
+        let rc = unsafe {
+            sys::idaens_reinit_at_return(self.raw, idx.as_ptr(), idx.len() as c_int, dy.map_or(ptr::null(), |v| v.as_ptr()),
+                                         dyp.map_or(ptr::null(), |v| v.as_ptr()))
+        };
+        if rc != 0 {
+            return Err(Error::Library { code: rc, message: self.last_error() });
+        }
+        Ok(())
+    }
+
     /// Root functions g_i = y[comps[i]] - thresholds[i] (the family of examples/roberts.rs), before the first `solve`.
     pub fn set_roots(&mut self, comps: &[i32], thresholds: &[f64]) -> Result<(), Error> {
         assert_eq!(comps.len(), thresholds.len());

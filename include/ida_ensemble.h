@@ -185,12 +185,40 @@ int idaens_get_stop_time(const idaens* e, double* hTstop /* [batch], NaN where n
  * controller state changes -- the first solve computes its own initial step size. */
 enum { IDAENS_YA_YDP_INIT = 1, IDAENS_Y_INIT = 2 };
 int idaens_calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus /* [batch] */);
+/* The same for listed systems at any point of a run: systems that have not taken a step since idaens_create or idaens_reinit -- after
+ * an event a DAE needs consistent algebraic components and derivatives before it steps on. hTout1 / hStatus: [nsys] by list position;
+ * each system's own t0 is its current t. The per-system machine, its statuses and counters are idaens_calc_ic's; the snapshot rows
+ * and phi[2..5] are renewed for the listed systems only, and no field of another system changes. Refused (-2 with a text naming the
+ * system, nothing changed) when a listed system has started (a step taken, the first-call block run, mid-flight, or a fatal status), for
+ * an id out of range or listed twice, and for what idaens_calc_ic refuses: constraints, a Krylov ctx, suppress_alg. */
+int idaens_calc_ic_systems(idaens* e, int icopt, const int32_t* hIdx, int nsys, const double* hTout1 /* [nsys] */,
+                           int32_t* hStatus /* [nsys] */);
+
+/* C IDA's IDAReInit for the listed systems of a running ensemble: each becomes a created system (Ida::new) at
+ * t0 = hT0[q] with y0 = hYY0[q], y0' = hYP0[q] (host arrays by list position, [nsys] and [nsys][n]). Everything per-system starts over:
+ * the controller record, all counters (IDAENS_C_NBACKTR, _NPE, _NPS included), the root state (as idaens_set_roots leaves it), no stop
+ * time (a restarted system is Ida::new, which has none), and a sticky negative status is gone. The next idaens_solve /
+ * idaens_solve_schedule call runs the first-call block for exactly these systems -- the initial step size from that call's tout, the
+ * constraints check of y0, the root functions at t0 -- on whichever stepper the call runs on; every other system continues as if
+ * the call had not been made. idaens_total_newton_iters keeps the iterations of the discarded integration.
+ * idaens_reinit_at_return is the event path: t0 = the tret the system last returned with, and the new values are what it reported
+ * there (the device's yy / yp, idaens_get_yy) plus the jump hDY / hDYP ([nsys][n]; NULL: that side as it is), one addition per
+ * component on the device -- nothing but the jump crosses to the device.
+ * Refused (-2 with a text naming the first offending system, nothing changed): a listed system inside a round-limited call
+ * (IDAENS_UNFINISHED); a t0 that is not finite; an id out of range or listed twice; for idaens_reinit_at_return a system that has
+ * not returned from a solve call since it was created or reinitialised.
+ * idaens_stream / idaens_stream_group restart systems at the ensemble's t0 = 0: while any system's start time differs from it bit
+ * for bit they are refused (-2 with a text). After a reinit at t0 = 0 they work, and restart from the new values. */
+int idaens_reinit(idaens* e, const int32_t* hIdx, int nsys, const double* hT0 /* [nsys] */, const double* hYY0,
+                  const double* hYP0 /* [nsys][n] */);
+int idaens_reinit_at_return(idaens* e, const int32_t* hIdx, int nsys, const double* hDY, const double* hDYP /* [nsys][n] or NULL */);
 
 /* Ida::solve(tout, &mut tret, itask) for every system (src/impl_solve.rs:69-376). hTret/hStatus: [batch].
  * max_rounds > 0 bounds the number of lock-step attempt rounds (systems still stepping report IDAENS_UNFINISHED and
  * resume on the next call with the same tout). Returns 0, or < 0 on a device/ABI failure.
  * A negative per-system status (an IdaError) is sticky: later solve calls leave that system alone and report the same status
- * again (the reference's Ida::solve can be called again after an error and would try to continue). */
+ * again (the reference's Ida::solve can be called again after an error and would try to continue), until idaens_reinit gives the
+ * system new values: a reinitialised system is a created one, with no status. */
 int idaens_solve(idaens* e, double tout, int itask, double* hTret, int32_t* hStatus, long max_rounds);
 
 /* The same for a whole output schedule: for every system Ida::solve(touts[0]), Ida::solve(touts[1]), ... in IDA_NORMAL

@@ -495,6 +495,15 @@ int idahip_get_dky(idahip_ctx* ctx, const int32_t* hKfirst, const int32_t* hKlas
  * initial conditions were uploaded); idahip_restore_initial puts the listed systems back to it. */
 int idahip_snapshot_initial(idahip_ctx* ctx);
 int idahip_restore_initial(idahip_ctx* ctx, const int32_t* hIdx, int nsys);
+/* Ida::new with new values for the listed systems, in the middle of a run (C IDA's IDAReInit, the vector part; libidaens:
+ * idaens_reinit). add == 0: hYY0 / hYP0 are host arrays [nsys][n] by list position, both required, the new y0 / y0'. add != 0: the
+ * new values are the system's current device yy / yp (what a returned system reported) plus the packed increment, one IEEE
+ * addition per component; either pointer may be NULL and that side is then taken as it is (no + 0.0, a -0.0 stays). For every
+ * listed system phi[0] = yy = y0, phi[1] = yp = y0', phi[2..5] = +0.0, and where idahip_snapshot_initial has been taken the
+ * snapshot's rows follow, so that a later idahip_restore_initial starts from the new values. The ctx's own per-system marks (a
+ * Krylov ctx's npe / nps of the lock-step rounds, the band preconditioner's "has factors") return to a created system's. Systems
+ * not listed are not touched. Every ctx form; no matrix is read or written. The list rules are those of every listed entry point. */
+int idahip_reinit(idahip_ctx* ctx, const int32_t* hIdx, int nsys, const double* hYY0, const double* hYP0, int add);
 
 /* ---- Consistent initial conditions: the device side of C IDA's IDACalcIC (the reference has none) ----
  * The Newton / line-search state machine of DESIGN.md section 4f runs per system on the host (libidaens: idaens_calc_ic); these are

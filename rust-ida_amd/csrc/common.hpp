@@ -104,6 +104,8 @@ struct idahip_ctx {
     std::vector<int64_t> kry_h_npe, kry_h_nps;  // [batch] the systems' npe / nps around idahip_round_solve (idahip_krylov_rounds_put/get_counters)
     double *ic_y = nullptr, *ic_yp = nullptr;  // [batch][n] initial conditions kept for idahip_restore_initial (lazy)
     double* dky = nullptr;                     // [batch][n] result buffer of idahip_get_dky (lazy)
+    double* reinit_stage = nullptr;            // idahip_reinit: the packed y0 rows, then the y0' rows, of one call (lazy, grows)
+    size_t reinit_cap = 0;                     // doubles
     // idahip_set_jac_in_lu: a linear dense ctx with analytic Jacobians forms J = B + cj*A inside the first launches of the factorisation
     // (LuJac, lu_kernels.hpp) instead of in the residual sweep; in effect only where jac_in_lu_on (idahip.hip) says the ctx is eligible.
     // -1 = never set: on in idahip_round_solve where n > 448, off in the list entry points; 0 / 1 = set by the caller, for both

@@ -342,7 +342,7 @@ int idahip_destroy(idahip_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->kry_rcnt, c->kry_rint, c->kry_rres, c->kry_pab, c->kry_ppiv, c->kry_V, c->kry_st, c->kry_stage, c->kry_b, c->kry_x, c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
                     c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->d_constr, c->ic_y,
-                    c->ic_yp, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
+                    c->ic_yp, c->reinit_stage, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d, c->ma_blob};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -2083,6 +2083,39 @@ int idahip_restore_initial(idahip_ctx* c, const int32_t* hIdx, int nsys) {
         hipLaunchKernelGGL(restore_initial_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), (const double*)c->ic_y,
                            (const double*)c->ic_yp, f.idx);
     });
+    return f.done();
+}
+
+int idahip_reinit(idahip_ctx* c, const int32_t* hIdx, int nsys, const double* hYY0, const double* hYP0, int add) {
+    ListCall f(c, hIdx, nsys);
+    if (f.rc) return f.rc;
+    if (!add && !f.args({hYY0, hYP0})) return f.rc;
+    if (!f.stage()) return f.rc;
+    // the packed rows: one copy per array into the ctx's staging buffer, which grows to the largest list seen
+    const size_t rows = (size_t)nsys * c->n;
+    if ((hYY0 || hYP0) && c->reinit_cap < 2 * rows) {
+        IDAHIP_HIP(c, hipStreamSynchronize(c->stream));  // an earlier call's kernel may still read the old buffer
+        if (c->reinit_stage) (void)hipFree(c->reinit_stage);
+        c->reinit_cap = 0;
+        if (int rc = dalloc(c, &c->reinit_stage, 2 * rows)) return rc;
+        c->reinit_cap = 2 * rows;
+    }
+    const double* d_y = hYY0 ? c->reinit_stage : nullptr;
+    const double* d_yp = hYP0 ? c->reinit_stage + rows : nullptr;
+    if (hYY0) IDAHIP_HIP(c, hipMemcpyAsync(c->reinit_stage, hYY0, rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (hYP0) IDAHIP_HIP(c, hipMemcpyAsync(c->reinit_stage + rows, hYP0, rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    f.launch(IDAHIP_K_VECTOR, nsys, "reinit", [&] {
+        hipLaunchKernelGGL(reinit_kernel, dim3(nsys), dim3(256), 0, c->stream, vec_state(c), f.idx, d_y, d_yp, add ? 1 : 0, c->ic_y, c->ic_yp);
+    });
+    if (f.rc) return f.rc;
+    // what a created system starts without and the ctx holds outside the controller record: the lock-step rounds' npe / nps of a
+    // Krylov ctx, and the mark that the band preconditioner has factors for the system
+    for (int s = 0; s < nsys; ++s) {
+        const size_t b = (size_t)hIdx[s];
+        if (b < c->kry_h_npe.size()) c->kry_h_npe[b] = 0;
+        if (b < c->kry_h_nps.size()) c->kry_h_nps[b] = 0;
+        if (b < c->kry_pready.size()) c->kry_pready[b] = 0;
+    }
     return f.done();
 }
 

@@ -162,6 +162,12 @@ __device__ __forceinline__ void el_restore_initial(const VecState& s, long vb, i
     s.yp[vb + i] = yp;
 }
 
+// Ida::new with values of the caller's (idahip_reinit): as above, and the higher columns +0.0 as a created system has them
+__device__ __forceinline__ void el_reinit(const VecState& s, long vb, int i, double y, double yp) {
+    el_restore_initial(s, vb, i, y, yp);
+    for (int j = 2; j < MXORDP1; ++j) el_phi(s, j, vb, i) = 0.0;
+}
+
 // the root finding's yy (ida_flow.hpp)
 __device__ __forceinline__ void el_yy_from_phi01(const VecState& s, long vb, int i, double f) {
     s.yy[vb + i] = el_phi(s, 0, vb, i) + f * el_phi(s, 1, vb, i);

@@ -204,4 +204,32 @@ __global__ __launch_bounds__(256) void restore_initial_kernel(VecState s, const 
     for (int i = threadIdx.x; i < s.n; i += 256) el_restore_initial(s, vb, i, icy[vb + i], icyp[vb + i]);
 }
 
+// Ida::new with new values for the listed systems (idahip_reinit): y0 / yp0 are packed [nsys][n] by list position. add == 0: the
+// values themselves; add != 0: the system's current yy / yp plus the packed row, one addition per component, and a null side is
+// taken as it is (no + 0.0: a -0.0 stays). icy / icyp: the snapshot's rows follow when it has been taken, else null.
+__global__ __launch_bounds__(256) void reinit_kernel(VecState s, const int* __restrict__ idx, const double* __restrict__ y0,
+                                                     const double* __restrict__ yp0, int add, double* __restrict__ icy,
+                                                     double* __restrict__ icyp) {
+    const int b = idx[blockIdx.x];
+    const long vb = (long)b * s.n;
+    const long src = (long)blockIdx.x * s.n;
+    for (int i = threadIdx.x; i < s.n; i += 256) {
+        double y, yp;
+        if (add) {
+            y = s.yy[vb + i];
+            yp = s.yp[vb + i];
+            if (y0) y = y + y0[src + i];
+            if (yp0) yp = yp + yp0[src + i];
+        } else {
+            y = y0[src + i];
+            yp = yp0[src + i];
+        }
+        el_reinit(s, vb, i, y, yp);
+        if (icy) {
+            icy[vb + i] = y;
+            icyp[vb + i] = yp;
+        }
+    }
+}
+
 }  // namespace idahip

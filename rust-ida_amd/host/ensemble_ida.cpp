@@ -68,6 +68,8 @@ struct Sys : SysCore {
     RootVecs rt;
     long nbacktr = 0;  // idaens_calc_ic: line-search backtracks (host-only: SysCore's size is part of the device steppers' ABI)
     long npe = 0, nps = 0;  // band preconditioner of a Krylov ctx: setups and solves (C IDA's npe, nps; host-only as well)
+    double t_start = 0.0;   // the t0 this system was created or last reinitialised at (idaens_reinit); idaens_stream restarts at e->t0
+    bool returned = false;  // a solve call has returned for this system since then: yy / yp on the device hold what it reported
 };
 
 }  // namespace
@@ -832,6 +834,7 @@ int solve_core_device(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, 
         } else {
             hStatus[b] = s.status;
             hTret[b] = s.tret;
+            s.returned = true;
         }
     }
     e->total_rounds += rounds_run >= 0 ? rounds_run : rmax;
@@ -1010,6 +1013,7 @@ int solve_core(idaens* e, SolveCall& C, double* hTret, int32_t* hStatus, long ma
         } else {
             hStatus[b] = s.status;
             hTret[b] = s.tret;
+            s.returned = true;
         }
     }
     e->sched_unfinished = C.ntout > 1 && unfinished;
@@ -1047,6 +1051,10 @@ int idaens_stream(idaens* e, const double* touts, int ntout, long max_rounds, lo
     for (int b = 0; b < e->batch; ++b)
         if (e->sys[b].tstopset)
             return efail(e, -2, "idaens_stream does not combine with a stop time (system %d has one): a restarted system is Ida::new, which has none", b);
+    for (int b = 0; b < e->batch; ++b)
+        if (std::memcmp(&e->sys[b].t_start, &e->t0, sizeof(double)) != 0)
+            return efail(e, -2, "idaens_stream does not combine with a start time of a system's own (system %d was reinitialised at t0 = %.17g): a restarted system starts at %.17g",
+                         b, e->sys[b].t_start, e->t0);
     if (!e->have_ic) return efail(e, -2, "no snapshot of the initial conditions (idaens_create failed to take it)");
     SolveCall C;
     C.touts = touts;
@@ -1101,7 +1109,9 @@ struct State {
 };
 }  // namespace ic
 
-int calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus) {
+// cand: the systems to correct, none of which has taken a step; hTout1 / hStatus go by position in cand. whole: cand is the whole
+// batch (idaens_calc_ic), and the call ends with the batch-wide snapshot and zero upload; otherwise both act on cand's systems only.
+int calc_ic(idaens* e, int icopt, const std::vector<int32_t>& cand, const double* hTout1, int32_t* hStatus, bool whole) {
     using namespace ic;
     std::vector<Sys>& S = e->sys;
     const int batch = e->batch;
@@ -1115,8 +1125,11 @@ int calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus) {
     std::vector<int32_t> info;
 
     // ---- setup (steps 1-8). The distance test is made first, on the host: a call that can do nothing launches nothing
-    for (int b = 0; b < batch; ++b) {
+    std::vector<double> tout1_of(batch, 0.0);
+    for (size_t q = 0; q < cand.size(); ++q) tout1_of[cand[q]] = hTout1[q];
+    for (int b : cand) {
         const double t0 = S[b].tn;
+        const double tout1 = tout1_of[b];
         const double tdist = std::fabs(tout1 - t0);
         // tdist == 0.0 is named on its own, as in the stepper's first call: with t0 == tout1 == 0 the bound is 0 too, and 0 < 0 is false
         if (tdist == 0.0 || tdist < 2.0 * eps * (std::fabs(t0) + std::fabs(tout1))) T[b].status = IDAENS_ILL_INPUT;
@@ -1134,6 +1147,7 @@ int calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus) {
                 continue;
             }
             const double t0 = S[b].tn;
+            const double tout1 = tout1_of[b];
             t.hic = 0.001 * std::fabs(tout1 - t0);
             if (nrm[q] > 0.5 / t.hic) t.hic = 0.5 / nrm[q];
             if (tout1 < t0) t.hic = -t.hic;
@@ -1313,17 +1327,57 @@ int calc_ic(idaens* e, int icopt, double tout1, int32_t* hStatus) {
 
     // ---- a failed system keeps what it was created with; the restarts of idaens_stream begin from the corrected values
     L.clear();
-    bool launched = false;
-    for (int b = 0; b < batch; ++b) {
-        hStatus[b] = T[b].status;
+    std::vector<int32_t> ran;
+    for (size_t q = 0; q < cand.size(); ++q) {
+        const int b = cand[q];
+        hStatus[q] = T[b].status;
         if (T[b].status != 0 && T[b].status != IDAENS_ILL_INPUT) L.push_back(b);
-        launched = launched || T[b].status != IDAENS_ILL_INPUT;
+        if (T[b].status != IDAENS_ILL_INPUT) ran.push_back(b);
     }
     if (!L.empty()) ENS_CALL(e, idahip_restore_initial(e->ctx, L.data(), (int)L.size()));
-    if (launched) {
+    if (!ran.empty() && whole) {
         ENS_CALL(e, idahip_snapshot_initial(e->ctx));
         const std::vector<double> zero((size_t)batch * e->n, 0.0);  // phi[2..4] held the iterate and delnew
         for (int j = 2; j <= 4; ++j) ENS_CALL(e, idahip_upload(e->ctx, (idahip_field)(IDAHIP_F_PHI0 + j), 0, batch, zero.data()));
+    } else if (!ran.empty()) {
+        // the same two actions for these systems alone: their yy / yp equal phi[0] / phi[1] here (idahip_ic_commit and
+        // idahip_restore_initial write both), so a reinit "at the current values" renews their snapshot rows and zeroes phi[2..5]
+        ENS_CALL(e, idahip_reinit(e->ctx, ran.data(), (int)ran.size(), nullptr, nullptr, 1));
+    }
+    return 0;
+}
+
+// the refusals idaens_calc_ic and idaens_calc_ic_systems share, after the argument checks of each
+int calc_ic_refusals(idaens* e, const char* who) {
+    if (idahip_constraints(e->ctx, nullptr) == 1) return efail(e, -2, "%s: a ctx with constraints is not supported (idahip_set_constraints)", who);
+    if (idahip_krylov(e->ctx, nullptr) == 1) return efail(e, -2, "%s: a Krylov ctx is not supported (idahip_create_krylov)", who);
+    if (idahip_suppress_alg(e->ctx) == 1)
+        return efail(e, -2, "%s: not with suppress_alg on (set_id, calc_ic, idahip_set_suppress_alg(1), solve is the supported order)", who);
+    if (!e->have_ic) return efail(e, -2, "no snapshot of the initial conditions (idaens_create failed to take it)");
+    return 0;
+}
+
+// IDAReInit for the listed systems: hT0 by list position; hYY0 / hYP0 / add as idahip_reinit takes them
+int reinit_systems(idaens* e, const char* who, const int32_t* hIdx, int nsys, const double* hT0, const double* hYY0, const double* hYP0,
+                   int add) {
+    for (int q = 0; q < nsys; ++q) {
+        const int b = hIdx[q];
+        if (b < 0 || b >= e->batch) return efail(e, -2, "%s: system id %d out of range at list position %d", who, b, q);
+        if (e->sys[b].ph != PH_IDLE)
+            return efail(e, -2, "%s: system %d is inside a round-limited call (IDAENS_UNFINISHED): finish that call first", who, b);
+        if (!std::isfinite(hT0[q])) return efail(e, -2, "%s: the t0 of system %d is not finite", who, b);
+    }
+    ENS_CALL(e, idahip_reinit(e->ctx, hIdx, nsys, hYY0, hYP0, add));  // (a list with one id twice is refused here: nothing has changed yet)
+    for (int q = 0; q < nsys; ++q) {
+        Sys& s = e->sys[hIdx[q]];
+        e->retired_iters += s.niters;  // idaens_total_newton_iters is a total since creation
+        s = Sys();
+        s.tn = s.t_start = hT0[q];
+        s.rt.glo.assign(e->nrtfn, 0.0);  // the root state as install_roots leaves it
+        s.rt.ghi.assign(e->nrtfn, 0.0);
+        s.rt.grout.assign(e->nrtfn, 0.0);
+        s.rt.iroots.assign(e->nrtfn, 0.0);
+        s.rt.gactive.assign(e->nrtfn, 0);
     }
     return 0;
 }
@@ -1336,12 +1390,50 @@ extern "C" int idaens_calc_ic(idaens* e, int icopt, double tout1, int32_t* hStat
     if (icopt == IDAENS_YA_YDP_INIT && idahip_id(e->ctx, nullptr) != 1)
         return efail(e, -2, "idaens_calc_ic: IDAENS_YA_YDP_INIT needs the id vector (idahip_set_id)");
     if (e->started) return efail(e, -2, "idaens_calc_ic: only before the first solve, solve_schedule or stream call");
-    if (idahip_constraints(e->ctx, nullptr) == 1) return efail(e, -2, "idaens_calc_ic: a ctx with constraints is not supported (idahip_set_constraints)");
-    if (idahip_krylov(e->ctx, nullptr) == 1) return efail(e, -2, "idaens_calc_ic: a Krylov ctx is not supported (idahip_create_krylov)");
-    if (idahip_suppress_alg(e->ctx) == 1)
-        return efail(e, -2, "idaens_calc_ic: not with suppress_alg on (set_id, calc_ic, idahip_set_suppress_alg(1), solve is the supported order)");
-    if (!e->have_ic) return efail(e, -2, "no snapshot of the initial conditions (idaens_create failed to take it)");
-    return calc_ic(e, icopt, tout1, hStatus);
+    if (const int rc = calc_ic_refusals(e, "idaens_calc_ic")) return rc;
+    std::vector<int32_t> all(e->batch);
+    for (int b = 0; b < e->batch; ++b) all[b] = b;
+    const std::vector<double> touts((size_t)e->batch, tout1);
+    return calc_ic(e, icopt, all, touts.data(), hStatus, true);
+}
+
+extern "C" int idaens_calc_ic_systems(idaens* e, int icopt, const int32_t* hIdx, int nsys, const double* hTout1, int32_t* hStatus) {
+    if (!e || nsys < 0 || (nsys > 0 && (!hIdx || !hTout1 || !hStatus))) return -1;
+    if (icopt != IDAENS_YA_YDP_INIT && icopt != IDAENS_Y_INIT) return efail(e, -2, "idaens_calc_ic_systems: unknown icopt %d", icopt);
+    if (icopt == IDAENS_YA_YDP_INIT && idahip_id(e->ctx, nullptr) != 1)
+        return efail(e, -2, "idaens_calc_ic_systems: IDAENS_YA_YDP_INIT needs the id vector (idahip_set_id)");
+    if (const int rc = calc_ic_refusals(e, "idaens_calc_ic_systems")) return rc;
+    std::vector<uint8_t> seen((size_t)e->batch, 0);
+    for (int q = 0; q < nsys; ++q) {
+        const int b = hIdx[q];
+        if (b < 0 || b >= e->batch) return efail(e, -2, "idaens_calc_ic_systems: system id %d out of range at list position %d", b, q);
+        if (seen[b]) return efail(e, -2, "idaens_calc_ic_systems: system id %d listed twice (again at list position %d)", b, q);
+        seen[b] = 1;
+        const Sys& s = e->sys[b];
+        if (s.ph != PH_IDLE || s.nst > 0 || s.setup_done || s.dead)
+            return efail(e, -2, "idaens_calc_ic_systems: system %d has started: only systems that have not taken a step since idaens_create or idaens_reinit", b);
+    }
+    if (nsys == 0) return 0;
+    return calc_ic(e, icopt, std::vector<int32_t>(hIdx, hIdx + nsys), hTout1, hStatus, false);
+}
+
+extern "C" int idaens_reinit(idaens* e, const int32_t* hIdx, int nsys, const double* hT0, const double* hYY0, const double* hYP0) {
+    if (!e || nsys < 0 || (nsys > 0 && (!hIdx || !hT0 || !hYY0 || !hYP0))) return -1;
+    return reinit_systems(e, "idaens_reinit", hIdx, nsys, hT0, hYY0, hYP0, 0);
+}
+
+extern "C" int idaens_reinit_at_return(idaens* e, const int32_t* hIdx, int nsys, const double* hDY, const double* hDYP) {
+    if (!e || nsys < 0 || (nsys > 0 && !hIdx)) return -1;
+    std::vector<double> t0((size_t)nsys, 0.0);
+    for (int q = 0; q < nsys; ++q) {
+        const int b = hIdx[q];
+        if (b < 0 || b >= e->batch) return efail(e, -2, "idaens_reinit_at_return: system id %d out of range at list position %d", b, q);
+        const Sys& s = e->sys[b];
+        if (s.ph == PH_IDLE && !s.returned)
+            return efail(e, -2, "idaens_reinit_at_return: system %d has not returned from a solve call since it was created or reinitialised", b);
+        t0[q] = s.tret;
+    }
+    return reinit_systems(e, "idaens_reinit_at_return", hIdx, nsys, t0.data(), hDY, hDYP, 1);
 }
 
 extern "C" {

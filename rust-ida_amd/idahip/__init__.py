@@ -53,6 +53,7 @@ HIP_SYMBOLS = [
     "idahip_set_krylov_rounds", "idahip_krylov_rounds", "idahip_krylov_rounds_put_counters", "idahip_krylov_rounds_get_counters",
     "idahip_set_suppress_alg", "idahip_suppress_alg", "idahip_wrms_masked",
     "idahip_set_mass_action", "idahip_mass_action_pattern", "idahip_mass_action_jac", "idahip_set_rate_network",
+    "idahip_reinit",
 ]
 ENS_SYMBOLS = [
     "idaens_create", "idaens_destroy", "idaens_last_error", "idaens_set_max_num_steps", "idaens_set_max_ord", "idaens_set_fused_newton", "idaens_set_device_controller", "idaens_device_controller_active", "idaens_set_roots", "idaens_set_root_fn",
@@ -60,6 +61,7 @@ ENS_SYMBOLS = [
     "idaens_get_counter", "idaens_get_real", "idaens_get_yy", "idaens_get_yp", "idaens_get_dky", "idaens_total_newton_iters",
     "idaens_total_rounds", "idaens_trace_system", "idaens_trace_len", "idaens_trace_get", "idaens_calc_ic",
     "idaens_set_stop_time", "idaens_get_stop_time",
+    "idaens_reinit", "idaens_reinit_at_return", "idaens_calc_ic_systems",
 ]
 
 from . import mass_action  # noqa: E402,F401  (IDAHIP_MASS_ACTION: a network checked and flattened, numpy only)
@@ -151,6 +153,7 @@ def load():
     H.idahip_get_dky.argtypes = [vp, i32p, i32p, dp, dp, i32p, ci]
     H.idahip_snapshot_initial.argtypes = [vp]
     H.idahip_restore_initial.argtypes = [vp, i32p, ci]
+    H.idahip_reinit.argtypes = [vp, i32p, ci, dp, dp, ci]
     H.idahip_set_lu_variant.argtypes = [vp, ci]
     H.idahip_set_jac_in_lu.argtypes = [vp, ci]
     H.idahip_jac_in_lu.argtypes = [vp]
@@ -218,6 +221,9 @@ def load():
     E.idaens_stream.argtypes = [vp, dp, ci, C.c_long, C.c_long, i64p]
     E.idaens_calc_ic.argtypes = [vp, ci, cd, i32p]
     E.idaens_set_stop_time.argtypes = [vp, dp, ci]
+    E.idaens_reinit.argtypes = [vp, i32p, ci, dp, dp, dp]
+    E.idaens_reinit_at_return.argtypes = [vp, i32p, ci, dp, dp]
+    E.idaens_calc_ic_systems.argtypes = [vp, ci, i32p, ci, dp, i32p]
     E.idaens_get_stop_time.argtypes = [vp, dp]
     E.idaens_get_counter.argtypes = [vp, ci, i64p]
     E.idaens_get_real.argtypes = [vp, ci, dp]
@@ -820,6 +826,15 @@ class Ctx:
         idx = self.all_idx() if idx is None else _i32(idx)
         self._chk(self.H.idahip_restore_initial(self.h, _p(idx, i32p), idx.size), "restore_initial")
 
+    def reinit(self, idx, yy0, yp0, add=False):
+        """Ida::new with new values for the listed systems: phi[0] = yy = y0, phi[1] = yp = y0', phi[2..5] = 0, and the snapshot's
+        rows where one has been taken. yy0 / yp0: [nsys][n] by list position; with add they are increments on the systems' current
+        yy / yp, and either may be None (that side stays as it is)."""
+        idx = self.all_idx() if idx is None else _i32(idx)
+        yy0 = None if yy0 is None else _f64(yy0).reshape(idx.size, self.n)
+        yp0 = None if yp0 is None else _f64(yp0).reshape(idx.size, self.n)
+        self._chk(self.H.idahip_reinit(self.h, _p(idx, i32p), idx.size, _p(yy0), _p(yp0), 1 if add else 0), "reinit")
+
     def pow_batch(self, x, y):
         """The device controller's pow (glibc_pow.hpp) for arrays of arguments."""
         x, y = _f64(x), _f64(y)
@@ -1027,6 +1042,36 @@ class Ensemble:
         if rc < 0:
             self.ctx.fail("idaens_calc_ic failed (%d): %s" % (rc, (self.E.idaens_last_error(self.h) or b"").decode()))
         return status
+
+    def calc_ic_systems(self, icopt, idx, tout1):
+        """calc_ic for listed systems that have not taken a step since they were created or reinitialised (after an event);
+        tout1: a scalar or one value per listed system. -> status [nsys] by list position."""
+        idx = _i32(np.atleast_1d(idx))
+        tout1 = _f64(np.broadcast_to(tout1, idx.shape))
+        status = np.zeros(idx.size, dtype=np.int32)
+        rc = self.E.idaens_calc_ic_systems(self.h, int(icopt), _p(idx, i32p), idx.size, _p(tout1), _p(status, i32p))
+        if rc < 0:
+            self.ctx.fail("idaens_calc_ic_systems failed (%d): %s" % (rc, (self.E.idaens_last_error(self.h) or b"").decode()))
+        return status
+
+    def reinit(self, idx, t0, yy0, yp0):
+        """C IDA's IDAReInit for the listed systems: each is a created system again, at t0 (a scalar or one value per listed
+        system) with y0 = yy0, y0' = yp0 ([nsys][n]): counters, root state, stop time and a fatal status start over, and the next
+        solve runs the first-call block for these systems alone. Refusals raise IdaHipError."""
+        idx = _i32(np.atleast_1d(idx))
+        t0 = _f64(np.broadcast_to(t0, idx.shape))
+        yy0, yp0 = _f64(yy0).reshape(idx.size, self.ctx.n), _f64(yp0).reshape(idx.size, self.ctx.n)
+        if self.E.idaens_reinit(self.h, _p(idx, i32p), idx.size, _p(t0), _p(yy0), _p(yp0)) != 0:
+            raise IdaHipError("reinit: %s" % (self.E.idaens_last_error(self.h) or b"").decode())
+
+    def reinit_at_return(self, idx, dy=None, dyp=None):
+        """The event path of reinit: t0 = the tret each listed system last returned with, and the new values are what it
+        reported there plus the jump dy / dyp ([nsys][n]; None: that side as it is), added on the device."""
+        idx = _i32(np.atleast_1d(idx))
+        dy = None if dy is None else _f64(dy).reshape(idx.size, self.ctx.n)
+        dyp = None if dyp is None else _f64(dyp).reshape(idx.size, self.ctx.n)
+        if self.E.idaens_reinit_at_return(self.h, _p(idx, i32p), idx.size, _p(dy), _p(dyp)) != 0:
+            raise IdaHipError("reinit_at_return: %s" % (self.E.idaens_last_error(self.h) or b"").decode())
 
     def solve(self, tout, itask=0, max_rounds=0):
         tret = np.zeros(self.ctx.batch)
