@@ -218,7 +218,17 @@ int idaens_reinit_at_return(idaens* e, const int32_t* hIdx, int nsys, const doub
  * resume on the next call with the same tout). Returns 0, or < 0 on a device/ABI failure.
  * A negative per-system status (an IdaError) is sticky: later solve calls leave that system alone and report the same status
  * again (the reference's Ida::solve can be called again after an error and would try to continue), until idaens_reinit gives the
- * system new values: a reinitialised system is a created one, with no status. */
+ * system new values: a reinitialised system is a created one, with no status.
+ * Both time directions are supported: the first tout of a system fixes its direction (tout < t0: hh < 0), and every test of the
+ * flow is written with the sign of hh. A tout behind the last step -- tout on the far side of tn - hused, in either direction;
+ * a tout inside the last step interpolates -- returns IDAENS_BAD_T, sticky as above, with tret left as the previous return set
+ * it. With root functions that refusal comes from the root check of the call's entry, r_check3, whose interpolation at tout it
+ * is: r_check3 does NOT evaluate the root functions at a refused tout, and nge does not count such an evaluation. What comes before
+ * it is as in the reference: directly after a IDAENS_ROOT_RETURN, r_check2 evaluates g at the root (and once more next to it where
+ * a function is zero there) and counts that in nge before r_check3 refuses. (The reference's r_check3 ignores the failed
+ * interpolation, evaluates g on the values of the previous return, counts that evaluation and searches a bracket made of them
+ * before its stop test refuses the same tout, src/impl_r_check.rs:236-252: since the system is left alone from then on, the
+ * library spends nothing on values that are not y(tout).) */
 int idaens_solve(idaens* e, double tout, int itask, double* hTret, int32_t* hStatus, long max_rounds);
 
 /* The same for a whole output schedule: for every system Ida::solve(touts[0]), Ida::solve(touts[1]), ... in IDA_NORMAL

@@ -120,16 +120,20 @@ class DirectIda(KR.RefIda):
         o = self.o
         o.set("nsetups", o.get("nsetups") + 1)
         o.set("nje", o.get("nje") + 1)
-        if self.dq:
-            J = dense_dq(self.net, self.k, o.getv("yy"), o.getv("yp"), o.getv("ewt"), r, o.get("cj"), o.get("hh"))
-            self.nre_dq += self.net.n
-        else:
-            J = jac(self.net, self.k, o.get("cj"), o.getv("yy"))
-        info, self.lu, self.piv = O.getrf(J.T)
+        info, self.lu, self.piv = O.getrf(self._jacobian(r).T)
         o.set("cjold", o.get("cj"))
         o.set("cjratio", 1.0)
         o.set("ss", 20.0)
         return KR.NLS_SUCCESS if info == 0 else KR.NLS_LSETUP_RECVR
+
+    def _jacobian(self, r):
+        """J [n][n] column-major at the oracle's current state, r the residual there (a subclass with another problem overrides
+        this and _res: tests/backward_cases.py)."""
+        o = self.o
+        if self.dq:
+            self.nre_dq += self.net.n
+            return dense_dq(self.net, self.k, o.getv("yy"), o.getv("yp"), o.getv("ewt"), r, o.get("cj"), o.get("hh"))
+        return jac(self.net, self.k, o.get("cj"), o.getv("yy"))
 
     # -------- the constraint check of an attempt (constr_ref._constraint_check, inherited), between the Newton solve and the error
     # test. krylov_ref.RefIda._step has no place for it and is not copied here: a recoverable violation leaves the Newton solve as

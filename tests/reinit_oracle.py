@@ -13,7 +13,8 @@ roots_cases case as roots_cases.drive drives them, and after every solve op the 
 `only` admits) are reinitialised with the jump dy = -0.5 * y (JUMPS: 4 * y on Lorenz) at the components of the root functions that
 fired, zero elsewhere, and y' as reported. how = "at_return": t0 = tret and the jump is added by the callee; how = "host": t0 = tret + 0.25 and the sum y + dy is
 formed by the caller with numpy's addition (one IEEE addition per component either way). A system restarted beyond the tout of the
-next call integrates backwards to it, and every later tout would lie behind it (IDAENS_BAD_T): how = "host" drives the first tout only.
+next call integrates backwards to it, and every later tout lies behind it: IDAENS_BAD_T, sticky, with the root functions not
+evaluated at the refused tout by r_check3 (tests/roots_oracle.py models it, include/ida_ensemble.h states it). Both variants drive every tout.
 """
 import ctypes as C
 
@@ -87,7 +88,8 @@ class Harness(RO.Harness):
         self.L.oracle_ida_record_steps(self.h, 1)
         self.dead = None
         self.calls = []
-        self.last_tret = 0.0
+        self.last_tret = self.prev_tret = 0.0
+        self.refused_evals = 0  # nge starts over with the new object
 
     def state(self):
         d = RO.Harness.state(self)
@@ -165,7 +167,7 @@ def drive_events(c, d, how="at_return", only=None):
     ops = []
     jumps = {}
     cap = MAX_JUMPS[how]
-    for t in (c["touts"][:1] if how == "host" else c["touts"]):
+    for t in c["touts"]:
         for _ in range(MAX_RETURNS):
             ops.append(("solve", float(t)))
             st = d.solve(float(t))

@@ -108,7 +108,16 @@ def test_census_of_the_event_runs(name, how):
         for b in np.nonzero(r["status"] == T.ROOT_RETURN)[0]:
             times[b].add(float(r["tret"][b]))
     assert sum(1 for o in ops if o[0] == "jump") >= 1
-    if how == "at_return":  # (how = "host" stops after the first tout: it restarts whoever has a root before it)
+    if how == "host" and name in ("lorenz", "heat20"):
+        # a system restarted beyond the first tout went back towards it: a later tout lies behind it and the call is refused. Lorenz
+        # gets there from a SUCCESS at the first tout (r_check3 is entered: the evaluation the library does not make); heat, unstable
+        # backwards, from TOO_MUCH_WORK (tretlast == tn: stop_test1 refuses, no root check on either side). Roberts and linear24 fail
+        # their error tests on the way back and never see a later tout.
+        bad = rec[-1]["status"] == RO.BAD_T
+        assert bad.any() and (rec[-1]["hh"][bad] < 0.0).all(), rec[-1]["status"]
+        assert sum(h.refused_evals for h in d.hs) >= (int(bad.sum()) if name == "lorenz" else 0)
+        assert name != "heat20" or sum(h.refused_evals for h in d.hs) == 0
+    if how == "at_return":  # (how = "host" restarts whoever has a root before the first tout, and those systems end there)
         assert all(len(t) >= 1 for t in times), "a system without a root return"
         first = {min(t) for t in times}
         assert len(first) >= 3, first

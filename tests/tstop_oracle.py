@@ -4,6 +4,8 @@ setters), compiled into a temporary directory with the oracle Makefile's flags a
 TEST INFRASTRUCTURE ONLY. `Harness` is one `Ida` object that follows the library's calling rules where they differ from the oracle's:
   * a negative status is sticky (the library leaves such a system alone), except IDAENS_TOO_MUCH_WORK and an IDAENS_ILL_INPUT of a
     system that has not started (tret = t0 then);
+  * IDAENS_BAD_T (a tout behind the last step) sets no tret: the reference returns an Err there. The library's tret stays what the
+    previous return left, and so does the harness';
   * quirk Q15: after a TSTOP return of an IDA_ONE_STEP call the oracle, like the reference, keeps the stop time; the library clears
     it as C IDA does, and so does this helper, by hand.
 A run is a list of ops, the same list for the product (tests/test_gpu_stop_time.py) and for the harness:
@@ -25,7 +27,7 @@ import oracle_lib as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = np.finfo(np.float64).eps
 SUCCESS, TSTOP_RETURN, ROOT_RETURN = 0, 1, 2
-TOO_MUCH_WORK, ILL_INPUT, BAD_TSTOP = -1, -22, -27
+TOO_MUCH_WORK, ILL_INPUT, BAD_T, BAD_TSTOP = -1, -22, -26, -27
 NORMAL, ONE_STEP = 0, 1
 SCALARS = ("tn", "hh", "hused", "kused", "nst", "nre", "nni", "netf", "ncfn", "nsetups")
 _LIB = None
@@ -98,6 +100,7 @@ class Harness(O.OracleIda):
             self.set("mxstep", mxstep)
         mine.oracle_ida_record_steps(self.h, 1)
         self.dead = None      # (status, tret) once a status is sticky
+        self.prev_tret = self.t0  # what the previous return left
         self.calls = []       # census: one dict per solve call
 
     def _lib(self):
@@ -125,10 +128,13 @@ class Harness(O.OracleIda):
         nst0, tstop0, tn0, hh0 = int(self.get("nst")), self.stop_time(), self.get("tn"), self.get("hh")
         st, tret = O.OracleIda.solve(self, tout, itask)
         nst1 = int(self.get("nst"))
+        if st == BAD_T:
+            tret = self.prev_tret
         if st == ILL_INPUT and nst1 == 0:
             tret = self.t0  # the system has not started
         elif st < 0 and st != TOO_MUCH_WORK:
             self.dead = (st, tret)
+        self.prev_tret = tret
         if st == TSTOP_RETURN and itask == ONE_STEP and nst1 == nst0:
             self.set_stop_time(None)  # Q15
         self.calls.append({"tout": tout, "itask": itask, "status": st, "nst0": nst0, "nst1": nst1, "tstop0": tstop0, "tn0": tn0, "hh0": hh0,
