@@ -446,6 +446,20 @@ impl Ctx {
         self.check(rc).map(|_| ())
     }
 
+    /// Device lock-step stepper, dense direct ctx, n <= 1024: `Some(true)` = a round's LU launches are sized on the host by the
+    /// length of its list (one host wait per round, no surplus workgroups), `Some(false)` = sized for the batch, `None` = the
+    /// library's choice; results identical.
+    pub fn set_lu_count_on_host(&mut self, on: Option<bool>) -> Result<(), Error> {
+        let rc = unsafe { sys::idahip_set_lu_count_on_host(self.raw, on.map_or(-1, |v| v as i32)) };
+        self.check(rc).map(|_| ())
+    }
+
+    /// Workgroups of the panels' SLOW launches (they walk their list grid-stride: any number is correct); 0 = automatic.
+    pub fn set_lu_slow_grid(&mut self, workgroups: i32) -> Result<(), Error> {
+        let rc = unsafe { sys::idahip_set_lu_slow_grid(self.raw, workgroups) };
+        self.check(rc).map(|_| ())
+    }
+
     /// Difference-quotient Jacobians (C IDA's idaLsDenseDQJac / idaLsBandDQJac) for every Jacobian this ctx forms.
     /// (Like the rest of this crate, not compiled in this repository's checks.)
     pub fn set_jacobian_dq(&mut self, on: bool) -> Result<(), Error> {

@@ -631,6 +631,25 @@ int idahip_lu_superpanel(const idahip_ctx* ctx); /* the setting in force */
  * the factorisation's time is proportional to the batch (config 3). */
 int idahip_set_lu_period(idahip_ctx* ctx, int rounds);
 int idahip_lu_period(const idahip_ctx* ctx); /* the setting in force */
+/* Device lock-step stepper (idahip_round_solve) on a dense direct ctx, 8 < n <= 1024: where the length of a round's list of systems
+ * to factor is known when the factorisation's kernels are launched.
+ *   1: on the host. The kernel that builds the list posts its length to pinned host memory, the host polls for it behind the round's
+ *      first residual sweep, every LU launch of the round has exactly the workgroups it needs, and a round without setups launches
+ *      neither the setups' residual sweep nor a factorisation. One host wait per round.
+ *   0: on the device only. Every LU launch is sized for the whole batch and its surplus workgroups leave on reading the count; the
+ *      host never waits inside a round.
+ *  -1: the library's choice (the default; IDAHIP_LU_COUNT_ON_HOST=-1|0|1, read at idahip_create, sets it too).
+ * Matrices with more than 1024 rows always take the host count; band and Krylov contexts never do. A scheduling choice: the
+ * same kernels run on the same matrices, results and counters are bit-identical (tests/test_gpu_lu_launch_sizes.py).
+ * Any other value is refused (-1). */
+int idahip_set_lu_count_on_host(idahip_ctx* ctx, int on);
+int idahip_lu_count_on_host(const idahip_ctx* ctx); /* what idahip_round_solve does on this ctx now: 0 or 1 */
+/* The number of workgroups of the wave-per-matrix panels' second (SLOW) launches (LU variant 4, <= 512 live rows), in every call that
+ * factors. They walk the list of matrices their first launch handed over -- matrices with exact zeros, NaNs or infinities;
+ * normally none -- in a grid-stride loop, so that any number is correct. 0 = automatic (the default): one per listed system, and in
+ * idahip_round_solve with the count on the host (n <= 1024) clamp(2 * the largest list of the last round's factorisation + 32, 32,
+ * count). Tests set 1 or 2 to make every workgroup walk several entries. Negative values are refused (-1). */
+int idahip_set_lu_slow_grid(idahip_ctx* ctx, int workgroups);
 /* 0 for the product library. 1 for a TIMING BUILD (-DIDAHIP_TIMING_BUILD, rust-ida_amd/csrc/exp_switches.hpp): a library in
  * which parts of kernels were removed or replaced to measure what they cost -- its results are garbage by design; a caller
  * that cares (tests, bench.py) refuses to run on one. No ctx, no device needed. */

@@ -20,6 +20,7 @@ namespace idahip {
 constexpr int MXORDP1 = 6;      // src/constants.rs:6
 constexpr int TINY_N = 8;       // n <= TINY_N: one thread per system (whole Newton body in registers/L1)
 constexpr int LU_NB = 32;       // panel width of the blocked LU
+constexpr int LU_COUNT_ON_HOST_DEFAULT = 1;  // idahip_round_solve, n <= 1024: what idahip_set_lu_count_on_host(-1) means (profiles/lu_launch_sizes_ab.txt)
 constexpr int LU_MAX_N = 1024;  // blocked LU, fast pipelines: at most two panel rows per lane of a 512-thread workgroup
 constexpr int LU_WIDE_ROWS = 2048;  // n > 1024: at most this many live rows -> 16-column panels with four rows per lane (above: 8 columns, eight rows)
 constexpr int LU_ZMAP_MIN_N = 2048;  // from this size on the factorisation leaves a map of the factors' zero blocks for the triangular solves
@@ -121,6 +122,14 @@ struct idahip_ctx {
     // (k - 1) / k of the stepping systems ask for one, at most k - 1 rounds in a row. Pays where a factorisation's cost hardly depends
     // on the number of matrices (n > 1024: one workgroup per matrix, a chain of launches): idahip_set_lu_period / IDAHIP_LU_PERIOD.
     int lu_period = 1;
+    // idahip_round_solve on a dense direct ctx: the LU list's length travels to the host every round (posted by round_lists_kernel,
+    // polled behind the first residual sweep) and sizes the round's LU launches exactly; a round without setups launches none.
+    // -1 = the library's choice (lu_count_on_host_on, idahip.hip), 0 = the launches are sized for the batch and their surplus
+    // workgroups leave on reading the count, 1 = on the host at every n: idahip_set_lu_count_on_host / IDAHIP_LU_COUNT_ON_HOST.
+    int lu_count_on_host = -1;
+    // idahip_set_lu_slow_grid: workgroups of the panels' SLOW launches; 0 = automatic (one per listed system; idahip_round_solve with
+    // the count on the host: from the last round's largest redo count)
+    int lu_slow_grid = 0;
                          // 3: panel kernels with two rows per lane + narrow update (lu_kernels.hpp): cross-check, and n > 512
 
     // device-resident stepper for small systems (tiny_ida.hpp): controller states and per-call buffers (lazy)
@@ -132,9 +141,11 @@ struct idahip_ctx {
     int tiny_ntout_cap = 0, tiny_yout_cap = 0;
 
     // device-resident lock-step stepper (round_ida.hpp): per-system round state, the LU list, the round summary (lazy)
-    int32_t* rnd_i = nullptr;   // 8 int arrays of length batch + lu_cnt[1] + summary[2]
+    int32_t* rnd_i = nullptr;   // 8 int arrays of length batch + lu_cnt[2] + summary[2] + lu_wait[1] + the statistics
     double* rnd_d = nullptr;    // 4 double arrays of length batch
     int32_t* rnd_host = nullptr;  // pinned: the round summary
+    int32_t* rnd_mail = nullptr;  // pinned, coherent, [4]: round_lists_kernel posts the LU list's length, the last redo maximum and a sequence number
+    int rnd_mail_seq = 0;         // the number the host waits for (idahip_round_solve, the count on the host, n <= 1024)
 
     unsigned long long* dbg_stamps = nullptr;  // timing builds only (idahip_debug_stamps)
 
@@ -177,7 +188,7 @@ struct idahip_ctx {
     // timing
     int timing = 0;  // 0 off, 1 per kernel class, 2 also per kernel of the LU
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-    hipEvent_t ev_cnt = nullptr;  // idahip_round_solve, n > 1024: the LU list's length has reached the host
+    hipEvent_t ev_cnt = nullptr;  // idahip_round_solve, the count on the host: the LU list's length has reached the host
     double k_ms[IDAHIP_K_COUNT] = {0};
     int64_t k_launches[IDAHIP_K_COUNT] = {0};
     int64_t k_systems[IDAHIP_K_COUNT] = {0};

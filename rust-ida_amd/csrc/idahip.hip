@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <thread>
 
 #include "common.hpp"
 #include "list_call.hpp"
@@ -219,6 +220,10 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
         const int v = (int)std::strtol(sp, nullptr, 10);
         if (v >= 1 && v <= 64) c->lu_period = v;
     }
+    if (const char* sp = std::getenv("IDAHIP_LU_COUNT_ON_HOST")) {  // (A/B runs of one library: -1, 0 or 1 as idahip_set_lu_count_on_host)
+        const int v = (int)std::strtol(sp, nullptr, 10);
+        if (v >= -1 && v <= 1) c->lu_count_on_host = v;
+    }
     int ndev = 0;
     if (device < 0 || hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) { delete c; return -100; }
     DevGuard dev_guard__(device);  // allocations, stream and events below belong to `device`; the caller's device is restored
@@ -240,7 +245,7 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     rc |= dalloc(c, &c->phi, (size_t)MXORDP1 * bn);
     if (!krylov_maxl) { rc |= dalloc(c, &c->piv, bn); rc |= dalloc(c, &c->perm, bn); }  // a Krylov ctx has no pivots
     rc |= dalloc(c, &c->lu_info, (size_t)batch);  // (also the band calls on caller-owned buffers report through it, on any ctx)
-    if (!krylov_maxl) { rc |= dalloc(c, &c->lu_redo, (size_t)batch); rc |= dalloc(c, &c->lu_nzb, (size_t)batch); }
+    if (!krylov_maxl) { rc |= dalloc(c, &c->lu_redo, (size_t)LU_REDO_SLOTS + 2 * (size_t)batch); rc |= dalloc(c, &c->lu_nzb, (size_t)batch); }  // (lu_redo: counters, then flag and list entry interleaved: LuWs::redo)
     if (band) rc |= dalloc(c, &c->bab, bn * c->ldab);  // instead of every n x n buffer below
     if (!nomat) rc |= dalloc(c, &c->lu, bnn);
     if (!nomat && n > LU_MAX_N) rc |= dalloc(c, &c->lu_bz, (size_t)batch * 64);
@@ -288,7 +293,7 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     // pivots and row permutation in range before the first setup: a Newton iteration or solve ahead of it gathers rows by them
     if (c->piv) (void)hipMemsetAsync(c->piv, 0, bn * sizeof(int64_t), c->stream);
     if (c->perm) (void)hipMemsetAsync(c->perm, 0, bn * sizeof(int32_t), c->stream);
-    if (c->lu_redo) (void)hipMemsetAsync(c->lu_redo, 0, (size_t)batch * sizeof(int), c->stream);
+    if (c->lu_redo) (void)hipMemsetAsync(c->lu_redo, 0, ((size_t)LU_REDO_SLOTS + 2 * (size_t)batch) * sizeof(int), c->stream);
     if (c->bab) (void)hipMemsetAsync(c->bab, 0, bn * c->ldab * sizeof(double), c->stream);
     if (c->lu_dirty) {  // the factors start as zeros, and so does the map of their blocks that have ever held anything else
         (void)hipMemsetAsync(c->lu, 0, bnn * sizeof(double), c->stream);
@@ -349,6 +354,7 @@ int idahip_destroy(idahip_ctx* c) {
     delete c->ma;
     delete c->ma_law;
     if (c->rnd_host) (void)hipHostFree(c->rnd_host);
+    if (c->rnd_mail) (void)hipHostFree(c->rnd_mail);
     if (c->cb_jpin) (void)hipHostFree(c->cb_jpin);
     if (c->cb_jdev) (void)hipFree(c->cb_jdev);
     for (int i = 0; i < NSLOT; ++i) {
@@ -2563,12 +2569,55 @@ static int krylov_round_setup(idahip_ctx* c, const RoundArgs& a, SysArgs& sa) {
     return band_factor(c, c->kry_pab, (long)c->kry_pldab * n, c->kry_ppiv, n, c->kry_pml, c->kry_pmu, a.lu_list, batch, a.lu_cnt);
 }
 
+// whether idahip_round_solve brings the LU list's length to the host and sizes the round's LU launches by it: dense direct contexts
+// only; n > 1024 always (measured in round 4), up to 1024 by idahip_set_lu_count_on_host, the library's choice being LU_COUNT_ON_HOST_DEFAULT
+static bool lu_count_on_host_on(const idahip_ctx* c) {
+    if (c->krylov || c->band || c->n <= TINY_N) return false;
+    if (c->n > LU_MAX_N) return true;
+    return (c->lu_count_on_host < 0 ? LU_COUNT_ON_HOST_DEFAULT : c->lu_count_on_host) != 0;
+}
+
 // the setup launches of a round on a direct ctx: residual and Jacobian of the systems that set up, and the factorisation of the
-// device-built list. lu_cnt_on_host: the list's length is on its way to the host (ev_cnt) and sizes the LU's launches.
+// device-built list. lu_cnt_on_host: the list's length is on its way to the host (ev_cnt) and sizes the LU's launches. Up to
+// n = 1024 the host waits for it first thing -- behind the residual sweep round_newton has just enqueued -- and a round without
+// setups (idahip_set_lu_period's postponed rounds among them) launches nothing here; above, after the setups' own sweeps, as ever.
 static int direct_round_setup(idahip_ctx* c, const RoundArgs& a, SysArgs& sa, bool lu_cnt_on_host) {
     const int batch = c->batch, n = c->n;
     const long nn = (long)n * n;
     int rc;
+    int nlu = batch, slow_grid = 0;
+    const int* d_cnt = a.lu_cnt;
+    const auto count_arrives = [&]() -> int {
+        const int32_t* got = c->rnd_host + 2;
+        if (a.host_mail) {
+            // round_lists_kernel posts the count to pinned memory itself: nothing sits in the stream between it and the residual sweep
+            // behind it. The host polls; a stream that has run dry without the post (a launch that failed) ends the wait.
+            got = c->rnd_mail;
+            for (unsigned spins = 1; __atomic_load_n(&c->rnd_mail[2], __ATOMIC_ACQUIRE) != a.mail_seq; ++spins) {
+                std::this_thread::yield();  // (the core goes to whoever wants it: the other groups' threads enqueue meanwhile)
+                if ((spins & 0x3ff) != 0) continue;
+                const hipError_t e = hipStreamQuery(c->stream);
+                if (e == hipSuccess && __atomic_load_n(&c->rnd_mail[2], __ATOMIC_ACQUIRE) != a.mail_seq)
+                    return fail(c, -4, "the round's list length never reached the host");
+                if (e != hipSuccess && e != hipErrorNotReady) return fail(c, -100, "hipStreamQuery failed: %s", hipGetErrorString(e));
+            }
+        } else {
+            IDAHIP_HIP(c, hipEventSynchronize(c->ev_cnt));
+        }
+        nlu = got[0];
+        d_cnt = nullptr;
+        if (nlu < 0 || nlu > batch) return fail(c, -4, "list length %d outside 0..%d", nlu, batch);
+        if (!a.host_mail) return 0;  // (n > 1024: the redo maximum does not travel; the SLOW launches keep a wave per system)
+        // the SLOW panel launches walk a list that is normally empty: clamp(2 * the last round's largest list + 32, 32, count) workgroups
+        const int redo = std::min(std::max(got[1], 0), batch);
+        slow_grid = c->lu_slow_grid > 0 ? c->lu_slow_grid : std::min(std::max(2 * redo + 32, 32), nlu);
+        return 0;
+    };
+    const bool count_first = lu_cnt_on_host && a.host_mail;
+    if (count_first) {
+        if ((rc = count_arrives())) return rc;
+        if (nlu == 0) return 0;
+    }
     if (a.jac_in_lu) {  // the plain sweep for the systems that set up: the factorisation forms J from A and B itself
         KTimer kt(c, IDAHIP_K_SYS, 0);
         sa.skip = a.skipL;
@@ -2589,18 +2638,11 @@ static int direct_round_setup(idahip_ctx* c, const RoundArgs& a, SysArgs& sa, bo
                                batch, dq_evals(c));
         if ((rc = launch_jac(c, c->jw, a.ident, a.cj, batch, nullptr, nullptr, nullptr, a.skipL, c->dq_hh))) return rc;
     }
-    int nlu = batch;
-    const int* d_cnt = a.lu_cnt;
-    if (lu_cnt_on_host) {
-        IDAHIP_HIP(c, hipEventSynchronize(c->ev_cnt));
-        nlu = c->rnd_host[2];
-        d_cnt = nullptr;
-        if (nlu < 0 || nlu > batch) return fail(c, -4, "list length %d outside 0..%d", nlu, batch);
-    }
+    if (lu_cnt_on_host && !count_first && (rc = count_arrives())) return rc;
     const LuJac jq{c->A, c->B, a.cj, 1};  // (cj by system id)
     KTimer kt(c, IDAHIP_K_LU, 0);
     if (c->band) rc = band_factor(c, c->bab, (long)c->ldab * n, c->piv, n, c->ml, c->mu, a.lu_list, nlu, d_cnt);
-    else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt, a.jac_in_lu ? &jq : nullptr);
+    else rc = lu_factor_batched(c, c->jw, nn, c->lu, nn, (long long*)c->piv, n, c->perm, a.lu_list, nlu, d_cnt, a.jac_in_lu ? &jq : nullptr, slow_grid);
     if (rc) return rc;
     return post_launch(c, "lu");
 }
@@ -2677,6 +2719,12 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     if (!c->rnd_d) rc |= dalloc(c, &c->rnd_d, (size_t)4 * batch);
     if (rc) return rc;
     if (!c->rnd_host) IDAHIP_HIP(c, hipHostMalloc((void**)&c->rnd_host, 4 * sizeof(int32_t)));
+    const bool lu_cnt_on_host = lu_count_on_host_on(c);
+    const bool lu_cnt_mail = lu_cnt_on_host && n <= LU_MAX_N;  // (above, the count comes by copy and event behind the setups' sweeps, as measured in round 4)
+    if (lu_cnt_mail && !c->rnd_mail) {
+        IDAHIP_HIP(c, hipHostMalloc((void**)&c->rnd_mail, 4 * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(c->rnd_mail, 0, 4 * sizeof(int32_t));
+    }
     // whether any system of the call has a stop time: the kernels without it are the ones that ran before there was one
     bool tstop = false;
     for (int b = 0; b < batch; ++b) tstop = tstop || static_cast<const idactl::SysCore*>(hSys)[b].tstopset;
@@ -2711,9 +2759,12 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
     a.roots = (idahip_root_state*)c->tiny_roots;
     int* ib = c->rnd_i;
     a.stepping = ib; a.in_newton = ib + batch; a.skipP = ib + 2 * batch; a.skipL = ib + 3 * batch; a.skipI = ib + 4 * batch;
-    a.skipS = ib + 5 * batch; a.ident = ib + 6 * batch; a.lu_list = ib + 7 * batch; a.lu_cnt = ib + 8 * batch; a.summary = ib + 8 * batch + 1; a.lu_wait = ib + 8 * batch + 3;
-    a.stats = (unsigned long long*)(ib + 8 * batch + 4);  // (8 * batch + 4 ints: 8-byte aligned for even batch; checked below)
-    if (((uintptr_t)a.stats & 7) != 0) a.stats = (unsigned long long*)(ib + 8 * batch + 5);
+    a.skipS = ib + 5 * batch; a.ident = ib + 6 * batch; a.lu_list = ib + 7 * batch; a.lu_cnt = ib + 8 * batch; a.summary = ib + 8 * batch + 2; a.lu_wait = ib + 8 * batch + 4;
+    a.lu_redo = (n <= LU_MAX_N && !kry && !c->band) ? c->lu_redo : nullptr;  // (n > 1024: the round is the one it was; the SLOW launches, where there are any, keep a wave per system)
+    a.host_mail = nullptr; a.mail_seq = 0;
+    if (lu_cnt_mail) IDAHIP_HIP(c, hipHostGetDevicePointer((void**)&a.host_mail, c->rnd_mail, 0));
+    a.stats = (unsigned long long*)(ib + 8 * batch + 6);  // (8 * batch + 6 ints: 8-byte aligned for even batch; checked below)
+    if (((uintptr_t)a.stats & 7) != 0) a.stats = (unsigned long long*)(ib + 8 * batch + 7);
     IDAHIP_HIP(c, hipMemsetAsync(a.stats, 0, IDAHIP_K_COUNT * sizeof(unsigned long long), c->stream));
     a.lu_info = c->lu_info;
     a.tn = c->rnd_d; a.cj = c->rnd_d + batch; a.scale = c->rnd_d + 2 * batch; a.nrm_out = c->rnd_d + 3 * batch;
@@ -2730,20 +2781,27 @@ int idahip_round_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip
         if (call->max_rounds > 0 && r >= call->max_rounds) break;
         a.round = r;
         a.first_round = r == 0;
+        if (a.host_mail) a.mail_seq = ++c->rnd_mail_seq;  // (what round_lists_kernel posts last and direct_round_setup waits for)
         {
             KTimer kt(c, IDAHIP_K_VECTOR, 0);
             auto kern = call->nroots > 0 ? (tstop ? round_begin_kernel<true, true> : round_begin_kernel<true, false>)
                                          : (tstop ? round_begin_kernel<false, true> : round_begin_kernel<false, false>);
             hipLaunchKernelGGL(kern, dim3(batch), dim3(WG_NT), shm_wg, c->stream, a);
             // (a Krylov ctx without the preconditioner factors nothing: no list)
-            if (!kry || c->kry_prec) hipLaunchKernelGGL(round_lists_kernel, dim3(1), dim3(1024), 0, c->stream, a);
+            if (!kry || c->kry_prec) {
+                if (a.lu_redo) hipLaunchKernelGGL(round_lists_kernel<true>, dim3(1), dim3(1024), 0, c->stream, a);
+                else hipLaunchKernelGGL(round_lists_kernel<false>, dim3(1), dim3(1024), 0, c->stream, a);
+            }
         }
         // n > 1024 (config 4): a factorisation is ~640 launches, most of them one workgroup per matrix, and a third of a small
         // batch needs one in any round -- launches sized for the whole batch cost more than they do at n = 512 (11.4 against
         // 12.3 k iters/s in round 4). The list's length comes back to the host (4 bytes, behind the residual kernels enqueued
         // next: the copy's round trip is hidden) and the LU's launches are sized by it, as the host stepper's are.
-        const bool lu_cnt_on_host = !kry && n > LU_MAX_N && !c->band;  // (the band LU is one launch: its surplus lanes leave on reading the count)
-        if (lu_cnt_on_host) {
+        // n <= 1024: the host sizes the launches too (idahip_set_lu_count_on_host), but round_lists_kernel posts
+        // the count to pinned memory itself (RoundArgs::host_mail): no copy and no event in the stream. Either way the last
+        // factorisation's largest redo count rides along and sizes the SLOW panel launches.
+        // (the band LU is one launch: its surplus lanes leave on reading the count)
+        if (lu_cnt_on_host && !lu_cnt_mail) {
             IDAHIP_HIP(c, hipMemcpyAsync(c->rnd_host + 2, a.lu_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
             IDAHIP_HIP(c, hipEventRecord(c->ev_cnt, c->stream));
         }
@@ -2802,6 +2860,17 @@ int idahip_set_lu_period(idahip_ctx* c, int rounds) {
     return 0;
 }
 int idahip_lu_period(const idahip_ctx* c) { return c ? c->lu_period : -1; }
+int idahip_set_lu_count_on_host(idahip_ctx* c, int on) {
+    if (!c || on < -1 || on > 1) return -1;
+    c->lu_count_on_host = on;
+    return 0;
+}
+int idahip_lu_count_on_host(const idahip_ctx* c) { return c ? (lu_count_on_host_on(c) ? 1 : 0) : -1; }
+int idahip_set_lu_slow_grid(idahip_ctx* c, int workgroups) {
+    if (!c || workgroups < 0) return -1;
+    c->lu_slow_grid = workgroups;
+    return 0;
+}
 
 // LSolver::get_type / num_iters / res_norm of the dense direct solver (crates/linear/src/dense.rs:30-36, traits.rs:82-90)
 int idahip_ls_type(const idahip_ctx* c) { return c ? (c->krylov ? IDAHIP_LS_ITERATIVE : IDAHIP_LS_DIRECT) : -1; }

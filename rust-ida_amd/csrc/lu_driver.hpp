@@ -15,12 +15,14 @@ namespace idahip {
 // surplus workgroups leave on reading it.
 // jq (optional; lu_jac_eligible): the matrices are J = B + cj*A of a linear dense ctx and `work` does NOT hold them: the first
 // super-panel's launches and the first trailing launch form J from A and B as they load (LuJac, lu_kernels.hpp).
+// slow_grid: workgroups of the wave-per-matrix panels' SLOW launches, which walk their redo list grid-stride; 0 = what
+// idahip_set_lu_slow_grid says, else one per listed system.
 
 // J can be formed inside the factorisation on the wave-per-matrix pipeline alone: TINY_N < n <= WP_MAX_ROWS, LU variant 4
 inline bool lu_jac_eligible(const idahip_ctx* c) { return c->n > TINY_N && c->n <= WP_MAX_ROWS && c->lu_variant >= 4; }
 
 inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* out, long ostride, long long* piv, long pstride,
-                             int* perm, const int* d_idx, int nsys, const int* d_cnt = nullptr, const LuJac* jq = nullptr) {
+                             int* perm, const int* d_idx, int nsys, const int* d_cnt = nullptr, const LuJac* jq = nullptr, int slow_grid = 0) {
     const int n = c->n;
     if (nsys == 0) return 0;
     if (jq && !lu_jac_eligible(c)) return fail(c, -3, "J = B + cj*A inside the LU needs %d < n <= %d and LU variant 4", TINY_N, WP_MAX_ROWS);
@@ -34,7 +36,7 @@ inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* 
     if (d_cnt && c->lu_variant < 4) return fail(c, -3, "a device-side list length needs LU variant 4");
     LuWs w;
     w.mats = work; w.mstride = wstride; w.idx = d_idx; w.cnt = d_cnt; w.n = n;
-    w.pos = c->lu_pos; w.live = c->lu_live; w.prow = c->lu_prow; w.piv = piv; w.pstride = pstride; w.info = c->lu_info; w.redo = c->lu_redo; w.nzb = c->lu_nzb; w.bz = c->lu_bz;
+    w.pos = c->lu_pos; w.live = c->lu_live; w.prow = c->lu_prow; w.piv = piv; w.pstride = pstride; w.info = c->lu_info; w.redo = c->lu_redo ? c->lu_redo + LU_REDO_SLOTS : nullptr; w.nzb = c->lu_nzb; w.bz = c->lu_bz;
     w.zmap = (out == c->lu) ? c->lu_zmap : nullptr;  // the map describes the ctx's own factors (the Newton iteration's solves)
     w.dirty = (out == c->lu) ? c->lu_dirty : nullptr;  // (nothing else ever writes the ctx's own factors for n >= 2048)
     // the work matrix left all +0.0 for the next Jacobian (stencil_jac_kernel): only where every super-panel is 64 columns wide -- the
@@ -43,7 +45,11 @@ inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* 
     if (!w.jwzero && c->lu_jwzero && (work == c->jw || out == c->jw))  // the work matrix is about to hold something this flag does not describe
         (void)hipMemsetAsync(c->lu_jwzero, 0, (size_t)c->batch * sizeof(int), c->stream);
     w.l11 = c->lu_l11; w.stamps = c->dbg_stamps; w.out = out; w.ostride = ostride; w.l11ld = 64;
-    hipLaunchKernelGGL(lu_init_kernel, dim3(nsys), dim3(256), 0, c->stream, w);
+    if (slow_grid <= 0) slow_grid = c->lu_slow_grid;  // (idahip_set_lu_slow_grid holds for every caller)
+    const int nslow = slow_grid > 0 ? std::min(slow_grid, nsys) : nsys;
+    // (every super-panel of a multiple of 64 rows above 1024 on the super-panel pipeline is lu_superpanel_kernel's: no wave-per-matrix launch)
+    if (c->lu_variant >= 4 && !(c->lu_superpanel && n > LU_MAX_N && n % 64 == 0)) hipLaunchKernelGGL(lu_init_kernel<true>, dim3(nsys), dim3(256), 0, c->stream, w);
+    else hipLaunchKernelGGL(lu_init_kernel<false>, dim3(nsys), dim3(256), 0, c->stream, w);
     const int nsys8 = ((nsys + 7) / 8) * 8;
     constexpr int NB = LU_NB;
     auto panel2 = [&](int k0, int lbase) {  // two live rows per lane
@@ -107,7 +113,7 @@ inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* 
         } else if (c->lu_variant >= 4 && n - k0 <= WP_MAX_ROWS) {
             KTimer kt(c, IDAHIP_K_LU_PANEL, nsys);
             // one wave per matrix factors the whole 64-column super-panel (lu_wavepanel.hpp); the second launch finishes
-            // the few systems whose matrices have exact zeros or special values (it returns at once for the others)
+            // the few systems whose matrices have exact zeros or special values (the FAST launch lists them; nslow workgroups walk the list)
             const int ns = (n - k0 + 63) / 64;
 #define IDAHIP_WP_LAUNCH(NSV) \
     hipLaunchKernelGGL((lu_wavepanel_kernel<false, NSV>), dim3(nsys), dim3(64), 0, c->stream, w, k0)
@@ -128,10 +134,10 @@ inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* 
                 // that reads the count from the matrix size -- eight slots' registers and loads whatever the count, not measured
                 if (ns == 8) hipLaunchKernelGGL((lu_wavepanel_kernel<false, 8, LuJac>), dim3(nsys), dim3(64), 0, c->stream, w, k0, *jq);
                 else hipLaunchKernelGGL((lu_wavepanel_kernel<false, 0, LuJac>), dim3(nsys), dim3(64), 0, c->stream, w, k0, *jq);
-                hipLaunchKernelGGL((lu_wavepanel_kernel<true, 0, LuJac>), dim3(nsys), dim3(64), 0, c->stream, w, k0, *jq);
+                hipLaunchKernelGGL((lu_wavepanel_kernel<true, 0, LuJac>), dim3(nslow), dim3(64), 0, c->stream, w, k0, *jq);
             } else {
                 IDAHIP_WP_SWITCH()
-                hipLaunchKernelGGL((lu_wavepanel_kernel<true, 0>), dim3(nsys), dim3(64), 0, c->stream, w, k0);
+                hipLaunchKernelGGL((lu_wavepanel_kernel<true, 0>), dim3(nslow), dim3(64), 0, c->stream, w, k0);
             }
 #undef IDAHIP_WP_SWITCH
 #undef IDAHIP_WP_LAUNCH

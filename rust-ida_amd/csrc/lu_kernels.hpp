@@ -52,7 +52,11 @@ struct LuWs {
     int* jwzero;       // null, or [batch] (with dirty, work == the ctx's work matrix, every super-panel 64 columns wide): 1 = the factorisation has left the
                        // work matrix all +0.0 (lu_finalize_kernel clears what it reads and the pivot rows' entries right of their super-panel); stencil_jac_kernel
                        // then writes the band only. lu_init_kernel resets it, lu_finalize_kernel sets it.
-    int* redo;         // [batch]   lu_wavepanel_kernel: 0 | 1 + first 8-column block of the super-panel left to its SLOW launch
+    int* redo;         // lu_wavepanel_kernel, one allocation of LU_REDO_SLOTS + 2 * batch ints behind one pointer:
+                       //   redo[2 * b]      system b: 0 | 1 + first 8-column block of the super-panel left to its SLOW launch
+                       //   redo[2 * i + 1]  entry i of the list of matrices (list positions) the current super-panel's FAST launch handed over
+                       //                    (one list, rewritten by every super-panel: its SLOW launch has read it by then)
+                       //   redo[sp - LU_REDO_SLOTS]  the list's length for super-panel sp = k0 / 64 (the ints in front of the pointer)
     double* l11;       // [batch][L11_STRIDE] transposed L11: l11[kk*l11ld + k] = multiplier of the k-th pivot row for column kk
     int l11ld;         // row length of l11: the (super-)panel width, 32 or 64
     unsigned long long* stamps;  // timing builds (-DIDAHIP_STAMPS): time stamps of one launch, null otherwise
@@ -60,6 +64,7 @@ struct LuWs {
     long ostride;      // elements between consecutive systems in out
 };
 constexpr int L11_STRIDE = 64 * 64;  // elements per system in LuWs::l11
+constexpr int LU_REDO_SLOTS = LU_BIG_MAX_N / 64;  // counters in front of LuWs::redo, one per super-panel
 
 // The Newton matrix of a linear dense ctx, J = B + cj*A, formed by the factorisation's first launches as they load (k0 == 0:
 // lu_wavepanel_kernel<.., LuJac>, lu_trail64w_kernel<1024, LuJac>; idahip_set_jac_in_lu) -- J then never passes through memory. Multiply, then add,
@@ -74,7 +79,10 @@ struct LuJac {
 __host__ __device__ __forceinline__ LuJac lu_jac_arg() { return LuJac{nullptr, nullptr, nullptr, 0}; }
 __host__ __device__ __forceinline__ LuJac lu_jac_arg(const LuJac& j) { return j; }
 
+// REDO: the factorisation has wave-per-matrix panel launches (lu_wavepanel_kernel): their redo counters start at zero
+template <bool REDO>
 __global__ void lu_init_kernel(LuWs w) {
+    if (REDO && blockIdx.x == 0 && threadIdx.x < LU_REDO_SLOTS) w.redo[(int)threadIdx.x - LU_REDO_SLOTS] = 0;  // (before the count is read: the counters never describe an older call)
     if (w.cnt && (int)blockIdx.x >= *w.cnt) return;
     const int b = w.idx[blockIdx.x];
     for (int i = threadIdx.x; i < w.n; i += blockDim.x) {

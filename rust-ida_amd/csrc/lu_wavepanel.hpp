@@ -45,13 +45,24 @@ constexpr int WP_RING(int ns) { return !tb::WP_DEEP_RING ? 2 : (ns >= 1 && ns <=
 // and linear_jac_kernel. The blocks are stored to the work matrix as ever, so the multiplier re-reads of the left-looking loop, the
 // SLOW launch's replay and the transposed L11 find there what they always found.
 // (The J-forming instantiations carry one more kernel argument, the pack J = {LuJac}; the plain ones have the signature they always had.)
+//
+// FAST (SLOWK = false): workgroup i takes list position i; with the list's length on the device the surplus ones leave on reading it.
+// SLOW: the launch walks the redo list its FAST launch has just written (LuWs::redo), grid-stride -- any grid is correct, and a
+// super-panel that handed nothing over costs one read of the counter per workgroup. Per-matrix work does not depend on the order.
+// (One body for both: the FAST instantiations run it once and leave by `return` where the SLOW one goes on to its next entry.)
 template <bool SLOWK, int NS, class... J>
 __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void lu_wavepanel_kernel(LuWs w, const int k0, const J... jarg) {
     constexpr bool JAC = sizeof...(J) == 1;
     constexpr int BIG = 1 << 20;  // pstep of a row that is still live
-    if (w.cnt && (int)blockIdx.x >= *w.cnt) return;
-    const int b = w.idx[blockIdx.x];
-    if (w.info[b] != 0) return;
+    if (!SLOWK && w.cnt && (int)blockIdx.x >= *w.cnt) return;
+    const int nredo = SLOWK ? w.redo[(k0 >> 6) - LU_REDO_SLOTS] : 0;
+  for (int it = blockIdx.x; !SLOWK || it < nredo; it += gridDim.x) {
+    const int item = SLOWK ? w.redo[2 * it + 1] : (int)blockIdx.x;
+    const int b = w.idx[item];
+    if (w.info[b] != 0) {
+        if constexpr (SLOWK) continue;
+        else return;
+    }
     const int n = w.n;
     double* __restrict__ A = w.mats + (long)b * w.mstride;
     int* __restrict__ pos = w.pos + (long)b * n;
@@ -94,7 +105,7 @@ __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void l
     double jcj = 0.0;
     __amdgpu_buffer_rsrc_t rsJa = rsrc, rsJb = rsrc;
     if constexpr (JAC) {
-        jcj = jq.cj[jq.cj_by_sys ? b : (int)blockIdx.x];
+        jcj = jq.cj[jq.cj_by_sys ? b : item];
         rsJa = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(jq.a) + (long)b * n * n, 0, n * n * 8, 0x00020000);
         rsJb = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(jq.b) + (long)b * n * n, 0, n * n * 8, 0x00020000);
     }
@@ -395,8 +406,8 @@ __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void l
     int bstart = 0;
     if (SLOWK) {
         // this launch only finishes the systems the FAST launch handed over: redo = 1 + first block to be done in SLOW mode
-        const int rd = w.redo[b];
-        if (rd == 0) return;
+        const int rd = w.redo[2 * b];
+        if (rd == 0) continue;
         bstart = (rd - 1) * 8;
         // replay the pivots of the blocks the FAST launch completed (positions, pivot steps, owner table)
         for (int k = 0; k < bstart; ++k) {
@@ -416,8 +427,9 @@ __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void l
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
-        if (lane == 0) w.redo[b] = 0;
+        if (lane == 0) w.redo[2 * b] = 0;
     }
+    bool zero_pivot = false;
     for (int b8 = bstart; b8 < wsp; b8 += 8) {
         const int wb = (wsp - b8) < 8 ? (wsp - b8) : 8;
         double x[8][8];
@@ -433,13 +445,24 @@ __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void l
                 st = process(std::false_type{}, x, b8, 8);
             }
             if (st == 2) {  // hand the rest of this super-panel to the SLOW launch; nothing of this block has been stored
-                if (lane == 0) w.redo[b] = 1 + (b8 >> 3);
+                if (lane == 0) {
+                    w.redo[2 * b] = 1 + (b8 >> 3);
+                    w.redo[2 * atomicAdd(&w.redo[(k0 >> 6) - LU_REDO_SLOTS], 1) + 1] = item;  // the SLOW launch's list: any order serves
+                }
                 return;
             }
         }
-        if (st != 0) return;
+        if (st != 0) {  // a zero pivot (info is set): nothing more for this matrix
+            if constexpr (SLOWK) {
+                zero_pivot = true;
+                break;
+            } else {
+                return;
+            }
+        }
         store_block(x, b8, wb);
     }
+    if (SLOWK && zero_pivot) continue;
 
     // ---- positions, transposed L11 (multipliers of the pivot rows, read back from the matrix), compacted live list
     __syncthreads();  // the stores above (work matrix, prow) are visible to every lane of the wave
@@ -466,6 +489,8 @@ __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void l
         if (al) live[base + __popcll(bal & ((1ull << lane) - 1ull))] = rowid[S];
         base += __popcll(bal);
     });
+    if constexpr (!SLOWK) return;
+  }
 }
 
 }  // namespace idahip

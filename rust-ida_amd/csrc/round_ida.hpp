@@ -50,7 +50,10 @@ struct RoundArgs {
     int* skipS;             // residual kernel inside the iteration passes
     int* ident;             // 0, 1, 2, ...: the kernels' index list
     int* lu_list;           // systems to factor
-    int* lu_cnt;            // [1]
+    int* lu_cnt;            // [2]: the list's length; the largest redo count of the last factorisation's super-panels (for the host: the two travel together)
+    const int* lu_redo;     // [LU_REDO_SLOTS] the panels' redo counters (the ints in front of LuWs::redo), or null: n > 1024 or a ctx without the dense LU
+    int* host_mail;         // null, or pinned host memory [3]: round_lists_kernel posts lu_cnt[0], lu_cnt[1] and then mail_seq there, for a host
+    int mail_seq;           // that sizes the round's LU launches (n <= 1024: no copy and no event in the stream, the host polls the third word)
     int* lu_wait;           // [1] rounds in a row that have postponed their setups
     const int* lu_info;     // [batch] zero-pivot flags of the last factorisation
     double* tn;             // [batch] arguments of the residual kernels
@@ -211,11 +214,28 @@ __global__ __launch_bounds__(WG_NT) void round_begin_kernel(RoundArgs a) {
 // whose Newton solve starts over with a setup (newton_retry; call_lsetup is set either way: round_begin_kernel) -- and ask again
 // next round, while the others go on stepping. Which round a system's attempt runs in is the scheduler's business: its
 // arithmetic, its counters and its results do not change (tests/test_gpu_device_controller.py).
+__device__ __forceinline__ void round_post_count(const RoundArgs& a, int cnt, int redo) {
+    if (!a.host_mail) return;
+    a.host_mail[0] = cnt;
+    a.host_mail[1] = redo;
+    __threadfence_system();
+    __hip_atomic_store(&a.host_mail[2], a.mail_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// REDO: the round's LU launches are sized on the host from what this kernel posts (n <= 1024, idahip_set_lu_count_on_host), the last
+// factorisation's largest redo count with it; without it the kernel is the one it was.
+template <bool REDO>
 __global__ __launch_bounds__(1024) void round_lists_kernel(RoundArgs a) {
     __shared__ int s_wave[16], s_wave2[16];
     __shared__ int s_base, s_hold;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (t == 0) { s_base = 0; s_hold = 0; }
+    int redo = 0;
+    if (REDO && wave == 0) {  // what the SLOW launches of the last factorisation found to do, at most: sizes this round's (idahip_round_solve)
+        redo = (a.lu_redo && lane < LU_REDO_SLOTS) ? a.lu_redo[lane] : 0;
+        for (int o = 32; o > 0; o >>= 1) redo = max(redo, __shfl_xor(redo, o));
+        if (lane == 0) a.lu_cnt[1] = redo;
+    }
     __syncthreads();
     if (a.lu_period > 1) {
         int want = 0, step = 0;
@@ -246,7 +266,10 @@ __global__ __launch_bounds__(1024) void round_lists_kernel(RoundArgs a) {
                     a.skipL[b] = 1;
                     a.rounds_done[b] -= 1;
                 }
-            if (t == 0) a.lu_cnt[0] = 0;
+            if (t == 0) {
+                a.lu_cnt[0] = 0;
+                if (REDO) round_post_count(a, 0, redo);
+            }
             return;
         }
         __syncthreads();
@@ -282,6 +305,7 @@ __global__ __launch_bounds__(1024) void round_lists_kernel(RoundArgs a) {
             }
             atomicAdd(&a.stats[IDAHIP_K_LU], cnt);
         }
+        if (REDO) round_post_count(a, s_base, redo);
     }
 }
 

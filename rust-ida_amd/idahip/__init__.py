@@ -40,7 +40,7 @@ HIP_SYMBOLS = [
     "idahip_predict", "idahip_post_newton", "idahip_restore", "idahip_complete_step", "idahip_get_solution", "idahip_get_dky",
     "idahip_timing_enable", "idahip_timing_get", "idahip_timing_reset", "idahip_set_lu_variant", "idahip_set_jac_in_lu", "idahip_jac_in_lu", "idahip_snapshot_initial",
     "idahip_tiny_solve", "idahip_pow_batch", "idahip_round_solve", "idahip_lu_variant",
-    "idahip_restore_initial", "idahip_ls_type", "idahip_ls_num_iters", "idahip_ls_res_norm", "idahip_timing_build", "idahip_concurrent_streams", "idahip_release_streams", "idahip_stream_pair_share", "idahip_set_lu_superpanel", "idahip_lu_superpanel", "idahip_set_lu_period", "idahip_lu_period",
+    "idahip_restore_initial", "idahip_ls_type", "idahip_ls_num_iters", "idahip_ls_res_norm", "idahip_timing_build", "idahip_concurrent_streams", "idahip_release_streams", "idahip_stream_pair_share", "idahip_set_lu_superpanel", "idahip_lu_superpanel", "idahip_set_lu_period", "idahip_lu_period", "idahip_set_lu_count_on_host", "idahip_lu_count_on_host", "idahip_set_lu_slow_grid",
     "idahip_create_band", "idahip_band", "idahip_set_host_band_problem", "idahip_download_lu_band", "idahip_ls_setup_band", "idahip_ls_solve_band",
     "idahip_set_jacobian_dq", "idahip_jacobian_dq", "idahip_set_host_residual", "idahip_jac_dq", "idahip_nls_lsetup_dq",
     "idahip_set_id", "idahip_id", "idahip_ic_begin", "idahip_ic_reset", "idahip_ic_res", "idahip_ic_setup", "idahip_ic_setup_dq",
@@ -112,6 +112,9 @@ def load():
     H.idahip_lu_superpanel.argtypes = [vp]
     H.idahip_set_lu_period.argtypes = [vp, ci]
     H.idahip_lu_period.argtypes = [vp]
+    H.idahip_set_lu_count_on_host.argtypes = [vp, ci]
+    H.idahip_lu_count_on_host.argtypes = [vp]
+    H.idahip_set_lu_slow_grid.argtypes = [vp, ci]
     H.idahip_last_error.argtypes = [vp]
     H.idahip_last_error.restype = C.c_char_p
     H.idahip_sync.argtypes = [vp]
@@ -855,6 +858,20 @@ class Ctx:
 
     def lu_period(self):
         return int(self.H.idahip_lu_period(self.h))
+
+    def set_lu_count_on_host(self, on=-1):
+        """Device lock-step stepper, dense direct ctx, n <= 1024: 1 = the length of a round's LU list comes back to the host and sizes
+        the round's LU launches exactly (a round without setups launches none), 0 = launches sized for the batch whose surplus
+        workgroups leave on reading the count, -1 = the library's choice. Results unchanged."""
+        self._chk(self.H.idahip_set_lu_count_on_host(self.h, int(on)), "set_lu_count_on_host")
+
+    def lu_count_on_host(self):
+        return int(self._chk(self.H.idahip_lu_count_on_host(self.h), "lu_count_on_host"))
+
+    def set_lu_slow_grid(self, workgroups=0):
+        """Workgroups of the panels' SLOW launches (they walk the list of matrices with zeros or special values grid-stride: any
+        number is correct); 0 = automatic."""
+        self._chk(self.H.idahip_set_lu_slow_grid(self.h, int(workgroups)), "set_lu_slow_grid")
 
     def set_lu_variant(self, variant):
         self._chk(self.H.idahip_set_lu_variant(self.h, int(variant)), "set_lu_variant")
