@@ -614,6 +614,29 @@ int idahip_set_jac_in_lu(idahip_ctx* ctx, int on);
 /* What is in effect now: 0 = outside everywhere; 1 = inside in idahip_round_solve alone (never set, n > 448); 2 = inside in
  * idahip_round_solve, idahip_nls_lsetup and idahip_nls_sys_setup (set to 1). */
 int idahip_jac_in_lu(const idahip_ctx* ctx);
+/* Dense direct ctx, 8 < n <= 512, LU variant 4: the layout of the ctx's OWN factors (what idahip_nls_lsetup, idahip_nls_sys_setup,
+ * idahip_round_solve and the initial-condition setups write and idahip_newton_iter and the initial-condition solves read).
+ *   staged (1): below the diagonal block of every 64-column block column the rows of L stand in the order the factorisation's
+ *               list of not-yet-pivoted rows had when the block column's super-panel was done, not in final pivot order; a map per
+ *               system and super-panel says where each row went, and a solve permutes its right-hand side in LDS block by block
+ *               with it. The factorisation then ends without its pass that scatters rows to their pivot positions.
+ *   reference (0): every row at its pivot position (dgetrf's layout), written by that pass.
+ * Pivots, Newton iterations, norms and every result are bit-identical either way: each entry of a right-hand side receives the
+ * same updates in the same order. Never set: staged where 448 < n <= 512 (the size it was measured at), the reference layout
+ * below; 1: staged at every eligible n; 0: the reference layout.
+ * The setting describes the factors the ctx holds: after changing it (or the LU variant) every system is set up again before its
+ * next solve. Turning it on is refused (-2) on a ctx that is not eligible (band, Krylov, n outside the range); with LU variant 3
+ * the setting is kept and the reference layout used while that lasts.
+ * idahip_download_lu returns the REFERENCE layout under either setting (the maps are composed on the host). Caller-supplied
+ * matrices (idahip_ls_setup / idahip_ls_solve) are always in the reference layout; the ctx's own factors cannot reach
+ * idahip_ls_solve, since no call hands out their address.
+ * A system whose setup fails (info != 0): in the reference layout its previous factors stay whole (the scatter skips it); staged,
+ * the launches that ran before the zero pivot was found have already overwritten part of its factors, maps and permutation, and
+ * idahip_download_lu returns a mixture. Either way the system has no valid factors until a setup of it succeeds, and the steppers
+ * set it up again before they solve with it. */
+int idahip_set_lu_staged(idahip_ctx* ctx, int on);
+/* 1 = the ctx's own factors are written and read staged now, 0 = in the reference layout. */
+int idahip_lu_staged(const idahip_ctx* ctx);
 /* Matrices with more than 1024 rows: how a 64-column super-panel is factored. 1 = in one launch of the left-looking
  * workgroup-per-matrix kernel (lu_superpanel_kernel): the faster pipeline for BANDED matrices in dense storage (config 4's heat
  * Jacobians: 238 against 322 us per 4096 x 4096 matrix) and the default for IDAHIP_HEAT1D and IDAHIP_BRUSS1D; 0 = eight 8-column panel launches with a

@@ -111,6 +111,11 @@ struct idahip_ctx {
     // (LuJac, lu_kernels.hpp) instead of in the residual sweep; in effect only where jac_in_lu_on (idahip.hip) says the ctx is eligible.
     // -1 = never set: on in idahip_round_solve where n > 448, off in the list entry points; 0 / 1 = set by the caller, for both
     int jac_in_lu = -1;
+    // idahip_set_lu_staged: `lu` keeps L21 of every super-panel in the order of the live list behind it and the solves permute their
+    // right-hand side block by block with the maps in lu_ord (LuWs::ord) -- no lu_finalize_kernel. In effect where lu_staged_on
+    // (lu_driver.hpp) says so: 8 < n <= 512, LU variant 4. -1 = never set (on where n > 448), 0 / 1 = set by the caller.
+    int lu_staged = -1;
+    uint16_t* lu_ord = nullptr;  // [batch][ceil(n / 64)][n], allocated for 8 < n <= 512
     int lu_variant = 4;  // 4: one wave per matrix factors each 64-column super-panel (lu_wavepanel.hpp, default)
     // n > 1024: 1 = a 64-column super-panel is ONE launch of lu_superpanel_kernel (left-looking; made for banded matrices in dense
     // storage, where it is 26 % faster: config 4), 0 = round 4's eight 8-column panel launches with a narrow update after each,

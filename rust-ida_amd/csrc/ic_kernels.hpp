@@ -29,8 +29,8 @@ namespace idahip {
 template <int VEC>
 __global__ __launch_bounds__(256) void ic_solve_kernel(const double* __restrict__ LU, const int* __restrict__ perm, double* x,
                                                        const double* __restrict__ ewt, int n, const int* __restrict__ idx,
-                                                       double* __restrict__ out) {
-    ic_solve_body<VEC>(LU, perm, x, ewt, n, idx[blockIdx.x], out);
+                                                       double* __restrict__ out, const unsigned short* __restrict__ ord /* or null */) {
+    ic_solve_body<VEC>(LU, perm, x, ewt, n, idx[blockIdx.x], out, ord);
 }
 
 __global__ void ic_tiny_solve_kernel(const double* LU, const long long* piv, double* x, const double* ewt, int n, const int* idx,

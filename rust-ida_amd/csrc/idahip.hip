@@ -256,6 +256,7 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
         rc |= dalloc(c, &c->jw, bnn);
         rc |= dalloc(c, &c->lu_pos, bn); rc |= dalloc(c, &c->lu_live, bn); rc |= dalloc(c, &c->lu_prow, bn);
         rc |= dalloc(c, &c->lu_l11, (size_t)batch * L11_STRIDE);
+        if (n <= WP_MAX_ROWS) rc |= dalloc(c, &c->lu_ord, (size_t)batch * ((n + 63) / 64) * n);  // staged L: LuWs::ord
     }
     if (krylov_maxl > 0) {
         idakry::Sys* st = nullptr;
@@ -293,6 +294,7 @@ int create_ctx(idahip_ctx** out, int device, int n, int batch, idahip_problem ki
     // pivots and row permutation in range before the first setup: a Newton iteration or solve ahead of it gathers rows by them
     if (c->piv) (void)hipMemsetAsync(c->piv, 0, bn * sizeof(int64_t), c->stream);
     if (c->perm) (void)hipMemsetAsync(c->perm, 0, bn * sizeof(int32_t), c->stream);
+    if (c->lu_ord) (void)hipMemsetAsync(c->lu_ord, 0, (size_t)batch * ((n + 63) / 64) * n * sizeof(uint16_t), c->stream);  // (and the staged solve's maps)
     if (c->lu_redo) (void)hipMemsetAsync(c->lu_redo, 0, ((size_t)LU_REDO_SLOTS + 2 * (size_t)batch) * sizeof(int), c->stream);
     if (c->bab) (void)hipMemsetAsync(c->bab, 0, bn * c->ldab * sizeof(double), c->stream);
     if (c->lu_dirty) {  // the factors start as zeros, and so does the map of their blocks that have ever held anything else
@@ -346,7 +348,7 @@ int idahip_destroy(idahip_ctx* c) {
     if (!c) return 0;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->kry_rcnt, c->kry_rint, c->kry_rres, c->kry_pab, c->kry_ppiv, c->kry_V, c->kry_st, c->kry_stage, c->kry_b, c->kry_x, c->dq_stage, c->dq_out, c->dq_hh, c->yy, c->yp, c->yypredict, c->yppredict, c->ewt, c->ee, c->delta, c->savres, c->phi, c->lu, c->jw, c->piv, c->perm,
-                    c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->d_constr, c->ic_y,
+                    c->lu_pos, c->lu_live, c->lu_prow, c->lu_info, c->lu_redo, c->lu_nzb, c->lu_bz, c->lu_zmap, c->lu_dirty, c->lu_jwzero, c->lu_l11, c->lu_ord, c->params, c->A, c->B, c->C, c->d_atol_v, c->d_id, c->d_constr, c->ic_y,
                     c->ic_yp, c->reinit_stage, c->bab, c->dky, c->cb_stage, c->tiny_sys, c->tiny_touts, c->tiny_yout, c->tiny_ypout, c->tiny_start, c->tiny_rounds,
                     c->tiny_acc, c->tiny_roots, c->rnd_i, c->rnd_d, c->ma_blob};
     for (void* p : ptrs)
@@ -856,6 +858,29 @@ int idahip_download_lu(idahip_ctx* c, int sys, double* hLU, int64_t* hPiv) {
     const size_t nn = (size_t)c->n * c->n;
     if (hLU) IDAHIP_HIP(c, hipMemcpy(hLU, c->lu + sys * nn, sizeof(double) * nn, hipMemcpyDeviceToHost));
     if (hPiv) IDAHIP_HIP(c, hipMemcpy(hPiv, c->piv + (size_t)sys * c->n, sizeof(int64_t) * c->n, hipMemcpyDeviceToHost));
+    if (hLU && lu_staged_on(c)) {
+        // staged L: rows >= k0 + 64 of block column q stand in the order of the live list behind super-panel q. Composing the maps of
+        // the super-panels after it gives every such row its pivot position; the caller receives the reference layout as ever.
+        const int n = c->n, nq = (n + 63) / 64;
+        std::vector<uint16_t> ord((size_t)nq * n);
+        IDAHIP_HIP(c, hipMemcpy(ord.data(), c->lu_ord + (size_t)sys * nq * n, sizeof(uint16_t) * ord.size(), hipMemcpyDeviceToHost));
+        std::vector<int> fin(n), nxt(n);  // fin[i]: pivot position of entry i of the live list behind super-panel q
+        std::vector<double> col(n);
+        for (int q = nq - 2; q >= 0; --q) {
+            const int k1 = (q + 1) * 64, m1 = n - k1;  // the next super-panel's first column and live rows
+            for (int i = 0; i < m1; ++i) {
+                const int o = ord[(size_t)(q + 1) * n + i];
+                nxt[i] = o < 64 ? k1 + o : (o - 64 < m1 - 64 ? fin[o - 64] : k1);  // (a map never written -- no factorisation yet -- stays inside the matrix)
+            }
+            std::swap(fin, nxt);
+            for (int j = q * 64; j < k1; ++j) {
+                double* cj = hLU + (size_t)j * n;
+                for (int i = 0; i < m1; ++i) col[i] = cj[k1 + i];
+                for (int i = 0; i < m1; ++i)
+                    if (fin[i] < n) cj[fin[i]] = col[i];
+            }
+        }
+    }
     return 0;
 }
 
@@ -1488,13 +1513,20 @@ static int launch_newton_iter(idahip_ctx* c, const int* d_idx, const double* d_s
                            (const long long*)c->piv, c->delta, c->ee, (const double*)c->ewt, n, d_idx, nsys, d_scale, d_out, d_skip);
     } else if (n % 2 == 0 && n >= 2048) {
         hipLaunchKernelGGL((newton_iter_kernel<2, 1024>), dim3(nsys), dim3(1024), sizeof(double) * (n + (n > 4096 ? n : 4096)), c->stream, (const double*)c->lu,
-                           (const int*)c->perm, c->delta, c->ee, (const double*)c->ewt, n, d_idx, d_scale, d_out, d_skip, (const unsigned char*)c->lu_zmap);
+                           (const int*)c->perm, c->delta, c->ee, (const double*)c->ewt, n, d_idx, d_scale, d_out, d_skip, (const unsigned char*)c->lu_zmap, (const unsigned short*)nullptr);
+    } else if (lu_staged_on(c)) {  // the ctx's factors are staged (lu_driver.hpp): no gather through perm, the maps instead
+        if (n % 2 == 0)
+            hipLaunchKernelGGL((newton_iter_kernel<2, 256, true>), dim3(nsys), dim3(256), 2 * sizeof(double) * n, c->stream, (const double*)c->lu,
+                               (const int*)c->perm, c->delta, c->ee, (const double*)c->ewt, n, d_idx, d_scale, d_out, d_skip, (const unsigned char*)nullptr, (const unsigned short*)c->lu_ord);
+        else
+            hipLaunchKernelGGL((newton_iter_kernel<1, 256, true>), dim3(nsys), dim3(256), 2 * sizeof(double) * n, c->stream, (const double*)c->lu,
+                               (const int*)c->perm, c->delta, c->ee, (const double*)c->ewt, n, d_idx, d_scale, d_out, d_skip, (const unsigned char*)nullptr, (const unsigned short*)c->lu_ord);
     } else if (n % 2 == 0) {
         hipLaunchKernelGGL(newton_iter_kernel<2>, dim3(nsys), dim3(256), 2 * sizeof(double) * n, c->stream, (const double*)c->lu,
-                           (const int*)c->perm, c->delta, c->ee, (const double*)c->ewt, n, d_idx, d_scale, d_out, d_skip, (const unsigned char*)nullptr);
+                           (const int*)c->perm, c->delta, c->ee, (const double*)c->ewt, n, d_idx, d_scale, d_out, d_skip, (const unsigned char*)nullptr, (const unsigned short*)nullptr);
     } else {
         hipLaunchKernelGGL(newton_iter_kernel<1>, dim3(nsys), dim3(256), 2 * sizeof(double) * n, c->stream, (const double*)c->lu,
-                           (const int*)c->perm, c->delta, c->ee, (const double*)c->ewt, n, d_idx, d_scale, d_out, d_skip, (const unsigned char*)nullptr);
+                           (const int*)c->perm, c->delta, c->ee, (const double*)c->ewt, n, d_idx, d_scale, d_out, d_skip, (const unsigned char*)nullptr, (const unsigned short*)nullptr);
     }
     return post_launch(c, "newton_iter");
 }
@@ -2148,6 +2180,9 @@ void fill_ic_args(idahip_ctx* c, SysArgsIC& a, const double* d_lambda, int icopt
     a.id = (icopt == IDAHIP_IC_YA_YDP) ? c->d_id : nullptr;
 }
 
+// the maps of the ctx's staged factors for the IC solves (ic_solve_body), null where the factors are in the reference layout
+const unsigned short* staged_ord(const idahip_ctx* c) { return lu_staged_on(c) ? (const unsigned short*)c->lu_ord : nullptr; }
+
 // delta-like vector x <- J^-1 x with the ctx's factors, d_out[s] = sum (x_i ewt_i)^2
 int launch_ic_solve(idahip_ctx* c, double* x, const int* d_idx, double* d_out, int nsys) {
     const int n = c->n;
@@ -2165,10 +2200,10 @@ int launch_ic_solve(idahip_ctx* c, double* x, const int* d_idx, double* d_out, i
                            (const double*)c->ewt, n, d_idx, nsys, d_out);
     } else if (n % 2 == 0) {
         hipLaunchKernelGGL(ic_solve_kernel<2>, dim3(nsys), dim3(256), 2 * sizeof(double) * n, c->stream, (const double*)c->lu, (const int*)c->perm, x,
-                           (const double*)c->ewt, n, d_idx, d_out);
+                           (const double*)c->ewt, n, d_idx, d_out, staged_ord(c));
     } else {
         hipLaunchKernelGGL(ic_solve_kernel<1>, dim3(nsys), dim3(256), 2 * sizeof(double) * n, c->stream, (const double*)c->lu, (const int*)c->perm, x,
-                           (const double*)c->ewt, n, d_idx, d_out);
+                           (const double*)c->ewt, n, d_idx, d_out, staged_ord(c));
     }
     return post_launch(c, "ic_solve");
 }
@@ -2322,7 +2357,7 @@ int idahip_ic_trial(idahip_ctx* c, int icopt, const double* hTn, const double* h
     fill_ic_args(c, a, d_lambda, icopt);
     const bool fused = ic_fusable(c);
     if (fused) {
-        a.lu = c->lu; a.perm = c->perm; a.piv = (const long long*)c->piv; a.ewt = c->ewt; a.out = d_out;
+        a.lu = c->lu; a.perm = c->perm; a.ord = staged_ord(c); a.piv = (const long long*)c->piv; a.ewt = c->ewt; a.out = d_out;
     }
     f.launch(IDAHIP_K_SYS, nsys, nullptr, [&] { return launch_ic_sys(c, a, nsys, hTn, hIdx); });
     if (!fused) f.launch(IDAHIP_K_SOLVE, nsys, nullptr, [&] { return launch_ic_solve(c, a.delta, a.idx, d_out, nsys); });
@@ -2901,6 +2936,17 @@ int idahip_set_jac_in_lu(idahip_ctx* c, int on) {
     c->jac_in_lu = on ? 1 : 0;
     return 0;
 }
+
+int idahip_set_lu_staged(idahip_ctx* c, int on) {
+    if (!c) return -1;
+    if (on && !(c->lu_ord && c->n > TINY_N && c->n <= WP_MAX_ROWS))
+        return fail(c, -2, "idahip_set_lu_staged: staged L is for a dense direct ctx with %d < n <= %d", TINY_N, WP_MAX_ROWS);
+    c->lu_staged = on ? 1 : 0;
+    return 0;
+}
+
+// 1: the ctx's factors are written and read staged from now on; 0: in the reference layout
+int idahip_lu_staged(const idahip_ctx* c) { return c ? (lu_staged_on(c) ? 1 : 0) : -1; }
 
 // 0: nowhere now; 1: in idahip_round_solve alone (never set, n > 448); 2: there and in the list entry points (set to 1)
 int idahip_jac_in_lu(const idahip_ctx* c) { return c ? (jac_in_lu_on(c, true) ? 2 : jac_in_lu_on(c, false) ? 1 : 0) : -1; }

@@ -21,6 +21,15 @@ namespace idahip {
 // J can be formed inside the factorisation on the wave-per-matrix pipeline alone: TINY_N < n <= WP_MAX_ROWS, LU variant 4
 inline bool lu_jac_eligible(const idahip_ctx* c) { return c->n > TINY_N && c->n <= WP_MAX_ROWS && c->lu_variant >= 4; }
 
+// Staged L (idahip_set_lu_staged): the ctx's own factors keep L21 of every super-panel in the order of the live list behind it and
+// the solves permute their right-hand side block by block (LuWs::ord, wg_getrs<.., true>): no row scatter at the end. Needs the
+// wave-per-matrix panels for every super-panel: TINY_N < n <= WP_MAX_ROWS, LU variant 4. Never set: on where n > 448 -- the size it
+// was measured at (profiles/lu_staged_ab.txt) --, below that on request.
+inline bool lu_staged_on(const idahip_ctx* c) {
+    const bool wanted = c->lu_staged > 0 || (c->lu_staged < 0 && c->n > WP_MAX_ROWS - 64);
+    return wanted && c->lu_ord != nullptr && c->n > TINY_N && c->n <= WP_MAX_ROWS && c->lu_variant >= 4;
+}
+
 inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* out, long ostride, long long* piv, long pstride,
                              int* perm, const int* d_idx, int nsys, const int* d_cnt = nullptr, const LuJac* jq = nullptr, int slow_grid = 0) {
     const int n = c->n;
@@ -45,6 +54,8 @@ inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* 
     if (!w.jwzero && c->lu_jwzero && (work == c->jw || out == c->jw))  // the work matrix is about to hold something this flag does not describe
         (void)hipMemsetAsync(c->lu_jwzero, 0, (size_t)c->batch * sizeof(int), c->stream);
     w.l11 = c->lu_l11; w.stamps = c->dbg_stamps; w.out = out; w.ostride = ostride; w.l11ld = 64;
+    const bool staged = out == c->lu && lu_staged_on(c);  // user buffers (idahip_ls_setup) keep the reference layout
+    w.ord = staged ? c->lu_ord : nullptr; w.ordq = (n + 63) / 64; w.perm = perm;
     if (slow_grid <= 0) slow_grid = c->lu_slow_grid;  // (idahip_set_lu_slow_grid holds for every caller)
     const int nslow = slow_grid > 0 ? std::min(slow_grid, nsys) : nsys;
     // (every super-panel of a multiple of 64 rows above 1024 on the super-panel pipeline is lu_superpanel_kernel's: no wave-per-matrix launch)
@@ -177,7 +188,7 @@ inline int lu_factor_batched(idahip_ctx* c, double* work, long wstride, double* 
                 hipLaunchKernelGGL(lu_trail64w_kernel<LU_MAX_N>, dim3(nsys8 * ncb), dim3(256), 0, c->stream, w, k0, nsys, ncb, 1);
         }
     }
-    {
+    if (!staged) {  // (staged L: the panel and trailing launches have written the factors, the maps and perm)
         KTimer kt(c, IDAHIP_K_LU_FINALIZE, nsys);
         hipLaunchKernelGGL(lu_finalize_kernel, dim3(nsys, (n + 31) / 32), dim3(256), 0, c->stream, w, out, ostride, perm, 32, NB,
                            n > LU_MAX_N ? (c->lu_superpanel ? 64 : 8) : 0,  // (8: 16 where <= LU_WIDE_ROWS rows were live)

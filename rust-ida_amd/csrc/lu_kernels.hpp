@@ -62,6 +62,12 @@ struct LuWs {
     unsigned long long* stamps;  // timing builds (-DIDAHIP_STAMPS): time stamps of one launch, null otherwise
     double* out;       // factors in the reference layout (rows at their pivoted positions), column-major n x n
     long ostride;      // elements between consecutive systems in out
+    unsigned short* ord;  // null, or (staged L, idahip_set_lu_staged: out is the ctx's own factors, n <= 512, wave-per-matrix panels) [batch][ordq][n]:
+                       // ord[(b * ordq + q) * n + j] = where entry j of the live list in front of super-panel q goes: k < 64 when the row became
+                       // pivot k of the super-panel, else 64 + its index in the live list behind it. `out` then holds L21 of super-panel q
+                       // (rows k0 + 64 ..) in the order of that live list, and no launch of lu_finalize_kernel follows.
+    int ordq;          // super-panels per system in ord: ceil(n / 64)
+    int* perm;         // with ord (may be null): [batch][n] pivot position -> physical row, what lu_finalize_kernel writes otherwise
 };
 constexpr int L11_STRIDE = 64 * 64;  // elements per system in LuWs::l11
 constexpr int LU_REDO_SLOTS = LU_BIG_MAX_N / 64;  // counters in front of LuWs::redo, one per super-panel
@@ -1125,6 +1131,30 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
 #pragma unroll
             for (int i = 0; i < 4; ++i) creg[i][j] = breg[i][j] + jcj * creg[i][j];
     };
+    // staged L (LuWs::ord; n <= 1024): the workgroup of the first column block also stores the multipliers of every strip it loads to
+    // the factors, rows k0 + 64 + (index in the live list) of the super-panel's 64 columns -- L21 in the order of the live list, from
+    // the registers the loads arrived in: per request 16 consecutive rows of four columns. One wave-uniform branch for everyone else.
+    const bool stl = BUF && w.ord != nullptr && cbi == 0;
+    auto store_L = [&](int s, int h) {  // lreg holds chunk h of strip s
+        if constexpr (BUF) {
+            if (stl) {
+                int ln;
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(ln));
+                const int lr = s * 16 + (ln & 15);
+                const unsigned ovo = ((unsigned)(NB + lr) * 8u + kqn8) | ((unsigned)(mrem - 1 - lr) & OOB);  // (no such row: out of range, dropped)
+                const __amdgpu_buffer_rsrc_t rsO =
+                    __builtin_amdgcn_make_buffer_rsrc(w.out + (long)b * w.ostride + (long)k0 * n + k0, 0, (NB * n - k0) * 8, RSFLAGS);
+#pragma unroll
+                for (int i = 0; i < LPT; ++i) buf_store_f64<tb::NT_TRAIL>(rsO, ovo, (h * KC + 4 * i) * n * 8, lreg[i]);
+            }
+        }
+    };
+    // the same for a column block that leaves before its strips (its pivot rows' entries are all zeros): a plain copy
+    auto copy_L21 = [&]() {
+        double* __restrict__ O = w.out + (long)b * w.ostride;
+        for (int c = wave; c < NB; c += 4)
+            for (int lr = lane; lr < mrem; lr += 64) O[(long)(k0 + c) * n + k0 + NB + lr] = A[(long)(k0 + c) * n + s_live[lr]];
+    };
     auto load_C = [&](int s) {
         if constexpr (JAC) {  // the strip's A values
             unsigned cvo[4];
@@ -1319,6 +1349,7 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
             const int cc = wave * 16 + i;
             if (cc < ncols) O[(long)(cb0 + cc) * n + k0 + lane] = Us[lane][4 * (cc & 15) + (cc >> 4)];
         }
+        if (stl) copy_L21();
         return;
     }
     if (MAXROWS > 1024) {  // large n: most column blocks of a banded matrix have left by now, without having read these
@@ -1449,7 +1480,10 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     TSTAMP(4);
     const unsigned kmask0 = (unsigned)__builtin_amdgcn_readfirstlane((int)s_kmask[0]);
     const unsigned kmask1 = (unsigned)__builtin_amdgcn_readfirstlane((int)s_kmask[1]);
-    if (!JAC && slow && (kmask0 | kmask1) == 0u) return;  // (uniform over the workgroup) U12 of this block is all zeros: nothing to subtract
+    if (!JAC && slow && (kmask0 | kmask1) == 0u) {  // (uniform over the workgroup) U12 of this block is all zeros: nothing to subtract
+        if (stl) copy_L21();
+        return;
+    }
     if (MAXROWS > 1024 && slow) {
         // Large n, U12 nearly empty (a banded matrix: a few columns next to the panel, a few pivot rows): one live row per
         // thread, and only the columns and pivot rows that have a non-zero entry are touched -- the strips below would read
@@ -1543,6 +1577,7 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
     for (int s = s0; s < nstrips; s += sstep) {
 #pragma unroll
         for (int i = 0; i < LPT; ++i) Lw[4 * i + kq][lslot] = lreg[i];
+        store_L(s, 0);
         load_L(s, 1);  // the strip's second k-chunk, in flight behind the first chunk's arithmetic
         double c[4][4];
         int srow[4];
@@ -1563,6 +1598,7 @@ __global__ __launch_bounds__(256, MAXROWS <= 1024 ? 3 : 2) void lu_trail64w_kern
         }
 #pragma unroll
         for (int i = 0; i < LPT; ++i) Lw[4 * i + kq][lslot] = lreg[i];  // same wave, program order: chunk 0's reads are done
+        store_L(s, 1);
         if (s + sstep < nstrips) {  // next strip in flight behind the second chunk
             load_C(s + sstep);
             load_L(s + sstep, 0);

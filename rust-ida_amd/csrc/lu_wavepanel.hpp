@@ -470,15 +470,35 @@ __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void l
         constexpr int S = decltype(st)::value;
         if (pstep[S] >= 0) pos[rowid[S]] = rpos[S];
     });
+    unsigned short* __restrict__ om = w.ord ? w.ord + ((long)b * w.ordq + (k0 >> 6)) * n : nullptr;
     if (lane < wsp) {  // lane = pivot index k: l11[kk * 64 + k] = multiplier of pivot row k for column kk < k
         const double* __restrict__ src = A + (long)k0 * n + prow[k0 + lane];
-        for (int j0 = 0; j0 < lane; j0 += 8) {
-            double v[8];
+        if (om) {
+            // staged L: the read-back takes the pivot row's whole entry in the diagonal block, multipliers and U11 -- the same batches of
+            // eight loads, all of them on every lane -- and stores it to the factors at row k0 + k, its place in the reference layout
+            // (a column's 64 entries: one contiguous segment); the row's physical number goes to the solve's permutation
+            double* __restrict__ O = w.out + (long)b * w.ostride + (long)k0 * n + k0 + lane;
+            for (int j0 = 0; j0 < wsp; j0 += 8) {
+                double v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = (j0 + u < lane) ? src[(long)(j0 + u) * n] : 0.0;
+                for (int u = 0; u < 8; ++u) v[u] = (j0 + u < wsp) ? src[(long)(j0 + u) * n] : 0.0;
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (j0 + u < lane) l11[(j0 + u) * 64 + lane] = v[u];
+                for (int u = 0; u < 8; ++u)
+                    if (j0 + u < wsp) {
+                        O[(long)(j0 + u) * n] = v[u];
+                        if (j0 + u < lane) l11[(j0 + u) * 64 + lane] = v[u];
+                    }
+            }
+            if (w.perm) w.perm[(long)b * n + k0 + lane] = prow[k0 + lane];
+        } else {
+            for (int j0 = 0; j0 < lane; j0 += 8) {
+                double v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = (j0 + u < lane) ? src[(long)(j0 + u) * n] : 0.0;
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (j0 + u < lane) l11[(j0 + u) * 64 + lane] = v[u];
+            }
         }
     }
     int base = 0;
@@ -486,7 +506,10 @@ __global__ __launch_bounds__(64, SLOWK ? 1 : (NS > 0 && NS <= 3 ? 4 : 2)) void l
         constexpr int S = decltype(st)::value;
         const bool al = pstep[S] == BIG;
         const unsigned long long bal = __ballot(al);
-        if (al) live[base + __popcll(bal & ((1ull << lane) - 1ull))] = rowid[S];
+        const int rank = base + __popcll(bal & ((1ull << lane) - 1ull));
+        if (al) live[rank] = rowid[S];
+        // staged L: where entry S * 64 + lane of the live list this super-panel started from goes (LuWs::ord)
+        if (om && pstep[S] >= 0) om[S * 64 + lane] = (unsigned short)(al ? 64 + rank : pstep[S]);
         base += __popcll(bal);
     });
     if constexpr (!SLOWK) return;

@@ -188,7 +188,7 @@ __device__ __forceinline__ void ma_sys_wg_body(ARGS a, MaNetOf<LAWS> m, const do
     if constexpr (ARGS::IC) {
         if (a.lu) {
             __syncthreads();
-            ic_solve_body<VEC>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out);
+            ic_solve_body<VEC>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out, a.ord);
         }
     }
 }

@@ -48,6 +48,7 @@ struct SysArgsIC : SysArgs {
     // delta <- LU^-1 delta with the ctx's factors and out[s] = sum_i (delta_i ewt_i)^2, left to right
     const double* lu = nullptr;
     const int* perm = nullptr;        // n > 8
+    const unsigned short* ord = nullptr;  // n > 8, staged L (idahip_set_lu_staged): the factors' maps, LuWs::ord
     const long long* piv = nullptr;   // n <= 8
     const double* ewt = nullptr;
     double* out = nullptr;
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(256) void linear_sys_kernel(ARGS a, const double* _
     if constexpr (ARGS::IC) {
         if (a.lu) {  // delnew = J^-1 F and its norm, on the residual this workgroup has just left in a.delta
             __syncthreads();
-            ic_solve_body<VEC>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out);
+            ic_solve_body<VEC>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out, a.ord);
         }
     }
 }
@@ -309,7 +310,7 @@ __device__ __forceinline__ void stencil_sys_body(ARGS a, const double* __restric
     if constexpr (ARGS::IC) {
         if (a.lu) {  // (dynamic LDS: 2 n doubles)
             __syncthreads();
-            ic_solve_body<VEC>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out);
+            ic_solve_body<VEC>(a.lu, a.perm, a.delta, a.ewt, n, b, a.out, a.ord);
         }
     }
 }

@@ -45,9 +45,22 @@ __device__ __forceinline__ double seq_sum_lds(const double* sq, int n) {
 // its 2 n / 64 diagonal solves, and each of those was eight dependent round trips to memory (eight columns loaded, eight
 // steps, ...): 17 us per block at n = 4096. The block a solve needs is instead fetched by all threads while the sweep before
 // it streams (the factors are read-only), and the solve reads LDS.
-template <int VEC, int T = 256>
+// SL (T == 256, n <= 512; staged L, idahip_set_lu_staged): the factors hold L21 of block column q in the order of the live list behind
+// super-panel q (LuWs::ord, lu_kernels.hpp) and bs arrives in PHYSICAL row order. In front of forward block q the entries bs[kb .. n)
+// -- in the order of the live list in front of the super-panel -- move where its map sends them: the 64 pivots to kb .. kb + 63 in pivot
+// order, the others behind them in the order of the next live list (registers, barrier, LDS, barrier). The diagonal solve and the
+// sweep then read rows kb .. n of the block column exactly as they do in the reference layout, every b_i receives its updates in
+// the same ascending k, and bs ends the forward pass in pivot order: the backward pass is the same code. ord = the system's maps,
+// [ceil(n / 64)][n]. A thread needs two entries per block, at most sixteen per solve. They are NOT all fetched at kernel start: held in
+// registers across the `unroll 1` block loop they would be an array indexed at run time (scratch, or eight more live VGPRs in a
+// kernel that is asked for four workgroups per CU), and every __syncthreads() waits for all loads in flight anyway, so an early
+// request buys nothing past the next barrier. Instead block q + 1's two entries are requested right behind block q's second barrier:
+// the load travels with the diagonal block's first column group and has a whole diagonal solve and sweep to arrive -- never a
+// dependent load in front of a permutation. (Block 0's entries are requested before the loop, beside nothing: the one exposed trip.)
+template <int VEC, int T = 256, bool SL = false>
 __device__ __forceinline__ void wg_getrs(const double* __restrict__ LU, int n, double* bs, double* dg = nullptr,
-                                         const unsigned char* __restrict__ zmap = nullptr) {
+                                         const unsigned char* __restrict__ zmap = nullptr, const unsigned short* __restrict__ ord = nullptr) {
+    static_assert(!SL || T == 256, "staged L is the 256-thread solve's (n <= 512: two entries of a block's map per thread)");
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -83,10 +96,32 @@ __device__ __forceinline__ void wg_getrs(const double* __restrict__ LU, int n, d
     __shared__ int s_kfin;  // the entries of b the running column block multiplies with are all finite
     auto neg_zero = [](double x) { return __double_as_longlong(x) == (long long)0x8000000000000000ull; };
 
+    int so[2] = {0, 0};  // SL: where entries t and t + 256 of bs[kb .. n) go (the running block's map)
+    auto ld_ord = [&](const int kb) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int j = t + 256 * r;
+            so[r] = (kb < n && j < n - kb) ? (int)ord[(kb >> 6) * n + j] : 0;
+        }
+    };
+    if constexpr (SL) ld_ord(0);
+
     // ---- forward: L y = b, unit diagonal (dense.rs:188-194)
 #pragma unroll 1
     for (int kb = 0; kb < n; kb += 64) {
         const int kw = (n - kb) < 64 ? (n - kb) : 64;
+        if constexpr (SL) {  // (the sweep of the block before ended with a barrier)
+            const int m = n - kb;
+            double pv[2];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) pv[r] = (t + 256 * r < m) ? bs[kb + t + 256 * r] : 0.0;
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                if (t + 256 * r < m && so[r] < m) bs[kb + so[r]] = pv[r];  // (a map is a permutation of 0 .. m - 1; the test keeps one that was never written inside bs)
+            __syncthreads();
+            ld_ord(kb + 64);  // (behind the barrier, which waits for every load in flight: the request travels with the diagonal block's)
+        }
         if (!tb::NODIAG && wave == 0) {  // (tb::NODIAG / tb::NOSWEEP: timing builds of exp_switches.hpp, false in the product)
             const int i = kb + lane;
             double bi = (lane < kw) ? bs[i] : 0.0;
@@ -321,12 +356,14 @@ __global__ __launch_bounds__(256) void wrms_kernel(const double* __restrict__ X,
 // delta = -delta; delta = LU^-1 delta; delta *= scale; ee += delta; out = sum_i (delta_i ewt_i)^2 (sequential).
 // T = 1024 for n >= 2048: one workgroup per system streams 8 n^2 bytes, and with few large systems in a call (config 4: ~128
 // of 134 MB each) 256 threads per system do not keep enough loads in flight to fill the memory system.
-template <int VEC, int T = 256>
+// SL: the ctx's factors are staged (wg_getrs): the right-hand side is taken in physical order, no gather through perm; ord = LuWs::ord.
+template <int VEC, int T = 256, bool SL = false>
 __global__ __launch_bounds__(T, T == 256 ? 4 : 1) void newton_iter_kernel(const double* __restrict__ LU, const int* __restrict__ perm, double* __restrict__ delta,
                                                           double* __restrict__ ee, const double* __restrict__ ewt, int n,
                                                           const int* __restrict__ idx, const double* __restrict__ scale,
                                                           double* __restrict__ out, const int* __restrict__ skip,
-                                                          const unsigned char* __restrict__ zmap /* or null: lu_kernels.hpp, LuWs::zmap */) {
+                                                          const unsigned char* __restrict__ zmap /* or null: lu_kernels.hpp, LuWs::zmap */,
+                                                          const unsigned short* __restrict__ ord = nullptr) {
     extern __shared__ __align__(16) double sm[];
     double* bs = sm;
     double* sq = sm + n;
@@ -334,9 +371,10 @@ __global__ __launch_bounds__(T, T == 256 ? 4 : 1) void newton_iter_kernel(const 
     const int b = idx[blockIdx.x];
     const int t = threadIdx.x;
     const long vb = (long)b * n;
-    for (int i = t; i < n; i += T) bs[i] = -delta[vb + perm[vb + i]];  // neg_mut, then the row permutation
+    for (int i = t; i < n; i += T) bs[i] = -delta[vb + (SL ? i : perm[vb + i])];  // neg_mut, then the row permutation (SL: inside the solve)
     __syncthreads();
-    wg_getrs<VEC, T>(LU + (long)b * n * n, n, bs, T > 256 ? sq : nullptr, zmap ? zmap + (long)b * 4096 : nullptr);  // sq (>= 4096 doubles for T > 256) is free until the solve is done
+    wg_getrs<VEC, T, SL>(LU + (long)b * n * n, n, bs, T > 256 ? sq : nullptr, zmap ? zmap + (long)b * 4096 : nullptr,  // sq (>= 4096 doubles for T > 256) is free until the solve is done
+                         SL ? ord + (long)b * ((n + 63) >> 6) * n : nullptr);
     const double sc = scale[blockIdx.x];
     for (int i = t; i < n; i += T) {
         const double d = bs[i] * sc;  // ida_ls.rs:406-410 (sc == 1.0 exactly when cjratio == 1)
@@ -423,15 +461,22 @@ __global__ void tiny_newton_iter_kernel(const double* LU, const long long* piv, 
 // per system; dynamic LDS: 2 n doubles.
 template <int VEC>
 __device__ __forceinline__ void ic_solve_body(const double* __restrict__ LU, const int* __restrict__ perm, double* x,
-                                              const double* __restrict__ ewt, int n, int b, double* __restrict__ out) {
+                                              const double* __restrict__ ewt, int n, int b, double* __restrict__ out,
+                                              const unsigned short* __restrict__ ord = nullptr /* staged L: LuWs::ord, else null */) {
     extern __shared__ __align__(16) double sm[];
     double* bs = sm;
     double* sq = sm + n;
     const int t = threadIdx.x;
     const long vb = (long)b * n;
-    for (int i = t; i < n; i += 256) bs[i] = x[vb + perm[vb + i]];
-    __syncthreads();
-    wg_getrs<VEC>(LU + (long)b * n * n, n, bs);
+    if (ord) {  // (uniform over the launch; this solve is not the hot one: both forms in one kernel)
+        for (int i = t; i < n; i += 256) bs[i] = x[vb + i];
+        __syncthreads();
+        wg_getrs<VEC, 256, true>(LU + (long)b * n * n, n, bs, nullptr, nullptr, ord + (long)b * ((n + 63) >> 6) * n);
+    } else {
+        for (int i = t; i < n; i += 256) bs[i] = x[vb + perm[vb + i]];
+        __syncthreads();
+        wg_getrs<VEC>(LU + (long)b * n * n, n, bs);
+    }
     for (int i = t; i < n; i += 256) {
         const double d = bs[i];
         x[vb + i] = d;

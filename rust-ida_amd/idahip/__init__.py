@@ -38,7 +38,7 @@ HIP_SYMBOLS = [
     "idahip_dev_alloc", "idahip_dev_free", "idahip_memcpy_h2d", "idahip_memcpy_d2h", "idahip_ls_setup", "idahip_ls_solve",
     "idahip_wrms", "idahip_nls_sys", "idahip_nls_lsetup", "idahip_nls_sys_setup", "idahip_newton_iter", "idahip_newton_iter2", "idahip_init_first", "idahip_scale_phi1",
     "idahip_predict", "idahip_post_newton", "idahip_restore", "idahip_complete_step", "idahip_get_solution", "idahip_get_dky",
-    "idahip_timing_enable", "idahip_timing_get", "idahip_timing_reset", "idahip_set_lu_variant", "idahip_set_jac_in_lu", "idahip_jac_in_lu", "idahip_snapshot_initial",
+    "idahip_timing_enable", "idahip_timing_get", "idahip_timing_reset", "idahip_set_lu_variant", "idahip_set_jac_in_lu", "idahip_jac_in_lu", "idahip_set_lu_staged", "idahip_lu_staged", "idahip_snapshot_initial",
     "idahip_tiny_solve", "idahip_pow_batch", "idahip_round_solve", "idahip_lu_variant",
     "idahip_restore_initial", "idahip_ls_type", "idahip_ls_num_iters", "idahip_ls_res_norm", "idahip_timing_build", "idahip_concurrent_streams", "idahip_release_streams", "idahip_stream_pair_share", "idahip_set_lu_superpanel", "idahip_lu_superpanel", "idahip_set_lu_period", "idahip_lu_period", "idahip_set_lu_count_on_host", "idahip_lu_count_on_host", "idahip_set_lu_slow_grid",
     "idahip_create_band", "idahip_band", "idahip_set_host_band_problem", "idahip_download_lu_band", "idahip_ls_setup_band", "idahip_ls_solve_band",
@@ -160,6 +160,8 @@ def load():
     H.idahip_set_lu_variant.argtypes = [vp, ci]
     H.idahip_set_jac_in_lu.argtypes = [vp, ci]
     H.idahip_jac_in_lu.argtypes = [vp]
+    H.idahip_set_lu_staged.argtypes = [vp, ci]
+    H.idahip_lu_staged.argtypes = [vp]
     H.idahip_pow_batch.argtypes = [vp, dp, dp, dp, C.c_size_t]
     H.idahip_newton_iter2.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, i32p, i32p, ci]
     H.idahip_set_host_problem.argtypes = [vp, RES_FN, JAC_FN, vp]
@@ -888,6 +890,17 @@ class Ctx:
         or never set with n <= 448), 1 in the device lock-step rounds alone (never set, n > 448: nls_lsetup, nls_sys_setup and the
         host stepper do NOT take the path), 2 in the rounds and in those calls (set_jac_in_lu(True))."""
         return int(self._chk(self.H.idahip_jac_in_lu(self.h), "jac_in_lu"))
+
+    def set_lu_staged(self, on=True):
+        """Dense direct ctx, 8 < n <= 512: the ctx's own factors keep L below each diagonal block in the factorisation's elimination
+        order (no row scatter at the end; the solves permute their right-hand side with per-system maps) or in the reference
+        layout. Never set: staged where n > 448. Bit-identical results either way; download_lu returns the reference layout under
+        both. Set every system up again after changing it. Refused where the ctx is not eligible."""
+        self._chk(self.H.idahip_set_lu_staged(self.h, int(bool(on))), "set_lu_staged")
+
+    def lu_staged(self):
+        """1 when the ctx's own factors are written and read staged now, 0 in the reference layout."""
+        return int(self._chk(self.H.idahip_lu_staged(self.h), "lu_staged"))
 
     # --- measurement
     def timing(self, on):
