@@ -397,6 +397,17 @@ impl Ctx {
         self.check(rc).map(|_| (nnz as usize, ml as usize, mu as usize))
     }
 
+    /// A network of n <= 8 species: step on the one-thread stepper (a whole solve call in one launch) instead of the host stepper.
+    /// Off by default; refused for a context of another kind and for n > 8. Every solve call reads it anew.
+    pub fn set_mass_action_tiny(&mut self, on: bool) -> Result<(), Error> {
+        let rc = unsafe { sys::idahip_set_mass_action_tiny(self.raw, on as c_int) };
+        self.check(rc).map(|_| ())
+    }
+
+    pub fn mass_action_tiny(&self) -> bool {
+        unsafe { sys::idahip_mass_action_tiny(self.raw) == 1 }
+    }
+
     pub fn set_problem_params(&mut self, first: usize, params: &[f64], nparam: usize) -> Result<(), Error> {
         assert!(nparam > 0 && params.len() % nparam == 0);
         let rc = unsafe {

@@ -68,7 +68,8 @@ int idaens_set_fused_newton(idaens* e, int on);
  * (IDA_NORMAL, no trace, not a Krylov ctx unless idahip_set_krylov_rounds is on; root functions only of idaens_set_roots' family and at most IDAHIP_MAX_ROOTS = 4 of
  * them, and not in idaens_stream -- with more functions, or with a user callback (idaens_set_root_fn), the host stepper runs and
  * idaens_device_controller_active reports 0; the results are the same):
- *   - small systems (n <= 8: Roberts, Lorenz63): a solve / solve_schedule / stream call is ONE launch in which every system
+ *   - small systems (n <= 8: Roberts, Lorenz63, and reaction networks that opted in with idahip_set_mass_action_tiny, which every
+ *     solve call reads anew): a solve / solve_schedule / stream call is ONE launch in which every system
  *     runs its own time loop (idahip_tiny_solve);
  *   - linear dense, heat, Brusselator and mass-action problems with 8 < n <= 4096: lock-step rounds as below, but enqueued without a host round trip
  *     inside a round -- one synchronisation per round, none in idaens_stream (idahip_round_solve); for n > 1024 one more,
@@ -109,7 +110,7 @@ int idaens_set_root_fn(idaens* e, int nroots, idaens_root_fn fn, void* user);
  *     and towards maxncf together with convergence and setup failures; when the last allowed one is a constraint failure the system
  *     ends with IDAENS_CONSTR_FAIL, which is fatal and sticky like IDAENS_CONV_FAIL;
  *   - every problem kind (host callbacks included), dense and band contexts, both tasks, root finding, schedules and streams work;
- *     Roberts and Lorenz63 keep their one-thread-per-system device stepper; for n > 8 the host stepper runs
+ *     Roberts, Lorenz63 and reaction networks that opted in keep their one-thread-per-system device stepper; for n > 8 the host stepper runs
  *     (idaens_device_controller_active reports 0): the device lock-step rounds have no constraint check.
  * Refused (negative return with a text, nothing launched): any solve call on a ctx with constraints AND difference-quotient
  * Jacobians (C IDA flips the increments' signs there), and idaens_calc_ic on a ctx with constraints (C IDA's line search has a

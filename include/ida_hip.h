@@ -347,6 +347,16 @@ int idahip_mass_action_pattern(idahip_ctx* ctx, int* nnz, int* ml, int* mu);
  * column-major, every position outside the pattern +0.0. The kernel of idahip_nls_lsetup launched for one system into a buffer of its
  * own: the ctx's work matrices and factors are left alone. */
 int idahip_mass_action_jac(idahip_ctx* ctx, int sys, double cj, double* hJ);
+/* A network of n <= 8 species on the ONE-THREAD STEPPER (idahip_tiny_solve below). Off by default: with the switch off nothing
+ * changes -- idahip_tiny_solve refuses the ctx and libidaens steps it on the host stepper. With it on, idahip_tiny_solve takes the ctx
+ * (polynomial or with rate laws; analytic or difference-quotient Jacobians; roots, constraints, idaens_stream as for the built-in
+ * kinds) and libidaens' device controller runs it there: a whole solve call in one launch, one thread per system interpreting the
+ * network's tables. Per system the operations, their order and every counter are the host stepper's.
+ * idahip_set_mass_action_tiny returns -2 with a text (and changes nothing) on a ctx of another kind, for n > 8 and on a band or
+ * Krylov ctx. It may be called before or after the network is set, and between solve calls.
+ * idahip_mass_action_tiny: 1 on, 0 off, -1 for a null ctx. */
+int idahip_set_mass_action_tiny(idahip_ctx* ctx, int on);
+int idahip_mass_action_tiny(const idahip_ctx* ctx);
 /* LINEAR_DENSE data, systems [first, first+count): hA, hB [count][n*n] column-major, hC [count][n] */
 int idahip_set_linear_dense(idahip_ctx* ctx, int first, int count, const double* hA, const double* hB, const double* hC);
 /* IDAHIP_HOST_CALLBACK: the problem's callbacks (both required) and the pointer handed back to them */
@@ -536,7 +546,8 @@ int idahip_ic_trial(idahip_ctx* ctx, int icopt, const double* hTn, const double*
 int idahip_ic_accept(idahip_ctx* ctx, int icopt, const int32_t* hIdx, int nsys);
 int idahip_ic_commit(idahip_ctx* ctx, int32_t* hEwtBad, const int32_t* hIdx, int nsys);
 
-/* ---- device-resident stepper for small systems (n <= 8, IDAHIP_ROBERTS / IDAHIP_LORENZ63) ----
+/* ---- device-resident stepper for small systems (n <= 8: IDAHIP_ROBERTS / IDAHIP_LORENZ63, and an IDAHIP_MASS_ACTION ctx with
+ * idahip_set_mass_action_tiny on) ----
  * The whole of Ida::solve (src/impl_solve.rs:69-376: first-call block, loop-top checks, Ida::step with its attempt loop,
  * Newton::solve, error test, complete_step, stop tests and the interpolation to tout), for every system of the ctx, in ONE
  * launch: one thread per IVP runs its own time loop, the step-size and order controller included. The

@@ -165,6 +165,7 @@ struct idahip_ctx {
     idahip::MaLawNet* ma_law = nullptr;  // the same network with its factors (idahip_set_rate_network with nfac > 0), else null
     int ma_nnz = 0, ma_ml = 0, ma_mu = 0;
     int ma_force_wg = 0;  // measurements: the workgroup-per-system residual at every n (IDAHIP_MA_WG, read at idahip_create)
+    int ma_tiny = 0;      // idahip_set_mass_action_tiny: idahip_tiny_solve takes this ctx (n <= TINY_N); off by default
     idahip_res_fn cb_res = nullptr;                   // HOST_CALLBACK
     idahip_jac_fn cb_jac = nullptr;
     idahip_band_jac_fn cb_bjac = nullptr;             // HOST_CALLBACK on a band ctx

@@ -17,6 +17,7 @@
 #include "ic_kernels.hpp"
 #include "krylov_kernels.hpp"
 #include "tiny_ida.hpp"
+#include "tiny_net_ida.hpp"
 #include "round_ida.hpp"
 
 using namespace idahip;
@@ -786,6 +787,17 @@ int idahip_mass_action_pattern(idahip_ctx* c, int* nnz, int* ml, int* mu) {
     if (mu) *mu = c->ma_mu;
     return 0;
 }
+
+int idahip_set_mass_action_tiny(idahip_ctx* c, int on) {
+    if (!c) return -1;
+    if (c->kind != IDAHIP_MASS_ACTION) return fail(c, -2, "idahip_set_mass_action_tiny: not an IDAHIP_MASS_ACTION ctx (kind %d)", (int)c->kind);
+    if (c->n > TINY_N) return fail(c, -2, "idahip_set_mass_action_tiny: n = %d, the one-thread stepper takes n <= %d", c->n, TINY_N);
+    if (c->band || c->krylov) return fail(c, -2, "idahip_set_mass_action_tiny: not on a band or Krylov ctx");
+    c->ma_tiny = on ? 1 : 0;
+    return 0;
+}
+
+int idahip_mass_action_tiny(const idahip_ctx* c) { return c ? c->ma_tiny : -1; }
 
 int idahip_set_host_problem(idahip_ctx* c, idahip_res_fn res, idahip_jac_fn jac, void* user) {
     if (int rc = refuse_krylov(c, "idahip_set_host_problem")) return rc;
@@ -2483,8 +2495,10 @@ int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_
     DevGuard dev_guard__(c);
     if (!c) return -1;
     if (int rca = stepper_call_args(c, hSys, sys_bytes, call, hRoundsDone, hAcc, hAcc)) return rca;
-    if (c->n != 3 || (c->kind != IDAHIP_ROBERTS && c->kind != IDAHIP_LORENZ63))
-        return fail(c, -2, "the device-resident stepper takes the Roberts and Lorenz63 problems (n = 3)");
+    const bool network = c->kind == IDAHIP_MASS_ACTION && c->ma_tiny;  // (the switch is granted for n <= TINY_N alone)
+    if (!network && (c->n != 3 || (c->kind != IDAHIP_ROBERTS && c->kind != IDAHIP_LORENZ63)))
+        return fail(c, -2, "the device-resident stepper takes the Roberts and Lorenz63 problems (n = 3), and an IDAHIP_MASS_ACTION ctx with n <= %d that opted in (idahip_set_mass_action_tiny)", TINY_N);
+    if (int rcu = ma_unset(c, "idahip_tiny_solve")) return rcu;
     if (c->jac_dq && !c->h_constr.empty()) return fail(c, -2, "difference-quotient Jacobians and constraints do not combine (DESIGN.md section 4g)");
     const int batch = c->batch, n = c->n;
     int rc = stepper_call_begin(c, "idahip_tiny_solve", hSys, call, hYout || hYPout);
@@ -2510,30 +2524,54 @@ int idahip_tiny_solve(idahip_ctx* c, void* hSys, size_t sys_bytes, const idahip_
         // systems per wavefront (64, 32, ... 1) that keep the wavefront count at or below one per CU. Config 2 (1024 systems,
         // same box): 64 per wavefront 57.3 M Newton iterations/s in the stream (67.1 M whole pass), 16: 63.1 (70.5), 4: 70.9 (75.8),
         // 1: 65.6 (67.5). IDAHIP_TINY_SPW overrides (measurements). The per-system program is the same: results do not depend on it.
+        // LDS of one system: its controller record, and its vectors too when the device grants that much
+        const size_t lds_sys = sizeof(idactl::SysCore) + sizeof(double) * tiny_lds_doubles(n);
         int spw = 64;
         {
             const int simds = c->simds > 0 ? c->simds : 1024;
             while (spw > 1 && (long)(batch + spw / 2 - 1) / (spw / 2) <= simds / 4) spw >>= 1;
+            // A network's system grows with n (1184 B at n = 3, 2224 B at n = 8: 64 of those leave one wavefront per CU), so a network's
+            // wavefront is also bounded by LDS: the widest of which four workgroups fit a CU (TINY_NET_LDS_PER_WG, tiny_net_ida.hpp).
+            // Where the batch does not fill the device the rule above has gone below the bound already.
+            // Measured (tools/network_tiny_ab.py --spw, profiles/network_tiny_spw.json):
+            // lorenz, n = 3, B = 65536, seconds (medians of 7, same box): 8 0.05425, 16 0.03877, 32 0.03729, 64 0.03755, rule 0.03758
+            // enzyme8, n = 8, B = 65536, seconds (medians of 7, same box): 8 0.08500, 16 0.07345, 32 0.06917, 64 0.07092, rule 0.07366
+            // (the rule is 32 at n = 3 and 16 at n = 8). The bound is not the best one at n = 8: 32 systems per wavefront, two workgroups
+            // per CU, are 6 % faster there than the 16 that keep four resident. Lifting it is a follow-up (DESIGN.md section 4m+).
+            if (network)
+                while (spw > 1 && (size_t)spw * lds_sys > TINY_NET_LDS_PER_WG) spw >>= 1;
             if (const char* e = std::getenv("IDAHIP_TINY_SPW")) {
                 const int v = (int)std::strtol(e, nullptr, 10);
                 if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) spw = v;
             }
         }
-        // LDS: the controller records of a workgroup, and the systems' vectors too when the device grants that much
-        const size_t lds_state = (size_t)spw * sizeof(idactl::SysCore), lds_all = lds_state + (size_t)spw * sizeof(double) * tiny_lds_doubles(n);
+        const size_t lds_state = (size_t)spw * sizeof(idactl::SysCore), lds_all = (size_t)spw * lds_sys;
         // instantiations: problem x (root finding compiled in | out -- the bracketing code costs the plain stepper registers)
-        const bool roots = call->nroots > 0;
-        // and, for each, a twin with the constraint check compiled in (the plain kernels come out as they were without it)
-        const bool constr = !c->h_constr.empty();
-        auto kern = c->kind == IDAHIP_ROBERTS ? (roots ? tiny_ida_kernel<IDAHIP_ROBERTS, true, false> : tiny_ida_kernel<IDAHIP_ROBERTS, false, false>)
-                                              : (roots ? tiny_ida_kernel<IDAHIP_LORENZ63, true, false> : tiny_ida_kernel<IDAHIP_LORENZ63, false, false>);
-        if (constr)
-            kern = c->kind == IDAHIP_ROBERTS ? (roots ? tiny_ida_kernel<IDAHIP_ROBERTS, true, true> : tiny_ida_kernel<IDAHIP_ROBERTS, false, true>)
-                                             : (roots ? tiny_ida_kernel<IDAHIP_LORENZ63, true, true> : tiny_ida_kernel<IDAHIP_LORENZ63, false, true>);
-        const int lds_vec = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * (sizeof(idactl::SysCore) + sizeof(double) * tiny_lds_doubles(n)))) == hipSuccess ? 1 : 0;
-        if (!lds_vec) (void)hipGetLastError();
-        const size_t shm = lds_vec ? lds_all : lds_state;
-        hipLaunchKernelGGL(kern, dim3((batch + spw - 1) / spw), dim3(spw), shm, c->stream, a, lds_vec, constr ? (const double*)c->d_constr : (const double*)nullptr);
+        // x (the constraint check compiled in | out: the plain kernels come out as they were without it)
+        const bool roots = call->nroots > 0, constr = !c->h_constr.empty();
+        const double* dconstr = constr ? (const double*)c->d_constr : (const double*)nullptr;
+        auto launch = [&](auto kern, auto... more) {
+            const int lds_vec = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * lds_sys)) == hipSuccess ? 1 : 0;
+            if (!lds_vec) (void)hipGetLastError();
+            hipLaunchKernelGGL(kern, dim3((batch + spw - 1) / spw), dim3(spw), lds_vec ? lds_all : lds_state, c->stream, a, lds_vec, dconstr, more...);
+        };
+        if (!network) {
+            auto kern = c->kind == IDAHIP_ROBERTS ? (roots ? tiny_ida_kernel<IDAHIP_ROBERTS, true, false> : tiny_ida_kernel<IDAHIP_ROBERTS, false, false>)
+                                                  : (roots ? tiny_ida_kernel<IDAHIP_LORENZ63, true, false> : tiny_ida_kernel<IDAHIP_LORENZ63, false, false>);
+            if (constr)
+                kern = c->kind == IDAHIP_ROBERTS ? (roots ? tiny_ida_kernel<IDAHIP_ROBERTS, true, true> : tiny_ida_kernel<IDAHIP_ROBERTS, false, true>)
+                                                 : (roots ? tiny_ida_kernel<IDAHIP_LORENZ63, true, true> : tiny_ida_kernel<IDAHIP_LORENZ63, false, true>);
+            launch(kern);
+        } else {  // a network: polynomial | with rate laws, and the same twins
+            auto net = [&](auto laws, const auto& m) {
+                constexpr bool L = decltype(laws)::value;
+                auto kern = roots ? tiny_net_ida_kernel<L, true, false> : tiny_net_ida_kernel<L, false, false>;
+                if (constr) kern = roots ? tiny_net_ida_kernel<L, true, true> : tiny_net_ida_kernel<L, false, true>;
+                launch(kern, m, (const double*)c->params, n);
+            };
+            if (ma_laws(c)) net(std::true_type{}, *c->ma_law);
+            else net(std::false_type{}, *c->ma);
+        }
         if ((rc = post_launch(c, "tiny_ida"))) return rc;
     }
     if ((rc = stepper_call_end(c, hSys, call, hRoundsDone, hAcc, hYout, hYPout))) return rc;

@@ -155,6 +155,31 @@ struct TinyVecConstr : TinyVec {
     }
 };
 
+// Newton::solve over a backend N that supplies s, nls_sys, lsetup and newton_iter (TinyNewton below, TinyNetNewton of
+// tiny_net_ida.hpp). The flow is ida_controller.hpp's (newton_begin / newton_after_ctest); here: restart = the loop's first block
+// again, iterate = sys(y) and the loop's body again, done = return
+template <class N>
+__device__ __forceinline__ void tiny_newton_solve(const N& nb) {
+    idactl::SysCore& s = nb.s;
+    bool restart = true;
+    for (;;) {
+        if (restart) {
+            nb.nls_sys(true);  // sys(y0), y <- y0 = 0 (newton.rs:73)
+            if (s.call_lsetup) idactl::after_lsetup(s, nb.lsetup());
+            if (!idactl::newton_begin(s, s.call_lsetup)) return;
+            restart = false;
+        }
+        const double delnrm = nb.newton_iter();
+        s.niters += 1;
+        bool converged = false;
+        const int ret = idactl::conv_test(s, delnrm, &converged);
+        const idactl::NewtonNext next = idactl::newton_after_ctest(s, ret, converged);
+        if (next == idactl::NEWTON_DONE) return;
+        if (next == idactl::NEWTON_ITERATE) nb.nls_sys(false);  // sys(y)
+        else restart = true;
+    }
+}
+
 // Newton::solve for one attempt of one small system, in the owning thread (newton.rs:51-167 as ensemble_ida.cpp's
 // newton_solve_batched runs it for one system; tiny_sys_kernel / tiny_jac_kernel / tiny_getrf / tiny_newton_iter_kernel)
 template <int KIND>
@@ -223,27 +248,7 @@ struct TinyNewton {
         }
         return sqrt(acc / (double)n);
     }
-    // the flow is ida_controller.hpp's (newton_begin / newton_after_ctest); here: restart = the loop's first block again, iterate =
-    // sys(y) and the loop's body again, done = return
-    __device__ void solve() const {
-        bool restart = true;
-        for (;;) {
-            if (restart) {
-                nls_sys(true);  // sys(y0), y <- y0 = 0 (newton.rs:73)
-                if (s.call_lsetup) idactl::after_lsetup(s, lsetup());
-                if (!idactl::newton_begin(s, s.call_lsetup)) return;
-                restart = false;
-            }
-            const double delnrm = newton_iter();
-            s.niters += 1;
-            bool converged = false;
-            const int ret = idactl::conv_test(s, delnrm, &converged);
-            const idactl::NewtonNext next = idactl::newton_after_ctest(s, ret, converged);
-            if (next == idactl::NEWTON_DONE) return;
-            if (next == idactl::NEWTON_ITERATE) nls_sys(false);  // sys(y)
-            else restart = true;
-        }
-    }
+    __device__ void solve() const { tiny_newton_solve(*this); }
 };
 
 // doubles of LDS one system's vectors take: phi[6], yy, yp, yypredict, yppredict, ewt, ee, delta, savres (14 n), the Jacobian /

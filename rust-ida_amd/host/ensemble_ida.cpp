@@ -744,6 +744,8 @@ int device_ctl_applies(const idaens* e, const SolveCall& C) {
     if (kry)  // (constraints are refused on a Krylov ctx; no LU: the variant does not matter)
         return (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D || k == IDAHIP_BRUSS1D)) ? 2 : 0;
     if (e->n <= 8 && (k == IDAHIP_ROBERTS || k == IDAHIP_LORENZ63)) return 1;
+    // a reaction network of that size runs there when its ctx opted in (idahip_set_mass_action_tiny, read anew by every solve call)
+    if (e->n <= 8 && k == IDAHIP_MASS_ACTION && idahip_mass_action_tiny(e->ctx) == 1) return 1;
     if (idahip_constraints(e->ctx, nullptr) == 1) return 0;  // the lock-step device rounds have no constraint check
     if (e->n > 8 && e->n <= 4096 && (k == IDAHIP_LINEAR_DENSE || k == IDAHIP_HEAT1D || k == IDAHIP_BRUSS1D || k == IDAHIP_MASS_ACTION) && idahip_lu_variant(e->ctx) >= 4) return 2;
     return 0;

@@ -53,6 +53,7 @@ HIP_SYMBOLS = [
     "idahip_set_krylov_rounds", "idahip_krylov_rounds", "idahip_krylov_rounds_put_counters", "idahip_krylov_rounds_get_counters",
     "idahip_set_suppress_alg", "idahip_suppress_alg", "idahip_wrms_masked",
     "idahip_set_mass_action", "idahip_mass_action_pattern", "idahip_mass_action_jac", "idahip_set_rate_network",
+    "idahip_set_mass_action_tiny", "idahip_mass_action_tiny",
     "idahip_reinit",
 ]
 ENS_SYMBOLS = [
@@ -127,6 +128,8 @@ def load():
     H.idahip_set_rate_network.argtypes = [vp, ci, i32p, ci, i32p, ci, ci, i32p, i32p, dp, dp]
     H.idahip_mass_action_pattern.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     H.idahip_mass_action_jac.argtypes = [vp, ci, cd, dp]
+    H.idahip_set_mass_action_tiny.argtypes = [vp, ci]
+    H.idahip_mass_action_tiny.argtypes = [vp]
     H.idahip_upload.argtypes = [vp, ci, ci, ci, dp]
     H.idahip_download.argtypes = [vp, ci, ci, ci, dp]
     H.idahip_download_lu.argtypes = [vp, ci, dp, i64p]
@@ -510,6 +513,14 @@ class Ctx:
         for q, s in enumerate(idx):  # (idahip_mass_action_jac is an inspection call: one system at a time)
             self._chk(self.H.idahip_mass_action_jac(self.h, int(s), float(cj[q]), _p(J[q])), "mass_action_jac")
         return J
+
+    def set_mass_action_tiny(self, on=True):
+        """A network of n <= 8 species: step on the one-thread stepper (idahip_tiny_solve, a whole solve call in one launch) instead
+        of the host stepper. Off by default; refused for a ctx of another kind and for n > 8. Read anew by every solve call."""
+        self._chk(self.H.idahip_set_mass_action_tiny(self.h, int(bool(on))), "set_mass_action_tiny")
+
+    def mass_action_tiny(self):
+        return bool(self._chk(self.H.idahip_mass_action_tiny(self.h), "mass_action_tiny"))
 
     def set_linear_dense(self, A, B, c, first=0):
         """A, B: [count][n][n] stored column-major per system, i.e. A[s, j, i] = A_s(i, j); c: [count][n]."""
